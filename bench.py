@@ -17,6 +17,7 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC only on t
 import ctypes
 import json
 import os
+import random
 import sys
 import time
 
@@ -331,6 +332,37 @@ def read_prof(_lib):
     return prof, totals, float(ov.value)
 
 
+DUMP_SAMPLE = 131072       # --dump-outputs: values kept per weight tensor (52 trainable tensors -> ~24 MB of the 64 MB allowed)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, last, model_target):
+    """--dump-outputs: what the last timed step handed its caller, as float32 `path/<name>.npy` -- each loss train_step returns
+    (`total_loss` = the summed loss), and `target.<param>` for every trainable weight it updated in place, in the reference's layout
+    (OIHW), tensors of more than DUMP_SAMPLE values as the same seeded sample of positions on every run."""
+    import numpy as np
+    import torch
+    from abr_iod_amd.utils.checkpoint import reference_state_dict
+
+    loss_dict, total = last
+    arrays = dict(loss_dict)
+    arrays["total_loss"] = total
+    sd = reference_state_dict(model_target)
+    rng = np.random.default_rng(0)
+    for name, p in model_target.named_parameters():
+        if p.requires_grad:
+            flat = sd[name].reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                flat = flat[torch.from_numpy(rng.integers(0, flat.numel(), DUMP_SAMPLE)).to(flat.device)]
+            arrays["target." + name] = flat
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    nbytes = sum(v.nbytes for v in arrays.values())
+    assert nbytes <= DUMP_MAX_BYTES, nbytes
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -380,7 +412,12 @@ def main():
     ap.add_argument("--inject-failure", type=int, default=-1,
                     help="(tests of the launcher only) with --rendezvous-only: this rank raises right after the rendezvous while the others enter a "
                          "second collective -- launch_ranks must end them and return non-zero")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step computed (its losses, a fixed sample of the updated "
+                         "trainable weights) as DIR/<name>.npy, float32: the same arguments give the same inputs, so two builds compare output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus))
     pinned = None
@@ -443,6 +480,7 @@ def main():
     n_old_cls, n_new_cls = {"15-5": (15, 5), "10-10": (10, 10), "10-5": (10, 5), "19-1": (19, 1)}[a.task]
     cfg_s, cfg_t = make_cfgs(a.task, dist_type=dist_type, feat=feat, alpha=alpha, beta=beta, gamma=gamma, ims_per_batch=B * world,
                              overrides=("DTYPE", "bfloat16") if a.math in ("bf16", "bf16-all") else ())
+    random.seed(rank)     # the source model's 64-of-128 soften picks draw from python's `random` (generalized_rcnn.py): same picks every run
     model_source, model_target = build_models(cfg_s, cfg_t, seed=0)       # same seed on every rank = broadcast weights
     optimizer = make_optimizer(cfg_t, model_target)
     scheduler = make_lr_scheduler(cfg_t, optimizer)
@@ -502,6 +540,8 @@ def main():
         last = train_step(model_source, model_target, im, tg, optimizer, scheduler, cfg_t, next_images=batch_of(a.warmup + i + 1)[0])
     barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last, model_target)      # before the informational legs below train the models further
     prof = serialised = None
     if time_kernels:
         prof, prof_totals, event_overhead_ms = read_prof(_lib)

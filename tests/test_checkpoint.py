@@ -168,29 +168,24 @@ def test_resume_with_torch_sgd_state(tmp_path):
     topt.load_state_dict(torch.load(ck.get_checkpoint_file(), weights_only=False)["optimizer"])
 
 
-REF = "/root/reference/maskrcnn_benchmark"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_reference_checkpointer_reads_our_file(tmp_path):
-    """Interop pin: the REFERENCE's own load_state_dict loads a file written by ours into the reference's
-    model, and its state_dict then equals what we exported."""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import ref_harness as rh
-    rh.setup()
-    from maskrcnn_benchmark.modeling.detector import build_detection_model as ref_build
-    from maskrcnn_benchmark.utils.model_serialization import load_state_dict as ref_load_state_dict
+def test_reference_checkpointer_reads_our_file(gold, tmp_path):
+    """Interop pin: a file written by ours loads into the REFERENCE's model the way the reference's Checkpointer._load_file /
+    _load_model do it (torch.load + utils/model_serialization.py:72-91: strip "module.", longest-suffix alignment, then
+    model.load_state_dict), and the model's state_dict then equals what we exported.  The reference model's state_dict --
+    every key, shape and dtype, the target at these widths -- is the one tests/golden/e2e_tiny.npz stores (T/), written by the
+    reference itself (tests/golden/make_golden_e2e.py)."""
+    rm_sd = _sd(gold("e2e_tiny"), "T/")
     cfg_s, cfg_t, ms, mt = _models()
     d = str(tmp_path / "ours")
     os.makedirs(d)
     Checkpointer(mt, save_dir=d, save_to_disk=True).save("model_final", trim=True)
-    rcfg = rh.default_cfg("configs/voc/15-5/e2e_faster_rcnn_R_50_C4_4x_RB_Target_model.yaml", TINY)
-    rm = ref_build(rcfg)
-    # (the reference's utils/checkpoint.py itself does not import on this torch -- utils/model_zoo.py:10 -- so call what its
-    #  Checkpointer._load_file/_load_model do: torch.load + utils/model_serialization.py:72 load_state_dict)
-    ref_load_state_dict(rm, torch.load(os.path.join(d, "model_final.pth"), weights_only=False)["model"])
+    loaded = torch.load(os.path.join(d, "model_final.pth"), weights_only=False)["model"]
     ours = reference_state_dict(mt)
-    assert set(rm.state_dict()) == set(ours)
-    for k, v in rm.state_dict().items():
-        assert torch.equal(v, ours[k]), k
+    assert set(rm_sd) == set(ours)
+    # every key of the reference's model takes the file's tensor of the same name (none keeps its initial value)
+    amap = align_keys(list(rm_sd), list(loaded))
+    assert amap == {k: k for k in rm_sd}
+    for k, v in rm_sd.items():
+        got = loaded[amap[k]]
+        assert got.shape == v.shape and got.dtype == v.dtype, k      # what load_state_dict's copy_ needs
+        assert torch.equal(got, ours[k]), k

@@ -133,11 +133,9 @@ int wino_output_transform(const float* M, int B, int H, int W, int N, const floa
 int wino_outgrad_transform(const float* gy, int B, int H, int W, int N, float* Mg, hipStream_t st, const AmaxRef* amax = nullptr);
 int wino_wgrad_inverse(const float* dU, int N, int C, const float* scale, float* dw, hipStream_t st);
 float* wino_ws(hipStream_t st, size_t floats);
-// cached Winograd-domain weights U [36][N][C] of the tensor at `w` (abr_conv_desc::w_version != 0), transformed on `st` when (w, version)
-// has not been seen; nullptr = no memory (transform into scratch instead)
-float* wino_u_cached(const float* w, int N, int C, int64_t version, hipStream_t st);
-// the cache behind it, for every kind of data derived from a weight tensor (conv_winograd.hip): `fill(buf)` writes `bytes` on `st` (0 = ok)
-enum DerivedKind { DERIVED_WINO_U = 0, DERIVED_X6_PLANES = 1, DERIVED_WINO_U_X6_PLANES = 2, DERIVED_H3_PLANES = 3, DERIVED_WINO_U_H3_PLANES = 4 };
+// the cache of data derived from a weight tensor (conv_winograd.hip), keyed by (w, kind) under abr_conv_desc::w_version != 0: `fill(buf)` writes
+// `bytes` on `st` (0 = ok) when (w, version) has not been seen; nullptr = no memory or the fill failed
+enum DerivedKind { DERIVED_NONE = -1, DERIVED_WINO_U = 0, DERIVED_X6_PLANES = 1, DERIVED_WINO_U_X6_PLANES = 2, DERIVED_H3_PLANES = 3, DERIVED_WINO_U_H3_PLANES = 4 };
 void* derived_cached(const void* w, int kind, size_t bytes, int64_t version, hipStream_t st, const std::function<int(void*)>& fill);
 // The same in two halves, for fills that are launched together (abr_conv_prepare_batch): derived_acquire returns the entry's buffer and, when the
 // entry does not hold `version` yet, a token (the refill is already ordered behind the entry's readers); the caller fills every such buffer on `st`
@@ -146,6 +144,23 @@ void* derived_acquire(const void* w, int kind, size_t bytes, int64_t version, hi
 void derived_commit(void* const* tokens, int n, hipStream_t st);
 // the fill did NOT happen (an error between acquire and commit): the entries hold no version and are evictable / refillable again
 void derived_abandon(void* const* tokens, int n);
+
+// How a convolution runs (conv_igemm.hip): the one place that decides the arithmetic a conv's kernels use, whether its forward pass and its
+// weight gradient take the Winograd path, and which derived weights the forward needs.  Every entry point that must know (abr_conv_forward,
+// abr_conv_wgrad, abr_conv_wino_v_floats, abr_conv_prepare_weights / _batch) asks here.  The only reader of ABR_WINOGRAD_MIN_C / ABR_WINOGRAD_WGRAD.
+struct ConvRoute {
+    int math;            // the forward's effective arithmetic: fp32 for the split arithmetics' stem (Cin % 32 != 0) and for bf16 with Cin % 64 != 0
+    int wgrad_math;      // the weight gradient's: its split-arithmetic kernels take any Cin % 4 == 0, bf16 falls back like the forward's
+    bool fwd_wino;       // the forward takes Winograd F(4x4,3x3)
+    bool wgrad_wino;     // the weight gradient does
+    int64_t v_floats;    // Winograd-domain input the forward keeps for the weight gradient (abr_conv_wino_v_floats): both take Winograd, else 0
+    int kind;            // DerivedKind of the weights the forward's kernels read, DERIVED_NONE = w itself
+    int64_t rows;        // ... derived from a [rows][K] matrix: [Cout][R*S*Cin], or U [36*Cout][Cin] for the Winograd kinds
+    int K;
+    size_t bytes;        // their size
+};
+// d.B == 0 (weight preparation, which knows no activation shape): the 2 GB bound on the Winograd tile tensors is not checked
+ConvRoute conv_route(const abr_conv_desc& d);
 
 // One job of a batched weight preparation (a table of these lives in device memory; workgroup b belongs to the job with first_block <= b).
 struct PrepJob {

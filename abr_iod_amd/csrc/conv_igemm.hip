@@ -483,20 +483,9 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvP p, const fl
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// bf16 math mode (abr_conv_desc::math == ABR_MATH_BF16; BASELINE.json configs[4] "bf16 MFMA backbone"): the SAME implicit GEMM
-// with both operands rounded to bf16 (round-to-nearest-even, v_cvt_pk_bf16_f32) on their way from the fetch registers into LDS
-// and multiplied by v_mfma_f32_32x32x16_bf16 with fp32 accumulation; tensors in HBM stay fp32, so every other kernel of the
-// step is unchanged and the epilogue is shared.  A bf16 x bf16 product is exact in fp32, so the result equals an fp32 (or
-// float64) convolution of the ROUNDED operands up to summation order -- that is what the parity tests check.
-// k-tile = 64 (all of this path's channel counts are multiples of 64; the 4-channel stem stays fp32); LDS rows are 64 bf16 +
-// 8 pad = 144 B, the same conflict-free pitch as the fp32 tiles; a lane's fragment is one ds_read_b128 = 8 consecutive k.
-// 32x32x16 bf16 issues 16x the flops per LDS byte of the fp32 MFMA: the kernel is bound by operand delivery (L2 -> LDS,
-// fp32 sources), not by the matrix pipe.
-// ------------------------------------------------------------------------------------------------------------------------
+// bf16 / fp16 operand vectors of the split arithmetics (bf16x6, f16x3, bf16: conv_igemm_x6w_kernel below)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
@@ -517,169 +506,6 @@ __device__ __forceinline__ void x6_split4(const float a, const float b, const fl
     o0 = make_uint2(*reinterpret_cast<const unsigned*>(&p0), *reinterpret_cast<const unsigned*>(&q0));
     o1 = make_uint2(*reinterpret_cast<const unsigned*>(&p1), *reinterpret_cast<const unsigned*>(&q1));
     o2 = make_uint2(*reinterpret_cast<const unsigned*>(&p2), *reinterpret_cast<const unsigned*>(&q2));
-}
-
-constexpr int BKH = 64;        // k per tile
-constexpr int LDH = BKH + 8;   // LDS row pitch in bf16 elements (144 B)
-
-template <int BM, int BN, int WM, int WN, bool DB>
-__global__ __launch_bounds__(256) void conv_igemm_bf16_kernel(const ConvP p, const float* __restrict__ x, const float* __restrict__ w,
-                                                               float* __restrict__ out) {
-    constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
-    constexpr int NA = BM / 16, NB = BN / 16;  // float4 staging loads per thread (16 rows x 16 float4 per pass)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    abr::prof_stamp_begin(p.prof_ts);
-    constexpr int NBUF = DB ? 2 : 1;
-    __bf16* As = reinterpret_cast<__bf16*>(smem);  // [NBUF][BM][LDH]
-    __bf16* Bs = As + NBUF * BM * LDH;             // [NBUF][BN][LDH]
-
-    const int tile = (int)abr::xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_m = tile / p.tiles_n, tile_n = tile % p.tiles_n;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int kq = tid & 15, srow = tid >> 4;  // 16 B slot inside the 256 B row segment, row srow + 16*i
-
-    constexpr unsigned kOOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w), 0, p.w_bytes, 0x00020000);
-    int a_hi0[NA], a_wi0[NA], a_off0[NA];
-    bool a_ok[NA];
-#pragma unroll
-    for (int i = 0; i < NA; i++) {
-        const int m = m0 + srow + 16 * i;
-        a_ok[i] = m < p.M;
-        const int mm = a_ok[i] ? m : 0;
-        unsigned b, rem, ho, wo;
-        p.d_howo.divmod((unsigned)mm, b, rem);
-        p.d_wo.divmod(rem, ho, wo);
-        a_hi0[i] = (int)ho * p.stride - p.pad;
-        a_wi0[i] = (int)wo * p.stride - p.pad;
-        a_off0[i] = (((int)b * p.H + a_hi0[i]) * p.W + a_wi0[i]) * p.Cin + kq * 4;
-    }
-    unsigned b_off0[NB];
-#pragma unroll
-    for (int i = 0; i < NB; i++) {
-        const int n = n0 + srow + 16 * i;
-        b_off0[i] = n < p.Cout ? (unsigned)(n * p.K + kq * 4) * 4u : kOOB;
-    }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 ra[NA], rb[NB];
-    auto load_tile = [&](int kt) {
-        const int k0 = kt * BKH;
-        unsigned rs, c0, r, s;
-        p.d_cin.divmod((unsigned)k0, rs, c0);
-        p.d_s.divmod(rs, r, s);
-        const int delta = ((int)r * p.W + (int)s) * p.Cin + (int)c0;
-#pragma unroll
-        for (int i = 0; i < NA; i++) {
-            const int hi = a_hi0[i] + (int)r, wi = a_wi0[i] + (int)s;
-            const bool ok = a_ok[i] & ((unsigned)hi < (unsigned)p.H) & ((unsigned)wi < (unsigned)p.W);
-            ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(ok ? (unsigned)(a_off0[i] + delta) * 4u : kOOB), 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < NB; i++) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rw, (int)b_off0[i], k0 * 4, 0);
-    };
-    auto pack = [](const u32x4 v) -> uint2 {
-        const f32x4v f = {__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
-        const bf16x4 h = __builtin_convertvector(f, bf16x4);   // RNE
-        return *reinterpret_cast<const uint2*>(&h);
-    };
-    auto store_tile = [&](int buf) {
-        __bf16* a = As + buf * BM * LDH;
-        __bf16* b = Bs + buf * BN * LDH;
-#pragma unroll
-        for (int i = 0; i < NA; i++) *reinterpret_cast<uint2*>(a + (srow + 16 * i) * LDH + kq * 4) = pack(ra[i]);
-#pragma unroll
-        for (int i = 0; i < NB; i++) *reinterpret_cast<uint2*>(b + (srow + 16 * i) * LDH + kq * 4) = pack(rb[i]);
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
-
-    const int l31 = lane & 31, lh = lane >> 5;
-    const __bf16* a_frag = As + (wm * (TM * 32) + l31) * LDH + lh * 8;
-    const __bf16* b_frag = Bs + (wn * (TN * 32) + l31) * LDH + lh * 8;
-    auto compute_tile = [&](int cur) {
-        const __bf16* af = a_frag + cur * BM * LDH;
-        const __bf16* bf = b_frag + cur * BN * LDH;
-#pragma unroll
-        for (int u = 0; u < BKH / 16; u++) {
-            bf16x8 fa[TM], fb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; i++) fa[i] = *reinterpret_cast<const bf16x8*>(af + i * 32 * LDH + u * 16);
-#pragma unroll
-            for (int j = 0; j < TN; j++) fb[j] = *reinterpret_cast<const bf16x8*>(bf + j * 32 * LDH + u * 16);
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int j = 0; j < TN; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    const int nk = p.K / BKH;
-    load_tile(0);
-    store_tile(0);
-    __syncthreads();
-    int kt = 0;
-    if (!DB) {
-        for (; kt + 1 < nk; kt++) {
-            load_tile(kt + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            compute_tile(0);
-            __syncthreads();
-            store_tile(0);
-            __syncthreads();
-        }
-        compute_tile(0);
-    } else {  // one barrier per k-tile, tile kt+2 fetched right behind the ds_writes of kt+1 (same shape as the fp32 loop)
-        if (kt + 1 < nk) load_tile(kt + 1);
-        for (; kt + 2 < nk; kt++) {
-            const int cur = kt & 1;
-            compute_tile(cur);
-            store_tile(cur ^ 1);
-            load_tile(kt + 2);
-            __syncthreads();
-        }
-        if (kt + 1 < nk) {
-            const int cur = kt & 1;
-            compute_tile(cur);
-            store_tile(cur ^ 1);
-            __syncthreads();
-            kt++;
-        }
-        compute_tile(kt & 1);
-    }
-    __syncthreads();  // the epilogue reuses the operand LDS
-    const unsigned ob = epilogue_rows<TM, TN>(p, acc, smem + wave * (32 * (TN * 32 + EPAD)), m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane, out);
-    if (p.out_amax) abr::h3_amax_emit(p.out_amax, p.out_epoch, ob);
-    abr::prof_stamp_end(p.prof_ts);
-}
-
-template <int BM, int BN, int WM, int WN, bool DB>
-int launch_bf16(const ConvP& p, const float* x, const float* w, float* out, hipStream_t st) {
-    ConvP q = p;
-    q.tiles_m = (p.M + BM - 1) / BM;
-    q.tiles_n = (p.Cout + BN - 1) / BN;
-    q.tiles_pb = q.tiles_m * q.tiles_n;
-    q.nbatch = 1; q.n_full = q.tiles_pb; q.split = 1; q.ws = nullptr; q.cnt = nullptr;
-    constexpr size_t lds_op = sizeof(__bf16) * (DB ? 2 : 1) * (BM + BN) * LDH;
-    constexpr size_t lds_ep = sizeof(float) * 4 * 32 * (BN / WN + EPAD);
-    const size_t lds = lds_op > lds_ep ? lds_op : lds_ep;
-    auto kern = conv_igemm_bf16_kernel<BM, BN, WM, WN, DB>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    q.prof_ts = abr::prof_stamp_slot(abr::PROF_IGEMM_BF16, 2.0 * (double)p.M * (double)p.Cout * (double)p.K);
-    kern<<<(unsigned)q.tiles_pb, 256, lds, st>>>(q, x, w, out);
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1683,28 +1509,7 @@ static void dispatch_igemm(const ConvP& p, const float* x, const float* w, float
     }
 }
 
-// bf16 math mode: biggest tile that still gives every CU a couple of workgroups
-static void dispatch_igemm_bf16(const ConvP& p, const float* x, const float* w, float* out, hipStream_t st) {
-    const int cus = num_cus();
-    const int64_t t128 = (int64_t)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-    const int64_t t12864 = (int64_t)((p.M + 127) / 128) * ((p.Cout + 63) / 64);
-    // double-buffered operand LDS (73.7 KB, still two workgroups per CU by registers) once there are enough k-tiles to pipeline:
-    // +3..10 % on the 128x128 tile (layer4 / RPN shapes).  What bounds these launches is operand delivery, not the matrix pipe:
-    // every workgroup pulls (BM + BN) x K fp32 through L2 (layer4 downsample: 4.3 GB per launch = 13.7 TB/s at 0.31 ms), 16x the
-    // bytes per flop of the fp32 MFMA it replaces.
-    static const int db_mink = getenv("ABR_BF16_DB_MINK") ? atoi(getenv("ABR_BF16_DB_MINK")) : 512;
-    const bool db = p.K >= db_mink;
-    if (p.Cout > 64 && t128 >= 2 * cus) {
-        if (db) launch_bf16<128, 128, 2, 2, true>(p, x, w, out, st);
-        else launch_bf16<128, 128, 2, 2, false>(p, x, w, out, st);
-    } else if (t12864 >= 2 * cus || p.Cout <= 64) {   // (measured: the narrower tiles are faster single-buffered, 3 workgroups / CU)
-        launch_bf16<128, 64, 4, 1, false>(p, x, w, out, st);
-    } else {
-        launch_bf16<64, 64, 2, 2, false>(p, x, w, out, st);
-    }
-}
-
-// The split arithmetics (bf16x6, f16x3, and bf16 as their one-product form): same tile rules as the bf16 mode.  p.w_planes -- the caller's, the
+// The split arithmetics (bf16x6, f16x3, and bf16 as their one-product form): tile choice + launch.  p.w_planes -- the caller's, the
 // library's per-version cache, or planes packed into stream scratch for a one-off call -- is never null here: the weights-direct kernel is the only one.
 static void dispatch_igemm_x6(const ConvP& p, const float* x, const float* /*w*/, float* out, hipStream_t st) {
     const int cus = num_cus();
@@ -1736,50 +1541,86 @@ static void dispatch_igemm_x6(const ConvP& p, const float* x, const float* /*w*/
     }
 }
 
-// stride-1 pad-1 3x3 conv as Winograd F(4x4,3x3): weight + input transforms, 36 batched GEMMs, output transform with the epilogue
-static bool wino_conv(const ConvP& p, const float* x, const float* w, float* out, hipStream_t st) {
+namespace abr {
+ConvRoute conv_route(const abr_conv_desc& d) {
+    static const int min_c = getenv("ABR_WINOGRAD_MIN_C") ? atoi(getenv("ABR_WINOGRAD_MIN_C")) : 128;
+    static const bool wino_wgrad = !(getenv("ABR_WINOGRAD_WGRAD") && atoi(getenv("ABR_WINOGRAD_WGRAD")) == 0);
+    ConvRoute r{};
+    // the split arithmetics' k-tile is 32 wide (the 4-channel stem has none); the bf16 mode covers the Cin % 64 == 0 layers (include/abr_iod_hip.h)
+    const bool bf16_off = d.math == ABR_MATH_BF16 && d.Cin % 64 != 0;
+    r.math = ((d.math == ABR_MATH_BF16X6 || d.math == ABR_MATH_F16X3) && d.Cin % BKX != 0) || bf16_off ? ABR_MATH_F32 : d.math;
+    r.wgrad_math = bf16_off ? ABR_MATH_F32 : d.math;
+    // Winograd F(4x4,3x3) for the wide stride-1 3x3 convs: 4x fewer multiply-adds (RPN 3x3: 1.42 -> 0.50 ms, layer4 conv2 1.14 -> 0.41, layer2 conv2
+    // 0.122 -> 0.073); layer1's 64-channel conv stays direct -- its 36 GEMMs would have K = 64 and the transforms' HBM traffic outweighs the saving.
+    // The tile tensors (T x C floats per Winograd point) must stay below 2 GB (32-bit buffer offsets).
+    const int64_t T = (int64_t)d.B * ((d.H + 3) / 4) * ((d.W + 3) / 4);
+    const bool wide3x3 = min_c > 0 && d.R == 3 && d.S == 3 && d.stride == 1 && d.pad == 1 && d.Cin >= min_c && d.Cout >= 128 &&
+                         T * std::max(d.Cin, d.Cout) * 4 < (int64_t)0x7FFFFFF0;
+    const bool scatter = !((d.out_H <= 0 || d.out_H == d.Ho) && (d.out_W <= 0 || d.out_W == d.Wo) && d.out_sh <= 1 && d.out_sw <= 1);
+    // bf16 stays direct (a Winograd transform of rounded operands is a different, less accurate function than the mode's definition).  The split
+    // arithmetics pack U's 36 Cout x Cin matrices as ONE [36 Cout][Cin] matrix whose 32-row blocks must not straddle two of them: Cout % 32 == 0.
+    r.fwd_wino = wide3x3 && !scatter && !d.residual && r.math != ABR_MATH_BF16 && d.Cin % BK == 0 && d.Cout % 4 == 0 &&
+                 (r.math == ABR_MATH_F32 || d.Cout % 32 == 0);
+    r.wgrad_wino = wide3x3 && wino_wgrad && r.wgrad_math != ABR_MATH_BF16 && d.Cin % 4 == 0;
+    r.v_floats = r.fwd_wino && r.wgrad_wino && d.math != ABR_MATH_BF16 ? 36 * T * d.Cin : 0;
+    // derived weights: the weights-direct kernel's packed planes (bf16 reads plane 0 of bf16x6's), of U for a Winograd conv; fp32 Winograd: U itself
+    const bool h3 = r.math == ABR_MATH_F16X3, x6 = r.math == ABR_MATH_BF16X6 || r.math == ABR_MATH_BF16;
+    r.rows = r.fwd_wino ? (int64_t)36 * d.Cout : d.Cout;
+    r.K = r.fwd_wino ? d.Cin : d.R * d.S * d.Cin;
+    if (r.fwd_wino) r.kind = h3 ? DERIVED_WINO_U_H3_PLANES : (x6 ? DERIVED_WINO_U_X6_PLANES : DERIVED_WINO_U);
+    else if ((h3 ? h3_planes_bytes(r.rows, r.K) : x6_packed_bytes(r.rows, r.K)) >= (int64_t)0xFFFFFFF0) r.kind = DERIVED_NONE;   // (abr_conv_forward refuses it)
+    else r.kind = h3 ? DERIVED_H3_PLANES : (x6 ? DERIVED_X6_PLANES : DERIVED_NONE);
+    r.bytes = r.kind == DERIVED_NONE ? 0 : (size_t)(r.kind == DERIVED_WINO_U ? r.rows * r.K * 4 : (h3 ? h3_packed_bytes(r.rows, r.K) : x6_packed_bytes(r.rows, r.K)));
+    return r;
+}
+}  // namespace abr
+
+static bool wino_split_kind(int kind) { return kind == abr::DERIVED_WINO_U_X6_PLANES || kind == abr::DERIVED_WINO_U_H3_PLANES; }
+
+// Writes the derived weights of route r for the tensor at w into buf on st (0 = ok).  The packed planes of U go through the fp32 U in `u`
+// (rows x K floats; nullptr = this stream's scratch, consumed by the pack launch right behind the transform).
+static int derive_weights(const abr::ConvRoute& r, const float* w, void* buf, float* u, hipStream_t st) {
+    if (r.kind == abr::DERIVED_WINO_U) return abr::wino_weight_transform(w, (int)(r.rows / 36), r.K, static_cast<float*>(buf), st);
+    const float* src = w;
+    if (wino_split_kind(r.kind)) {
+        if (!u) u = abr::wino_ws(st, (size_t)r.rows * r.K);
+        if (!u || abr::wino_weight_transform(w, (int)(r.rows / 36), r.K, u, st)) return 1;
+        src = u;
+    }
+    const bool h3 = r.kind == abr::DERIVED_H3_PLANES || r.kind == abr::DERIVED_WINO_U_H3_PLANES;
+    return h3 ? h3_pack(src, r.rows, r.K, buf, st) : x6_pack(src, r.rows, r.K, buf, st);
+}
+
+// The derived weights route r needs, from the library's per-(w, w_version) cache, filled here on a miss; nullptr = no version, or no memory.
+static const void* cached_weights(const abr::ConvRoute& r, const float* w, int64_t version, hipStream_t st) {
+    if (!version) return nullptr;
+    return abr::derived_cached(w, r.kind, r.bytes, version, st, [&](void* buf) { return derive_weights(r, w, buf, nullptr, st); });
+}
+
+// ... or, without a cache entry, derived into this stream's scratch behind the `own` floats the caller keeps there for itself (*ws = the scratch;
+// a one-off call derives again every time).  nullptr = no memory.
+static const void* conv_weights(const abr::ConvRoute& r, const float* w, int64_t version, hipStream_t st, size_t own = 0, float** ws = nullptr) {
+    const void* cached = cached_weights(r, w, version, st);
+    const size_t mine = cached ? 0 : r.bytes / 4 + (wino_split_kind(r.kind) ? (size_t)r.rows * r.K : 0);
+    float* s = own + mine ? abr::wino_ws(st, own + mine) : nullptr;
+    if (ws) *ws = s;
+    if (cached || !s) return cached;
+    float* buf = s + own;
+    return derive_weights(r, w, buf, buf + r.bytes / 4, st) ? nullptr : buf;
+}
+
+// stride-1 pad-1 3x3 conv as Winograd F(4x4,3x3): weight + input transforms, 36 batched GEMMs, output transform with the epilogue.  The
+// Winograd-domain weights (route r): U for the fp32 kernels, U's packed planes for the weights-direct kernel (bf16x6, f16x3).
+static bool wino_conv(const ConvP& p, const abr::ConvRoute& r, const float* x, const float* w, float* out, hipStream_t st) {
     const int th_n = (p.H + 3) / 4, tw_n = (p.W + 3) / 4;
     const int64_t T = (int64_t)p.B * th_n * tw_n;
-    const size_t nV = (size_t)36 * T * p.Cin, nU = (size_t)36 * p.Cout * p.Cin, nM = (size_t)36 * T * p.Cout;
-    if (T * (int64_t)std::max(p.Cin, p.Cout) * 4 >= (int64_t)0x7FFFFFF0) return false;
-    // Winograd-domain weights: from the per-weight cache when the caller vouches for (w, w_version), else transformed into scratch.
-    // bf16x6: the cached form is U's fragment-packed bf16x3 planes (36 matrices of Cout x Cin back to back: Cout % 32 == 0 makes the
-    // 36 * Cout rows pack as ONE matrix whose 32-row blocks never straddle two batches), fed to the weights-direct kernel.
-    // f16x3: the same with two fp16 planes and one scale per row of U (h3_pack_kernel); without a weight version U is transformed and packed
-    // into scratch on every call.
-    const bool h3 = p.math == ABR_MATH_F16X3, x6 = p.math == ABR_MATH_BF16X6;
-    if ((h3 || x6) && p.Cout % 32 != 0) return false;
-    const void* Up = nullptr;
-    if (x6 && p.w_version) {
-        Up = abr::derived_cached(w, abr::DERIVED_WINO_U_X6_PLANES, (size_t)x6_packed_bytes((int64_t)36 * p.Cout, p.Cin), p.w_version, st, [&](void* buf) {
-            float* Uf = abr::wino_ws(st, nU);   // fp32 U in this stream's scratch, consumed by the pack launch right behind it
-            if (!Uf || abr::wino_weight_transform(w, p.Cout, p.Cin, Uf, st)) return 1;
-            return x6_pack(Uf, (int64_t)36 * p.Cout, p.Cin, buf, st);
-        });
-    }
-    const size_t h3_up_floats = h3 ? (size_t)h3_packed_bytes((int64_t)36 * p.Cout, p.Cin) / 4 : (x6 ? (size_t)x6_packed_bytes((int64_t)36 * p.Cout, p.Cin) / 4 : 0);
-    if (h3 && p.w_version) {
-        Up = abr::derived_cached(w, abr::DERIVED_WINO_U_H3_PLANES, h3_up_floats * 4, p.w_version, st, [&](void* buf) {
-            float* Uf = abr::wino_ws(st, nU);
-            if (!Uf || abr::wino_weight_transform(w, p.Cout, p.Cin, Uf, st)) return 1;
-            return h3_pack(Uf, (int64_t)36 * p.Cout, p.Cin, buf, st);
-        });
-        if (!Up) return false;
-    }
-    float* Uc = (!Up && !h3 && p.w_version) ? abr::wino_u_cached(w, p.Cout, p.Cin, p.w_version, st) : nullptr;
-    const bool have_u = Uc || Up;
-    const size_t h3_extra = ((h3 || x6) && !Up) ? h3_up_floats : 0;   // split arithmetics without a version: fp32 U AND its planes live in scratch
-    float* ws = abr::wino_ws(st, (p.v_out ? 0 : nV) + (have_u ? 0 : nU) + nM + h3_extra);
-    if (!ws) return false;
+    const size_t nV = p.v_out ? 0 : (size_t)36 * T * p.Cin, nM = (size_t)36 * T * p.Cout;
+    float* ws = nullptr;
+    const void* U = conv_weights(r, w, p.w_version, st, nV + nM, &ws);
+    if (!U || !ws) return false;
     float* V = p.v_out ? p.v_out : ws;
-    float* U = Uc ? Uc : ws + (p.v_out ? 0 : nV);
-    float* Mm = ws + (p.v_out ? 0 : nV) + (have_u ? 0 : nU);
-    if (!have_u && abr::wino_weight_transform(w, p.Cout, p.Cin, U, st)) return false;
-    if ((h3 || x6) && !Up) {
-        void* planes = Mm + nM;
-        if (h3 ? h3_pack(U, (int64_t)36 * p.Cout, p.Cin, planes, st) : x6_pack(U, (int64_t)36 * p.Cout, p.Cin, planes, st)) return false;
-        Up = planes;
-    }
+    float* Mm = ws + nV;
+    const bool h3 = p.math == ABR_MATH_F16X3, x6 = p.math == ABR_MATH_BF16X6;
     abr::AmaxRef v_ref{nullptr, 0};
     if (h3) {
         v_ref = abr::h3_amax_alloc();
@@ -1798,35 +1639,19 @@ static bool wino_conv(const ConvP& p, const float* x, const float* w, float* out
     g.v_out = nullptr;
     g.out_amax = nullptr;   // (the conv's output is written by the output transform)
     if (h3) {
-        g.w_planes = Up; g.wp_bytes = (unsigned)h3_planes_bytes(p.Cout, p.Cin); g.wp_bs = (long)h3_planes_bytes(p.Cout, p.Cin); g.wp_nblocks = p.Cout / 32;
-        g.w_scales = reinterpret_cast<const float*>(reinterpret_cast<const char*>(Up) + h3_planes_bytes((int64_t)36 * p.Cout, p.Cin));
+        g.w_planes = U; g.wp_bytes = (unsigned)h3_planes_bytes(p.Cout, p.Cin); g.wp_bs = (long)h3_planes_bytes(p.Cout, p.Cin); g.wp_nblocks = p.Cout / 32;
+        g.w_scales = reinterpret_cast<const float*>(reinterpret_cast<const char*>(U) + h3_planes_bytes((int64_t)36 * p.Cout, p.Cin));
         g.a_amax = v_ref.word; g.a_epoch = v_ref.epoch;
-    } else {
-        g.w_planes = Up; g.wp_bytes = (unsigned)x6_packed_bytes(p.Cout, p.Cin); g.wp_bs = (long)x6_packed_bytes(p.Cout, p.Cin); g.wp_nblocks = p.Cout / 32;
+    } else if (x6) {
+        g.w_planes = U; g.wp_bytes = (unsigned)x6_packed_bytes(p.Cout, p.Cin); g.wp_bs = (long)x6_packed_bytes(p.Cout, p.Cin); g.wp_nblocks = p.Cout / 32;
     }
-    if (p.math == ABR_MATH_BF16X6 || h3) dispatch_igemm_x6(g, V, U, Mm, st);
-    else dispatch_igemm(g, V, U, Mm, st);
+    if (h3 || x6) dispatch_igemm_x6(g, V, nullptr, Mm, st);
+    else dispatch_igemm(g, V, static_cast<const float*>(U), Mm, st);
     const abr::AmaxRef o_ref{p.out_amax, p.out_epoch};
     return abr::wino_output_transform(Mm, p.B, p.H, p.W, p.Cout, p.scale, p.bias, p.relu, p.mask, out, st, p.out_amax ? &o_ref : nullptr) == 0;
 }
 
-static int wino_min_c() {
-    static const int v = getenv("ABR_WINOGRAD_MIN_C") ? atoi(getenv("ABR_WINOGRAD_MIN_C")) : 128;
-    return v;
-}
-
-extern "C" int64_t abr_conv_wino_v_floats(const abr_conv_desc* d) {
-    if (!d || d->math == ABR_MATH_BF16) return 0;
-    static const bool wino_wgrad = !(getenv("ABR_WINOGRAD_WGRAD") && atoi(getenv("ABR_WINOGRAD_WGRAD")) == 0);
-    const bool scatter = !((d->out_H <= 0 || d->out_H == d->Ho) && (d->out_W <= 0 || d->out_W == d->Wo) && d->out_sh <= 1 && d->out_sw <= 1);
-    const bool ok = wino_wgrad && wino_min_c() > 0 && d->R == 3 && d->S == 3 && d->stride == 1 && d->pad == 1 && !scatter && !d->residual &&
-                    d->Cin % BK == 0 && d->Cout % 4 == 0 && d->Cin >= wino_min_c() && d->Cout >= 128 &&
-                    (d->math != ABR_MATH_F16X3 || d->Cout % 32 == 0);   // (f16x3 packs U in 32-row blocks: wino_conv)
-    if (!ok) return 0;
-    const int64_t T = (int64_t)d->B * ((d->H + 3) / 4) * ((d->W + 3) / 4);
-    if (T * (int64_t)std::max(d->Cin, d->Cout) * 4 >= (int64_t)0x7FFFFFF0) return 0;
-    return 36 * T * d->Cin;
-}
+extern "C" int64_t abr_conv_wino_v_floats(const abr_conv_desc* d) { return d ? abr::conv_route(*d).v_floats : 0; }
 
 extern "C" int abr_conv_forward(const abr_conv_desc* d, const float* x, const float* w, float* out, void* stream) {
     ABR_REQUIRE(d && x && w && out, "conv_forward: null pointer");
@@ -1852,7 +1677,7 @@ extern "C" int abr_conv_forward(const abr_conv_desc* d, const float* x, const fl
     p.nbatch = 1; p.tiles_pb = 0; p.a_bs = p.w_bs = p.o_bs = 0;
     p.v_out = d->wino_v;
     p.w_version = d->w_version;
-    p.w_planes = d->math == ABR_MATH_BF16X6 ? d->w_planes : nullptr;   // the caller's own abr_conv_pack_weights(w, Cout, R*S*Cin) planes, if any
+    p.w_planes = nullptr;
     ABR_REQUIRE(x6_packed_bytes(d->Cout, p.K) < (int64_t)0xFFFFFFF0, "conv_forward: weight tensor too large for 32-bit buffer offsets");
     p.wp_bytes = (unsigned)x6_packed_bytes(d->Cout, p.K); p.wp_bs = 0; p.wp_nblocks = (d->Cout + 31) / 32;
     const int64_t xb = (int64_t)d->B * d->H * d->W * d->Cin * 4, wb = (int64_t)d->Cout * p.K * 4;
@@ -1861,9 +1686,9 @@ extern "C" int abr_conv_forward(const abr_conv_desc* d, const float* x, const fl
     p.d_howo.init((unsigned)(p.Ho * p.Wo)); p.d_wo.init((unsigned)p.Wo); p.d_cin.init((unsigned)p.Cin); p.d_s.init((unsigned)p.S);
     hipStream_t st = abr::as_stream(stream);
     ABR_REQUIRE(d->math == ABR_MATH_F32 || d->math == ABR_MATH_BF16 || d->math == ABR_MATH_BF16X6 || d->math == ABR_MATH_F16X3, "conv_forward: unknown math mode");
-    p.math = d->math;
-    if ((p.math == ABR_MATH_BF16X6 || p.math == ABR_MATH_F16X3) && p.Cin % BKX != 0) p.math = ABR_MATH_F32;   // the 4-channel stem: fp32 MFMA
-    p.nprod = 6;
+    const abr::ConvRoute r = abr::conv_route(*d);
+    p.math = r.math;
+    p.nprod = p.math == ABR_MATH_BF16 ? 1 : 6;
     p.a_amax = nullptr; p.a_epoch = 0; p.w_scales = nullptr;
     p.out_amax = reinterpret_cast<unsigned long long*>(d->out_amax); p.out_epoch = d->out_amax_epoch;   // (every kernel's epilogue feeds it)
     if (p.math == ABR_MATH_F16X3) {
@@ -1875,61 +1700,22 @@ extern "C" int abr_conv_forward(const abr_conv_desc* d, const float* x, const fl
         }
         p.a_amax = ar.word; p.a_epoch = ar.epoch;
         p.nprod = 3;
-        p.w_planes = nullptr;
         ABR_REQUIRE(h3_planes_bytes(d->Cout, p.K) < (int64_t)0xFFFFFFF0, "conv_forward: weight tensor too large for 32-bit buffer offsets");
         p.wp_bytes = (unsigned)h3_planes_bytes(d->Cout, p.K);
     }
-    if (d->math == ABR_MATH_BF16 && p.Cin % BKH == 0) {   // (the 4-channel stem has no 64-wide k-tile: it stays fp32)
-        // Round 4: with a weight version the bf16 mode runs on the weights-direct kernels of the default arithmetic, single product (NP = 1): plane 0
-        // of the packed weights (the cache entry bf16x6 uses) IS bf16(w), the first plane of the activation split IS bf16(x).  3x3 convs stay
-        // direct (a Winograd transform of rounded operands is a different, less accurate function than the mode's definition).
-        constexpr bool direct_on = true;   // (ABR_X6_WEIGHTS_DIRECT=0, the in-kernel weight split, was retired in round 6)
-        static const bool bf16_wd = !(getenv("ABR_BF16_WEIGHTS_DIRECT") && atoi(getenv("ABR_BF16_WEIGHTS_DIRECT")) == 0);
-        const void* planes = d->w_planes;
-        if (!planes && p.w_version && direct_on && bf16_wd && p.Cin % BKX == 0)
-            planes = abr::derived_cached(w, abr::DERIVED_X6_PLANES, p.wp_bytes, p.w_version, st, [&](void* buf) { return x6_pack(w, d->Cout, p.K, buf, st); });
-        if (planes && direct_on && bf16_wd) {
-            p.w_planes = planes;
-            p.nprod = 1;
-            dispatch_igemm_x6(p, x, w, out, st);
-            ABR_CHECK_LAUNCH("conv_forward (bf16, weights-direct)");
-            return ABR_OK;
-        }
-        dispatch_igemm_bf16(p, x, w, out, st);
-        ABR_CHECK_LAUNCH("conv_forward (bf16)");
+    if (r.fwd_wino) {
+        ABR_REQUIRE(wino_conv(p, r, x, w, out, st), "conv_forward (winograd): no memory for the scratch or an amax word, or a launch failed");
+        ABR_CHECK_LAUNCH("conv_forward (winograd)");
         return ABR_OK;
     }
-    // Winograd F(4x4,3x3) for the wide stride-1 3x3 convs: 4x fewer multiply-adds (RPN 3x3: 1.42 -> 0.50 ms, layer4 conv2 1.14 ->
-    // 0.41, layer2 conv2 0.122 -> 0.073); layer1's 64-channel conv stays direct -- its 36 GEMMs would have K = 64 and the transforms'
-    // HBM traffic outweighs the saving.
-    if (wino_min_c() > 0 && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && !p.scatter && !p.residual && p.Cin % BK == 0 &&
-        p.Cout % 4 == 0 && p.Cin >= wino_min_c() && p.Cout >= 128) {
-        if (wino_conv(p, x, w, out, st)) {
-            ABR_CHECK_LAUNCH("conv_forward (winograd)");
-            return ABR_OK;
-        }
-    }
-    if (p.math == ABR_MATH_F16X3) {
-        // packed fp16 planes + row scales of (w, w_version) from the library's cache, or packed into this stream's scratch for a one-off call
-        const size_t pb = (size_t)h3_packed_bytes(d->Cout, p.K);
-        const void* planes = p.w_version ? abr::derived_cached(w, abr::DERIVED_H3_PLANES, pb, p.w_version, st, [&](void* buf) { return h3_pack(w, d->Cout, p.K, buf, st); }) : nullptr;
-        if (!planes) {
-            void* scratch = abr::wino_ws(st, pb / 4);
-            ABR_REQUIRE(scratch && h3_pack(w, d->Cout, p.K, scratch, st) == 0, "conv_forward (f16x3): no memory for the weight planes");
-            planes = scratch;
-        }
-        p.w_planes = planes;
-        p.w_scales = reinterpret_cast<const float*>(reinterpret_cast<const char*>(planes) + h3_planes_bytes(d->Cout, p.K));
-        dispatch_igemm_x6(p, x, w, out, st);
-    } else if (p.math == ABR_MATH_BF16X6) {
-        // weights-direct kernel: the packed planes of (w, w_version) come from the library's cache (filled here on a miss: one small launch)
-        if (!p.w_planes && p.w_version)
-            p.w_planes = abr::derived_cached(w, abr::DERIVED_X6_PLANES, p.wp_bytes, p.w_version, st, [&](void* buf) { return x6_pack(w, d->Cout, p.K, buf, st); });
-        if (!p.w_planes) {   // a one-off call: planes into this stream's scratch (the in-kernel weight split of rounds 1-5 made the same three terms)
-            void* scratch = abr::wino_ws(st, (size_t)p.wp_bytes / 4 + 1);
-            ABR_REQUIRE(scratch && x6_pack(w, d->Cout, p.K, scratch, st) == 0, "conv_forward (bf16x6): no memory for the weight planes");
-            p.w_planes = scratch;
-        }
+    // (the weight gradient would read V back from the caller's buffer)
+    ABR_REQUIRE(!d->wino_v, "conv_forward: wino_v given for a conv that does not take the Winograd path (abr_conv_wino_v_floats)");
+    if (p.math != ABR_MATH_F32) {
+        // weights-direct kernel: the caller's own abr_conv_pack_weights(w, Cout, R*S*Cin) planes (bf16x6, bf16), else the route's derived weights
+        p.w_planes = p.math != ABR_MATH_F16X3 ? d->w_planes : nullptr;
+        if (!p.w_planes) p.w_planes = conv_weights(r, w, p.w_version, st);
+        ABR_REQUIRE(p.w_planes, "conv_forward: no memory for the weight planes");
+        if (p.math == ABR_MATH_F16X3) p.w_scales = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.w_planes) + h3_planes_bytes(d->Cout, p.K));
         dispatch_igemm_x6(p, x, w, out, st);
     } else {
         dispatch_igemm(p, x, w, out, st);
@@ -1980,11 +1766,9 @@ extern "C" int abr_conv_tail64_forward(const abr_conv_desc* d2, const abr_conv_d
     ConvP p, q;
     convp_from_desc(d2, p);
     convp_from_desc(d3, q);
-    // packed planes of both weights: the caller's, or the library's per-version cache (filled here on a miss), or packed into stream scratch
+    // packed planes of both weights: the caller's, or the library's per-version cache (filled here on a miss)
     auto planes_of = [&](const abr_conv_desc* d, const float* w, ConvP& c) -> bool {
-        if (c.w_planes) return true;
-        if (d->w_version)
-            c.w_planes = abr::derived_cached(w, abr::DERIVED_X6_PLANES, c.wp_bytes, d->w_version, st, [&](void* buf) { return x6_pack(w, d->Cout, c.K, buf, st); });
+        if (!c.w_planes) c.w_planes = cached_weights(abr::conv_route(*d), w, d->w_version, st);
         return c.w_planes != nullptr;
     };
     ABR_REQUIRE(planes_of(d2, w2, p) && planes_of(d3, w3, q), "conv_tail64_forward: needs w_version != 0 (or caller-packed planes) for both weights");
@@ -2000,49 +1784,21 @@ extern "C" int abr_conv_tail64_forward(const abr_conv_desc* d2, const abr_conv_d
     return ABR_OK;
 }
 
+// a conv's route as weight preparation sees it: no activation shape, no residual / scatter (they never occur on the convs that prepare)
+static abr::ConvRoute prep_route(int Cout, int R, int S, int Cin, int stride, int pad, int math) {
+    abr_conv_desc d{};
+    d.Cout = Cout; d.R = R; d.S = S; d.Cin = Cin; d.stride = stride; d.pad = pad; d.math = math;
+    return abr::conv_route(d);
+}
+
 extern "C" int abr_conv_prepare_weights(const float* w, int Cout, int R, int S, int Cin, int stride, int pad, int math, int64_t w_version,
                                         void* stream) {
     ABR_REQUIRE(w && w_version != 0, "conv_prepare_weights: needs a weight pointer and a non-zero w_version");
     ABR_REQUIRE(Cout > 0 && R > 0 && S > 0 && Cin > 0, "conv_prepare_weights: bad shape");
-    hipStream_t st = abr::as_stream(stream);
-    constexpr bool direct_on = true;   // (ABR_X6_WEIGHTS_DIRECT=0, the in-kernel weight split, was retired in round 6)
-    const int K = R * S * Cin;
-    // the same predicate as abr_conv_forward's Winograd branch (residual / scatter never occur on the convs that prepare)
-    if (wino_min_c() > 0 && math != ABR_MATH_BF16 && R == 3 && S == 3 && stride == 1 && pad == 1 && Cin % BK == 0 && Cout % 4 == 0 &&
-        Cin >= wino_min_c() && Cout >= 128) {
-        if (math == ABR_MATH_F16X3 && Cout % 32 == 0) {
-            const size_t nU = (size_t)36 * Cout * Cin;
-            void* up = abr::derived_cached(w, abr::DERIVED_WINO_U_H3_PLANES, (size_t)h3_packed_bytes((int64_t)36 * Cout, Cin), w_version, st, [&](void* buf) {
-                float* Uf = abr::wino_ws(st, nU);
-                if (!Uf || abr::wino_weight_transform(w, Cout, Cin, Uf, st)) return 1;
-                return h3_pack(Uf, (int64_t)36 * Cout, Cin, buf, st);
-            });
-            ABR_REQUIRE(up != nullptr, "conv_prepare_weights: no memory for the packed Winograd-domain weights");
-        } else if (math == ABR_MATH_F16X3) {
-            void* pl = abr::derived_cached(w, abr::DERIVED_H3_PLANES, (size_t)h3_packed_bytes(Cout, K), w_version, st, [&](void* buf) { return h3_pack(w, Cout, K, buf, st); });
-            ABR_REQUIRE(pl != nullptr, "conv_prepare_weights: no memory for the packed weight planes");
-        } else if (math == ABR_MATH_BF16X6 && direct_on && Cout % 32 == 0) {
-            const size_t nU = (size_t)36 * Cout * Cin;
-            void* up = abr::derived_cached(w, abr::DERIVED_WINO_U_X6_PLANES, (size_t)x6_packed_bytes((int64_t)36 * Cout, Cin), w_version, st, [&](void* buf) {
-                float* Uf = abr::wino_ws(st, nU);
-                if (!Uf || abr::wino_weight_transform(w, Cout, Cin, Uf, st)) return 1;
-                return x6_pack(Uf, (int64_t)36 * Cout, Cin, buf, st);
-            });
-            ABR_REQUIRE(up != nullptr, "conv_prepare_weights: no memory for the packed Winograd-domain weights");
-        } else {
-            ABR_REQUIRE(abr::wino_u_cached(w, Cout, Cin, w_version, st) != nullptr, "conv_prepare_weights: no memory for the Winograd-domain weights");
-        }
-        ABR_CHECK_LAUNCH("conv_prepare_weights");
-    } else if (math == ABR_MATH_F16X3 && Cin % BKX == 0 && h3_planes_bytes(Cout, K) < (int64_t)0xFFFFFFF0) {
-        void* pl = abr::derived_cached(w, abr::DERIVED_H3_PLANES, (size_t)h3_packed_bytes(Cout, K), w_version, st, [&](void* buf) { return h3_pack(w, Cout, K, buf, st); });
-        ABR_REQUIRE(pl != nullptr, "conv_prepare_weights: no memory for the packed weight planes");
-        ABR_CHECK_LAUNCH("conv_prepare_weights");
-    } else if ((math == ABR_MATH_BF16X6 || (math == ABR_MATH_BF16 && Cin % BKH == 0)) && direct_on && Cin % BKX == 0 &&
-               x6_packed_bytes(Cout, K) < (int64_t)0xFFFFFFF0) {
-        void* pl = abr::derived_cached(w, abr::DERIVED_X6_PLANES, (size_t)x6_packed_bytes(Cout, K), w_version, st, [&](void* buf) { return x6_pack(w, Cout, K, buf, st); });
-        ABR_REQUIRE(pl != nullptr, "conv_prepare_weights: no memory for the packed weight planes");
-        ABR_CHECK_LAUNCH("conv_prepare_weights");
-    }
+    const abr::ConvRoute r = prep_route(Cout, R, S, Cin, stride, pad, math);
+    if (r.kind == abr::DERIVED_NONE) return ABR_OK;
+    ABR_REQUIRE(cached_weights(r, w, w_version, abr::as_stream(stream)) != nullptr, "conv_prepare_weights: no memory for the derived weights");
+    ABR_CHECK_LAUNCH("conv_prepare_weights");
     return ABR_OK;
 }
 
@@ -2103,7 +1859,6 @@ extern "C" int abr_conv_prepare_batch(const abr_prep_item* items, int n, void* s
     ABR_REQUIRE(n >= 0 && (n == 0 || items), "conv_prepare_batch: bad args");
     if (n == 0) return ABR_OK;
     hipStream_t st = abr::as_stream(stream);
-    constexpr bool direct_on = true;   // (ABR_X6_WEIGHTS_DIRECT=0, the in-kernel weight split, was retired in round 6)
     std::lock_guard<std::mutex> lock(g_prep_mu);
     PrepTables& T = g_prep_tables[st];
     std::vector<abr::PrepJob> tj, uj, pj, hj, wj;    // transposes, Winograd weight transforms, bf16x3 packings, f16x3 packings, f16x3 Winograd weights straight to planes
@@ -2118,7 +1873,6 @@ extern "C" int abr_conv_prepare_batch(const abr_prep_item* items, int n, void* s
     std::vector<size_t> u_off;                    // per uj entry: offset (floats) of its U inside the scratch
     size_t u_total = 0;
     int tb = 0, ub = 0, pb = 0, hb = 0, hsb = 0, wb = 0, wsb = 0;  // workgroups of the launches (hsb: the f16x3 row-scale launch; wb / wsb: the direct Winograd pack / scale launches)
-    static const bool wino_direct = !(getenv("ABR_PREP_WINO_DIRECT") && atoi(getenv("ABR_PREP_WINO_DIRECT")) == 0);   // 0: through the fp32 U in the scratch (A/B)
     std::vector<int> h_scale_first;               // per hj entry: its first workgroup in the row-scale launch (stored in PrepJob::c once the sources are patched)
     auto add_pack_h3 = [&](const float* src, int64_t rows, int K, void* dst) {
         abr::PrepJob j{};
@@ -2134,55 +1888,39 @@ extern "C" int abr_conv_prepare_batch(const abr_prep_item* items, int n, void* s
         pb += j.gx * j.gy;
         pj.push_back(j);
     };
-    // what abr_conv_prepare_weights derives from tensor `w` ([Cout][R][S][Cin]) of a conv with this geometry: returns 1 when it had to go the per-tensor way
+    // what abr_conv_prepare_weights derives from tensor `w` ([Cout][R][S][Cin]) of a conv with this geometry: returns 1 when it has to go the per-tensor way
     auto derive = [&](const float* w, int Cout, int R, int S, int Cin, int stride, int pad, int math, int64_t ver) -> int {
-        const int K = R * S * Cin;
-        if (wino_min_c() > 0 && math != ABR_MATH_BF16 && R == 3 && S == 3 && stride == 1 && pad == 1 && Cin % BK == 0 && Cout % 4 == 0 &&
-            Cin >= wino_min_c() && Cout >= 128) {
-            const bool h3 = math == ABR_MATH_F16X3;
-            if (!(((math == ABR_MATH_BF16X6 && direct_on) || h3) && Cout % 32 == 0 && Cin % 4 == 0)) return 1;
-            void* tok = nullptr;
-            void* planes = h3 ? abr::derived_acquire(w, abr::DERIVED_WINO_U_H3_PLANES, (size_t)h3_packed_bytes((int64_t)36 * Cout, Cin), ver, st, &tok, &waited)
-                              : abr::derived_acquire(w, abr::DERIVED_WINO_U_X6_PLANES, (size_t)x6_packed_bytes((int64_t)36 * Cout, Cin), ver, st, &tok, &waited);
-            if (!planes) return 1;
-            if (!tok) return 0;   // already there
-            tokens.push_back(tok);
-            if (h3 && wino_direct && Cin % 64 == 0) {   // w -> planes, U never written (conv_winograd.hip: wino_h3_scales / wino_h3_pack)
-                abr::PrepJob j{};
-                j.src = w; j.dst = planes; j.a = Cout; j.b = Cin; j.gx = Cin / 64; j.gy = Cout / 32; j.first_block = wb; j.c = wsb;
-                wb += j.gx * j.gy;
-                wsb += Cout / 4;
-                wj.push_back(j);
-                return 0;
-            }
+        const abr::ConvRoute r = prep_route(Cout, R, S, Cin, stride, pad, math);
+        if (r.kind == abr::DERIVED_NONE) return 0;   // nothing to derive
+        if (r.kind == abr::DERIVED_WINO_U) return 1;
+        void* tok = nullptr;
+        void* dst = abr::derived_acquire(w, r.kind, r.bytes, ver, st, &tok, &waited);
+        if (!dst) return 1;
+        if (!tok) return 0;   // already there
+        tokens.push_back(tok);
+        const bool h3 = r.kind == abr::DERIVED_H3_PLANES || r.kind == abr::DERIVED_WINO_U_H3_PLANES;
+        if (!wino_split_kind(r.kind)) {
+            if (h3) add_pack_h3(w, r.rows, r.K, dst); else add_pack(w, r.rows, r.K, dst);
+            return 0;
+        }
+        if (h3 && Cin % 64 == 0) {   // w -> planes, U never written (conv_winograd.hip: wino_h3_scales / wino_h3_pack)
             abr::PrepJob j{};
-            j.src = w; j.a = Cout; j.b = Cin; j.gx = (int)(((int64_t)Cout * (Cin / 4) + 255) / 256); j.gy = 1; j.first_block = ub;
-            ub += j.gx;
-            uj.push_back(j);
-            u_off.push_back(u_total);
-            // the packing job reads the fp32 U from the scratch: its src is patched in once the scratch address is known
-            if (h3) { add_pack_h3(reinterpret_cast<const float*>(u_total), (int64_t)36 * Cout, Cin, planes); hj.back().c = 1; }
-            else { add_pack(reinterpret_cast<const float*>(u_total), (int64_t)36 * Cout, Cin, planes); pj.back().c = 1; }   // c = 1: src is a scratch offset
-            u_total += (size_t)36 * Cout * Cin;
+            j.src = w; j.dst = dst; j.a = Cout; j.b = Cin; j.gx = Cin / 64; j.gy = Cout / 32; j.first_block = wb; j.c = wsb;
+            wb += j.gx * j.gy;
+            wsb += Cout / 4;
+            wj.push_back(j);
             return 0;
         }
-        if (math == ABR_MATH_F16X3) {
-            if (!(Cin % BKX == 0 && h3_planes_bytes(Cout, K) < (int64_t)0xFFFFFFF0)) return 0;
-            void* tok = nullptr;
-            void* planes = abr::derived_acquire(w, abr::DERIVED_H3_PLANES, (size_t)h3_packed_bytes(Cout, K), ver, st, &tok, &waited);
-            if (!planes) return 1;
-            if (tok) { tokens.push_back(tok); add_pack_h3(w, Cout, K, planes); }
-            return 0;
-        }
-        if ((math == ABR_MATH_BF16X6 || (math == ABR_MATH_BF16 && Cin % BKH == 0)) && direct_on && Cin % BKX == 0 &&
-            x6_packed_bytes(Cout, K) < (int64_t)0xFFFFFFF0) {   // (the bf16 mode reads plane 0 of the same packed planes)
-            void* tok = nullptr;
-            void* planes = abr::derived_acquire(w, abr::DERIVED_X6_PLANES, (size_t)x6_packed_bytes(Cout, K), ver, st, &tok, &waited);
-            if (!planes) return 1;
-            if (tok) { tokens.push_back(tok); add_pack(w, Cout, K, planes); }
-            return 0;
-        }
-        return 0;   // nothing to derive
+        abr::PrepJob j{};
+        j.src = w; j.a = Cout; j.b = Cin; j.gx = (int)(((int64_t)Cout * (Cin / 4) + 255) / 256); j.gy = 1; j.first_block = ub;
+        ub += j.gx;
+        uj.push_back(j);
+        u_off.push_back(u_total);
+        // the packing job reads the fp32 U from the scratch: its src is patched in once the scratch address is known (c = 1: src is a scratch offset)
+        if (h3) { add_pack_h3(reinterpret_cast<const float*>(u_total), r.rows, r.K, dst); hj.back().c = 1; }
+        else { add_pack(reinterpret_cast<const float*>(u_total), r.rows, r.K, dst); pj.back().c = 1; }
+        u_total += (size_t)r.rows * r.K;
+        return 0;
     };
     std::vector<int> single_fwd, single_bwd;
     for (int i = 0; i < n; i++) {

@@ -789,11 +789,6 @@ void derived_abandon(void* const* tokens, int n) {
     }
 }
 
-float* wino_u_cached(const float* w, int N, int C, int64_t version, hipStream_t st) {
-    return reinterpret_cast<float*>(derived_cached(w, DERIVED_WINO_U, (size_t)36 * N * C * sizeof(float), version, st,
-                                                   [&](void* buf) { return wino_weight_transform(w, N, C, reinterpret_cast<float*>(buf), st); }));
-}
-
 // Entries with a fill token outstanding (derived_acquire .. derived_commit / derived_abandon on another thread) are left alone: their
 // DEntry* is in that thread's hands.  They become droppable once committed.
 void derived_cache_clear() {

@@ -46,7 +46,7 @@ int abr_device_info(int32_t* out_host);
  * out[id*6+{3,4,5}] = the same for launches made while abr_prof_mark_overlap(1) was in force (the host runs weight-gradient
  * kernels on a second stream next to the dgrad chain: those launches share CUs and their event-bracketed duration is not a
  * property of the kernel).  id = 0 igemm 128x128, 1 igemm 128x64, 2 igemm 64x64, 3 igemm small-C (stem), 4 wgrad, 5/6 ROIAlign
- * fwd/bwd, 7 igemm bf16, 8 wgrad bf16 / bf16x6, 9 / 10 / 11 the bf16x6 implicit GEMM's 128x128 / 128x64 / 64x64 tile instances, 12 / 13 / 14 the same tiles of its weights-direct form.  Synchronises on the recorded events and stops profiling. */
+ * fwd/bwd, 7 igemm bf16 (one-product instances of the weights-direct kernel), 8 wgrad bf16 / bf16x6, 9 / 10 / 11 the bf16x6 implicit GEMM's 128x128 / 128x64 / 64x64 tile instances, 12 / 13 / 14 the same tiles of its weights-direct form.  Synchronises on the recorded events and stops profiling. */
 int abr_prof_begin(void);
 int abr_prof_mark_overlap(int on);
 /* Order everything queued on `waiter` from now on behind everything queued on `signaller` so far (an event recorded on `signaller`, waited for by
@@ -266,15 +266,15 @@ typedef struct {
        terms, the six cross products with i + j <= 2 accumulated in fp32 (same error bound as an fp32 FMA chain; opt-in) */
     int math;
     /* Winograd-domain input reuse between a convolution's forward pass and its weight gradient (both transform the SAME input
-       with B^T d B).  abr_conv_forward: if wino_v is non-NULL and the conv takes the Winograd path, the transformed input V
-       (abr_conv_wino_v_floats floats) is written THERE instead of scratch.  abr_conv_wgrad: if wino_v is non-NULL and the
-       gradient takes the Winograd path, V is read from there and the input transform is skipped (x is not touched).  NULL =
-       self-contained calls. */
+       with B^T d B).  abr_conv_forward: if wino_v is non-NULL the transformed input V (abr_conv_wino_v_floats floats) is written
+       THERE instead of scratch; a conv that does not take the Winograd path, or cannot complete it, returns an error instead.
+       abr_conv_wgrad: if wino_v is non-NULL and abr_conv_wino_v_floats of its descriptor is non-zero, V is read from there and
+       the input transform is skipped (x is not touched).  NULL = self-contained calls. */
     float* wino_v;
-    /* ABR_MATH_BF16X6, abr_conv_forward only: the weights as FRAGMENT-PACKED bf16x3 planes made by abr_conv_pack_weights(w, Cout,
+    /* ABR_MATH_BF16X6 / ABR_MATH_BF16, abr_conv_forward only: the weights as FRAGMENT-PACKED bf16x3 planes made by abr_conv_pack_weights(w, Cout,
        R*S*Cin) (abr_conv_packed_bytes bytes): the weights-direct kernel then loads every weight fragment straight from these planes
        into the matrix-core registers -- no per-workgroup split, no LDS traffic for the weights.  NULL with w_version != 0: the library
-       packs (w, w_version) itself on first use and keeps the planes; NULL with w_version == 0: the weight tile is split in every workgroup. */
+       packs (w, w_version) itself on first use and keeps the planes; NULL with w_version == 0: packed into stream scratch on every call. */
     const void* w_planes;
     /* abr_conv_forward: non-zero = "the weight tensor at address w has not changed since the last call that passed this same
        (w, w_version) pair": the library then keeps data derived from it -- the Winograd-domain weights U = G g G^T (36*Cout*Cin
@@ -369,7 +369,8 @@ int abr_conv_cache_clear(void);
 int abr_conv_cache_drop_range(const void* base, int64_t bytes);
 int64_t abr_conv_cache_bytes(void);
 /* floats of the Winograd-domain input V = 36 * B*ceil(H/4)*ceil(W/4) * Cin if BOTH abr_conv_forward and abr_conv_wgrad take the
- * Winograd F(4x4,3x3) path for this descriptor (wide stride-1 pad-1 3x3, no residual / scatter, fp32 or bf16x6 math), else 0 */
+ * Winograd F(4x4,3x3) path for this descriptor (wide stride-1 pad-1 3x3, no residual / scatter; fp32 math, or bf16x6 / f16x3 with
+ * Cout % 32 == 0), else 0 */
 int64_t abr_conv_wino_v_floats(const abr_conv_desc* d_host);
 /* Fragment-packed bf16x3 planes of an fp32 matrix w [rows][K] (K % 16 == 0; a conv weight: rows = Cout, K = R*S*Cin) for
  * abr_conv_desc::w_planes.  Exact three-way split x = p0 + p1 + p2 (p0 = bf16(x), p1 = bf16(x - p0), p2 = bf16(x - p0 - p1), RNE), stored in

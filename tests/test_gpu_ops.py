@@ -855,6 +855,23 @@ def test_winograd_input_transform_is_shared_between_forward_and_wgrad(math):
     assert ops.wino_v_alloc(x, torch.zeros(64, 3, 3, 64, device="cuda"), 1, 1, m) is None
     assert ops.wino_v_alloc(torch.randn(1, 16, 16, 256, device="cuda"), torch.zeros(256, 1, 1, 256, device="cuda"), 1, 0, m) is None
     assert ops.wino_v_alloc(torch.randn(1, 16, 16, 256, device="cuda"), torch.zeros(256, 3, 3, 256, device="cuda"), 1, 1, ops.MATH_BF16) is None
+    if math == "bf16x6":
+        # Cout % 32 != 0: the forward runs direct, so nothing is kept, and the weight gradient (still Winograd) transforms x itself -- a wino_v
+        # handed to it anyway is not read.  Both meet the bf16x6 criterion against float64 (test_conv_bf16x6_mode_is_fp32_accurate).
+        x = torch.randn(2, 21, 10, 128, device="cuda", generator=g)
+        w = torch.randn(136, 3, 3, 128, device="cuda", generator=g) / (9 * 128) ** 0.5
+        gy = torch.randn(2, 21, 10, 136, device="cuda", generator=g)
+        sc = torch.rand(136, device="cuda", generator=g) + 0.5
+        assert ops.wino_v_alloc(x, w, 1, 1, m) is None
+        xr = x.cpu().double().permute(0, 3, 1, 2).requires_grad_(True); wr = w.cpu().double().permute(0, 3, 1, 2).requires_grad_(True)
+        yr = torch.nn.functional.conv2d(xr, wr, padding=1)
+        (yr * sc.cpu().double().view(1, -1, 1, 1)).backward(gy.cpu().double().permute(0, 3, 1, 2))
+        y = ops.conv_forward(x, w, 1, 1, math=m).permute(0, 3, 1, 2).cpu().double()
+        assert (y - yr.detach()).abs().max().item() < 5e-5 * max(1.0, yr.abs().max().item())
+        dw = torch.zeros_like(w)
+        ops.conv_wgrad(x, gy, dw, 1, 1, scale=sc, math=m, wino_v=torch.full((36 * 2 * 6 * 3 * 128,), float("nan"), device="cuda"))
+        want = wr.grad.permute(0, 2, 3, 1)
+        assert (dw.cpu().double() - want).abs().max().item() < 1e-4 * max(1.0, want.abs().max().item())
 
 
 def _unpack_planes(planes, rows, K):

@@ -12,10 +12,10 @@ SHAPES = [  # (Cout, R, Cin, stride, pad, with scale)
 ]
 
 
-@pytest.mark.parametrize("math_name", ["bf16x6", "f16x3", "f32"])
+@pytest.mark.parametrize("math_name", ["bf16x6", "f16x3", "f32", "bf16"])
 def test_batched_weight_preparation_equals_per_tensor_preparation(math_name):
     from abr_iod_amd import ops
-    math = {"bf16x6": ops.MATH_BF16X6, "f16x3": ops.MATH_F16X3, "f32": ops.MATH_F32}[math_name]
+    math = {"bf16x6": ops.MATH_BF16X6, "f16x3": ops.MATH_F16X3, "f32": ops.MATH_F32, "bf16": ops.MATH_BF16}[math_name]
     torch.manual_seed(0)
     ws, entries, wts, scales = [], [], [], []
     for i, (Cout, R, Cin, stride, pad, sc) in enumerate(SHAPES):

@@ -122,7 +122,9 @@ __device__ __forceinline__ bool det_sum_last(const float (&vals)[NV], const DetW
 enum ProfId { PROF_IGEMM_128x128 = 0, PROF_IGEMM_128x64, PROF_IGEMM_64x64, PROF_IGEMM_SMALLC, PROF_WGRAD, PROF_ROIALIGN_FWD,
               PROF_ROIALIGN_BWD, PROF_IGEMM_BF16, PROF_WGRAD_BF16,
               PROF_X6_128x128, PROF_X6_128x64, PROF_X6_64x64, PROF_X6W_128x128, PROF_X6W_128x64, PROF_X6W_64x64, PROF_X6W_TAIL64,
-              PROF_H3W_128x128, PROF_H3W_128x64, PROF_H3W_64x64, PROF_WGRAD_H3, PROF_COUNT };   // (ids are positions in bench.py's PROF_NAMES)
+              PROF_H3W_128x128, PROF_H3W_128x64, PROF_H3W_64x64, PROF_WGRAD_H3,
+              PROF_F16W_128x128, PROF_F16W_128x64, PROF_F16W_64x64, PROF_WGRAD_F16, PROF_COUNT };   // (the F16 ids lie past
+              // bench.py's list: bench.py never runs that arithmetic; tools/dtype_step_bench.py + a kernel trace measure it)   // (ids are positions in bench.py's PROF_NAMES)
 // Winograd F(4x4,3x3) transform kernels (conv_winograd.hip); the batched GEMM between them is launched by conv_igemm.hip
 struct AmaxRef;
 // `amax` (optional, here and below): the kernel also writes max |value it stored| into that amax word (f16x3 consumers read it)
@@ -265,6 +267,13 @@ __device__ __forceinline__ void h3_split2(const float a, const float b, const fl
     asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(h1) : "v"(a), "v"(inv_s), "v"(h0));
     asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(h1) : "v"(b), "v"(inv_s), "v"(h0));
     o0 = h0; o1 = h1;
+}
+// ABR_MATH_F16's operand: h0 of the pair alone (the first half of h3_split2: one rounding of x / s to fp16), as packed halves
+__device__ __forceinline__ unsigned h3_round2(const float a, const float b, const float inv_s) {
+    unsigned h0;
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "=v"(h0) : "v"(a), "v"(inv_s));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "+v"(h0) : "v"(b), "v"(inv_s));
+    return h0;
 }
 // Range report of an f16x3 operand (one call per inspecting WAVE, all lanes): nsmall = this lane's count of non-zero elements more than 18
 // binades below the amax (h3_small_threshold).  Flags as in include/abr_iod_hip.h (conditions somebody must act on); the count goes to the

@@ -92,7 +92,7 @@ struct ConvP {
     unsigned* x6_flags;      // bf16x6: device word of the range guard (abr::x6_flags_ptr)
     int64_t w_version;       // abr_conv_desc::w_version (0 = nothing derived from w may be cached)
     int nprod;               // 6 = bf16x6 (exact three-way split, six products); 1 = ABR_MATH_BF16 on the same kernels: plane 0 of both operands, one product;
-                             // 3 = ABR_MATH_F16X3 (two-term fp16 split, three products: common.h)
+                             // 3 = ABR_MATH_F16X3 (two-term fp16 split, three products: common.h); 1 with math == ABR_MATH_F16: f16x3's plane 0, one product
     // f16x3: the A operand's amax word (scale of its split), the per-row scales of the packed weight planes (folded into the epilogue's column
     // scale; batched mode: Cout per batch), and -- any arithmetic -- the amax word the epilogue feeds with max |out|
     const unsigned long long* a_amax;
@@ -549,7 +549,9 @@ constexpr int LDX = BKX + 8;   // LDS row pitch in bf16 elements (80 B)
 // plane 0 of the packed weights and keeping only the first plane of the activation split -- a third of the LDS and weight-fragment traffic and a sixth
 // of the MFMAs, with the tile shapes, the weights-direct operand path and the epilogue of the default arithmetic (round 4; the round-1 bf16 kernels
 // converted fp32 operands of BOTH sides in the loop and ran the step 20 % slower than bf16x6).
-template <int BM, int BN, int WM, int WN, bool PLAIN, int NP = 6>
+// F16 (with NP = 1): ABR_MATH_F16 -- the operands are f16x3's, scaled by the same amax words, but ROUNDED: the A write pass keeps h0 = fp16(x / s) only,
+// B is plane 0 of the packed f16x3 planes, one v_mfma_f32_32x32x16_f16 product.  Scales, amax emit and the NONFINITE / STALE report as under f16x3.
+template <int BM, int BN, int WM, int WN, bool PLAIN, int NP = 6, bool F16 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void conv_igemm_x6w_kernel(const ConvP p, const float* __restrict__ x_,
                                                                                                         float* __restrict__ out_) {
     const float* x = x_;
@@ -557,8 +559,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
     constexpr int NA = BM / 32;
     constexpr bool H3 = NP == 3;           // ABR_MATH_F16X3: two fp16 planes per operand, three products (common.h)
+    static_assert(!F16 || NP == 1, "ABR_MATH_F16 is the one-product form");
+    constexpr bool HF = H3 || F16;         // fp16 operands scaled by amax words, f16x3 weight planes
     constexpr int NPL = NP == 1 ? 1 : (H3 ? 2 : 3);   // operand planes in use
-    constexpr int NPW = H3 ? 2 : 3;        // planes per k-step in the packed weights (the bf16 mode reads plane 0 of the bf16x3 packing)
+    constexpr int NPW = HF ? 2 : 3;        // planes per k-step in the packed weights (the one-product modes read plane 0 of their packing)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     abr::prof_stamp_begin(p.prof_ts);
     __bf16* As = reinterpret_cast<__bf16*>(smem);  // [3][BM][LDX]
@@ -656,13 +660,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     // f16x3: the scale of the A operand's split from its amax word (every workgroup reads the same 8 bytes)
     unsigned a_bits = 0;
     float sa = 1.f, inv_sa = 1.f;
-    if constexpr (H3) {
+    if constexpr (HF) {
         a_bits = abr::h3_amax_load(p.a_amax, p.a_epoch);
         abr::h3_scales(a_bits, sa, inv_sa);
     }
     const unsigned small_thr = H3 ? abr::h3_small_threshold(a_bits) : 0u;
     unsigned nsmall = 0;
     auto store_a = [&]() {
+        if constexpr (F16) {
+#pragma unroll
+            for (int i = 0; i < NA; i++) {
+                const u32x4 v = ra[i];
+                uint2 o0;
+                o0.x = abr::h3_round2(__uint_as_float(v.x), __uint_as_float(v.y), inv_sa);
+                o0.y = abr::h3_round2(__uint_as_float(v.z), __uint_as_float(v.w), inv_sa);
+                *reinterpret_cast<uint2*>(As + (srow + 32 * i) * LDX + kq * 4) = o0;
+            }
+            return;
+        }
         if constexpr (H3) {
             if (chk_a) {
 #pragma unroll
@@ -738,7 +753,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
                 for (int i = 0; i < TM; i++)
 #pragma unroll
                     for (int j = 0; j < TN; j++) {
-                        if constexpr (H3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[i][pa[t]]), __builtin_bit_cast(f16x8, fb[j][pb[t]]), acc[i][j], 0, 0, 0);
+                        if constexpr (HF) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[i][pa[t]]), __builtin_bit_cast(f16x8, fb[j][pb[t]]), acc[i][j], 0, 0, 0);
                         else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][pa[t]], fb[j][pb[t]], acc[i][j], 0, 0, 0);
                     }
             if (kt_next < nk) load_b(kt_next, u);
@@ -759,14 +774,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
         __syncthreads();
     }
     compute_tile(nk);
-    if constexpr (H3) {
-        if (chk_a) abr::h3_report(a_bits, nsmall, p.x6_flags, p.h3_stats);
+    if constexpr (HF) {
+        if (chk_a) abr::h3_report(a_bits, nsmall, p.x6_flags, p.h3_stats);   // (ABR_MATH_F16: nsmall == 0, no statistics)
     } else {
         if (chk_a) abr::x6_report(bmin, nonfin, p.x6_flags);
     }
     __syncthreads();  // the epilogue reuses the operand LDS
     const float* wsc = nullptr;
-    if constexpr (H3) wsc = p.w_scales + (p.nbatch > 1 ? (size_t)wsc_bt * p.Cout : 0);
+    if constexpr (HF) wsc = p.w_scales + (p.nbatch > 1 ? (size_t)wsc_bt * p.Cout : 0);
     const unsigned ob = epilogue_rows<TM, TN, true>(p, acc, smem + wave * (32 * (TN * 32 + EPAD)), m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane, out, wsc, sa);
     if (p.out_amax) abr::h3_amax_emit(p.out_amax, p.out_epoch, ob);
     abr::prof_stamp_end(p.prof_ts);
@@ -1177,7 +1192,7 @@ static int num_cus() {
     return n;
 }
 
-template <int BM, int BN, int WM, int WN, int NP>
+template <int BM, int BN, int WM, int WN, int NP, bool F16 = false>
 int launch_x6w_np(const ConvP& p, const float* x, float* out, hipStream_t st) {
     ConvP q = p;
     q.tiles_m = (p.M + BM - 1) / BM;
@@ -1196,21 +1211,22 @@ int launch_x6w_np(const ConvP& p, const float* x, float* out, hipStream_t st) {
         else if (col_bytes * q.tiles_n > 3.0 * 1048576.0) g = col_bytes <= 1.6 * 1048576.0 ? 4 : (col_bytes <= 3.2 * 1048576.0 ? 2 : 0);   // (measured: tools/dbg/ngroup_time.py)
         q.ngroup = (g > 0 && g < q.tiles_n) ? g : 0;
     }
-    q.x6_flags = (NP != 1 && abr::x6_guard_enabled()) ? abr::x6_flags_ptr() : nullptr;   // (rounding to bf16 is defined for every finite value: no guard)
+    q.x6_flags = ((NP != 1 || F16) && abr::x6_guard_enabled()) ? abr::x6_flags_ptr() : nullptr;   // (rounding to bf16 is defined for every finite value: no guard)
     q.h3_stats = (NP == 3 && q.x6_flags) ? abr::h3_stats_ptr() : nullptr;
     if (q.h3_stats) abr::h3_stats_inspected((double)q.tiles_m * BM * (double)p.K * q.nbatch);   // (the first n-tile column's workgroups inspect their A rows)
     constexpr size_t lds_op = sizeof(__bf16) * (NP == 1 ? 1 : (NP == 3 ? 2 : 3)) * BM * LDX;
     constexpr size_t lds_ep = sizeof(float) * 4 * 32 * (BN / WN + EPAD);
     const size_t lds = lds_op > lds_ep ? lds_op : lds_ep;
     const bool plain = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0;
-    auto kern = plain ? conv_igemm_x6w_kernel<BM, BN, WM, WN, true, NP> : conv_igemm_x6w_kernel<BM, BN, WM, WN, false, NP>;
+    auto kern = plain ? conv_igemm_x6w_kernel<BM, BN, WM, WN, true, NP, F16> : conv_igemm_x6w_kernel<BM, BN, WM, WN, false, NP, F16>;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_x6w_kernel<BM, BN, WM, WN, true, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_x6w_kernel<BM, BN, WM, WN, false, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_x6w_kernel<BM, BN, WM, WN, true, NP, F16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_x6w_kernel<BM, BN, WM, WN, false, NP, F16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    constexpr int prof_id = NP == 1 ? abr::PROF_IGEMM_BF16
+    constexpr int prof_id = F16 ? (BM == 128 ? (BN == 128 ? abr::PROF_F16W_128x128 : abr::PROF_F16W_128x64) : abr::PROF_F16W_64x64)
+                            : NP == 1 ? abr::PROF_IGEMM_BF16
                             : NP == 3 ? (BM == 128 ? (BN == 128 ? abr::PROF_H3W_128x128 : abr::PROF_H3W_128x64) : abr::PROF_H3W_64x64)
                                       : (BM == 128 ? (BN == 128 ? abr::PROF_X6W_128x128 : abr::PROF_X6W_128x64) : abr::PROF_X6W_64x64);
     q.prof_ts = abr::prof_stamp_slot(prof_id, 2.0 * (double)p.M * (double)p.Cout * (double)p.K * q.nbatch);
@@ -1224,6 +1240,7 @@ int launch_x6w_np(const ConvP& p, const float* x, float* out, hipStream_t st) {
 }
 template <int BM, int BN, int WM, int WN>
 int launch_x6w(const ConvP& p, const float* x, float* out, hipStream_t st) {
+    if (p.math == ABR_MATH_F16) return launch_x6w_np<BM, BN, WM, WN, 1, true>(p, x, out, st);
     return p.nprod == 1 ? launch_x6w_np<BM, BN, WM, WN, 1>(p, x, out, st)
                         : (p.nprod == 3 ? launch_x6w_np<BM, BN, WM, WN, 3>(p, x, out, st) : launch_x6w_np<BM, BN, WM, WN, 6>(p, x, out, st));
 }
@@ -1509,7 +1526,7 @@ static void dispatch_igemm(const ConvP& p, const float* x, const float* w, float
     }
 }
 
-// The split arithmetics (bf16x6, f16x3, and bf16 as their one-product form): tile choice + launch.  p.w_planes -- the caller's, the
+// The split arithmetics (bf16x6, f16x3, and bf16 / f16 as their one-product forms): tile choice + launch.  p.w_planes -- the caller's, the
 // library's per-version cache, or planes packed into stream scratch for a one-off call -- is never null here: the weights-direct kernel is the only one.
 static void dispatch_igemm_x6(const ConvP& p, const float* x, const float* /*w*/, float* out, hipStream_t st) {
     const int cus = num_cus();
@@ -1546,9 +1563,10 @@ ConvRoute conv_route(const abr_conv_desc& d) {
     static const int min_c = getenv("ABR_WINOGRAD_MIN_C") ? atoi(getenv("ABR_WINOGRAD_MIN_C")) : 128;
     static const bool wino_wgrad = !(getenv("ABR_WINOGRAD_WGRAD") && atoi(getenv("ABR_WINOGRAD_WGRAD")) == 0);
     ConvRoute r{};
-    // the split arithmetics' k-tile is 32 wide (the 4-channel stem has none); the bf16 mode covers the Cin % 64 == 0 layers (include/abr_iod_hip.h)
+    // the split arithmetics' k-tile is 32 wide (the 4-channel stem has none; f16 follows them); the bf16 mode covers the Cin % 64 == 0 layers
+    // (include/abr_iod_hip.h)
     const bool bf16_off = d.math == ABR_MATH_BF16 && d.Cin % 64 != 0;
-    r.math = ((d.math == ABR_MATH_BF16X6 || d.math == ABR_MATH_F16X3) && d.Cin % BKX != 0) || bf16_off ? ABR_MATH_F32 : d.math;
+    r.math = ((d.math == ABR_MATH_BF16X6 || d.math == ABR_MATH_F16X3 || d.math == ABR_MATH_F16) && d.Cin % BKX != 0) || bf16_off ? ABR_MATH_F32 : d.math;
     r.wgrad_math = bf16_off ? ABR_MATH_F32 : d.math;
     // Winograd F(4x4,3x3) for the wide stride-1 3x3 convs: 4x fewer multiply-adds (RPN 3x3: 1.42 -> 0.50 ms, layer4 conv2 1.14 -> 0.41, layer2 conv2
     // 0.122 -> 0.073); layer1's 64-channel conv stays direct -- its 36 GEMMs would have K = 64 and the transforms' HBM traffic outweighs the saving.
@@ -1557,14 +1575,16 @@ ConvRoute conv_route(const abr_conv_desc& d) {
     const bool wide3x3 = min_c > 0 && d.R == 3 && d.S == 3 && d.stride == 1 && d.pad == 1 && d.Cin >= min_c && d.Cout >= 128 &&
                          T * std::max(d.Cin, d.Cout) * 4 < (int64_t)0x7FFFFFF0;
     const bool scatter = !((d.out_H <= 0 || d.out_H == d.Ho) && (d.out_W <= 0 || d.out_W == d.Wo) && d.out_sh <= 1 && d.out_sw <= 1);
-    // bf16 stays direct (a Winograd transform of rounded operands is a different, less accurate function than the mode's definition).  The split
+    // bf16 and f16 stay direct (a Winograd transform of rounded operands is a different, less accurate function than the mode's definition).  The split
     // arithmetics pack U's 36 Cout x Cin matrices as ONE [36 Cout][Cin] matrix whose 32-row blocks must not straddle two of them: Cout % 32 == 0.
-    r.fwd_wino = wide3x3 && !scatter && !d.residual && r.math != ABR_MATH_BF16 && d.Cin % BK == 0 && d.Cout % 4 == 0 &&
+    const bool rounded = r.math == ABR_MATH_BF16 || r.math == ABR_MATH_F16, wg_rounded = r.wgrad_math == ABR_MATH_BF16 || r.wgrad_math == ABR_MATH_F16;
+    r.fwd_wino = wide3x3 && !scatter && !d.residual && !rounded && d.Cin % BK == 0 && d.Cout % 4 == 0 &&
                  (r.math == ABR_MATH_F32 || d.Cout % 32 == 0);
-    r.wgrad_wino = wide3x3 && wino_wgrad && r.wgrad_math != ABR_MATH_BF16 && d.Cin % 4 == 0;
-    r.v_floats = r.fwd_wino && r.wgrad_wino && d.math != ABR_MATH_BF16 ? 36 * T * d.Cin : 0;
-    // derived weights: the weights-direct kernel's packed planes (bf16 reads plane 0 of bf16x6's), of U for a Winograd conv; fp32 Winograd: U itself
-    const bool h3 = r.math == ABR_MATH_F16X3, x6 = r.math == ABR_MATH_BF16X6 || r.math == ABR_MATH_BF16;
+    r.wgrad_wino = wide3x3 && wino_wgrad && !wg_rounded && d.Cin % 4 == 0;
+    r.v_floats = r.fwd_wino && r.wgrad_wino && d.math != ABR_MATH_BF16 && d.math != ABR_MATH_F16 ? 36 * T * d.Cin : 0;
+    // derived weights: the weights-direct kernel's packed planes (bf16 reads plane 0 of bf16x6's, f16 plane 0 of f16x3's), of U for a Winograd
+    // conv; fp32 Winograd: U itself
+    const bool h3 = r.math == ABR_MATH_F16X3 || r.math == ABR_MATH_F16, x6 = r.math == ABR_MATH_BF16X6 || r.math == ABR_MATH_BF16;
     r.rows = r.fwd_wino ? (int64_t)36 * d.Cout : d.Cout;
     r.K = r.fwd_wino ? d.Cin : d.R * d.S * d.Cin;
     if (r.fwd_wino) r.kind = h3 ? DERIVED_WINO_U_H3_PLANES : (x6 ? DERIVED_WINO_U_X6_PLANES : DERIVED_WINO_U);
@@ -1685,13 +1705,15 @@ extern "C" int abr_conv_forward(const abr_conv_desc* d, const float* x, const fl
     p.x_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
     p.d_howo.init((unsigned)(p.Ho * p.Wo)); p.d_wo.init((unsigned)p.Wo); p.d_cin.init((unsigned)p.Cin); p.d_s.init((unsigned)p.S);
     hipStream_t st = abr::as_stream(stream);
-    ABR_REQUIRE(d->math == ABR_MATH_F32 || d->math == ABR_MATH_BF16 || d->math == ABR_MATH_BF16X6 || d->math == ABR_MATH_F16X3, "conv_forward: unknown math mode");
+    ABR_REQUIRE(d->math == ABR_MATH_F32 || d->math == ABR_MATH_BF16 || d->math == ABR_MATH_BF16X6 || d->math == ABR_MATH_F16X3 || d->math == ABR_MATH_F16,
+                "conv_forward: unknown math mode");
     const abr::ConvRoute r = abr::conv_route(*d);
     p.math = r.math;
     p.nprod = p.math == ABR_MATH_BF16 ? 1 : 6;
     p.a_amax = nullptr; p.a_epoch = 0; p.w_scales = nullptr;
     p.out_amax = reinterpret_cast<unsigned long long*>(d->out_amax); p.out_epoch = d->out_amax_epoch;   // (every kernel's epilogue feeds it)
-    if (p.math == ABR_MATH_F16X3) {
+    const bool h3 = p.math == ABR_MATH_F16X3 || p.math == ABR_MATH_F16;   // amax-scaled fp16 operands, f16x3 weight planes
+    if (h3) {
         // the A operand's amax: the caller's word (written by the tensor's producer), else reduced here
         abr::AmaxRef ar{reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(d->x_amax)), d->x_amax_epoch};
         if (!ar.word) {
@@ -1699,7 +1721,7 @@ extern "C" int abr_conv_forward(const abr_conv_desc* d, const float* x, const fl
             ABR_REQUIRE(ar.word && abr::h3_amax_reduce(x, (int64_t)d->B * d->H * d->W * d->Cin, ar, st) == 0, "conv_forward (f16x3): amax reduction failed");
         }
         p.a_amax = ar.word; p.a_epoch = ar.epoch;
-        p.nprod = 3;
+        p.nprod = p.math == ABR_MATH_F16 ? 1 : 3;
         ABR_REQUIRE(h3_planes_bytes(d->Cout, p.K) < (int64_t)0xFFFFFFF0, "conv_forward: weight tensor too large for 32-bit buffer offsets");
         p.wp_bytes = (unsigned)h3_planes_bytes(d->Cout, p.K);
     }
@@ -1712,10 +1734,10 @@ extern "C" int abr_conv_forward(const abr_conv_desc* d, const float* x, const fl
     ABR_REQUIRE(!d->wino_v, "conv_forward: wino_v given for a conv that does not take the Winograd path (abr_conv_wino_v_floats)");
     if (p.math != ABR_MATH_F32) {
         // weights-direct kernel: the caller's own abr_conv_pack_weights(w, Cout, R*S*Cin) planes (bf16x6, bf16), else the route's derived weights
-        p.w_planes = p.math != ABR_MATH_F16X3 ? d->w_planes : nullptr;
+        p.w_planes = !h3 ? d->w_planes : nullptr;
         if (!p.w_planes) p.w_planes = conv_weights(r, w, p.w_version, st);
         ABR_REQUIRE(p.w_planes, "conv_forward: no memory for the weight planes");
-        if (p.math == ABR_MATH_F16X3) p.w_scales = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.w_planes) + h3_planes_bytes(d->Cout, p.K));
+        if (h3) p.w_scales = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.w_planes) + h3_planes_bytes(d->Cout, p.K));
         dispatch_igemm_x6(p, x, w, out, st);
     } else {
         dispatch_igemm(p, x, w, out, st);

@@ -73,7 +73,7 @@ struct WgP {
     float* ws;
     int final_store;             // the reduction stores (dw = sum: the Winograd-domain dU, never zero-filled) instead of dw += sum
     int map4;                    // accumulator interleave of conv_wgrad_x6_kernel (n = n0 + 4 i + 2 wm + tm) instead of n0 + wm*64 + 2 i + tm
-    // ABR_MATH_F16X3: the amax words of the two operands (their split scales; dW = s_gy s_x * sum); null otherwise
+    // ABR_MATH_F16X3 / ABR_MATH_F16: the amax words of the two operands (their split scales; dW = s_gy s_x * sum); null otherwise
     const unsigned long long* gy_amax;
     const unsigned long long* x_amax;
     unsigned gy_epoch, x_epoch;
@@ -404,7 +404,8 @@ constexpr int MRX = 32;
 
 // NP = 6: the bf16x6 arithmetic.  NP = 1: ABR_MATH_BF16 (operands rounded to bf16, one product) on the same loop: one plane per operand in LDS.
 // NP = 3: ABR_MATH_F16X3 (two fp16 planes per operand, scaled by the operand's amax word; three products on v_mfma_f32_32x32x16_f16).
-template <int NP>
+// F16 (with NP = 1): ABR_MATH_F16 -- f16x3's scaling, the operands ROUNDED to their first fp16 plane, one product; no small-element statistics.
+template <int NP, bool F16 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void conv_wgrad_x6_kernel(const WgP p, const float* __restrict__ x_, const float* __restrict__ gy_,
                                                              float* __restrict__ dw_) {
     const float* x = x_;
@@ -414,6 +415,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     abr::prof_stamp_begin(p.prof_ts);
     constexpr int PL = (MRX / 8) * 128 * 4;              // dwords per plane: [4 octets][4 j][32 q] chunks of 4 dwords
     constexpr bool H3 = NP == 3;
+    static_assert(!F16 || NP == 1, "ABR_MATH_F16 is the one-product form");
+    constexpr bool HF = H3 || F16;                       // fp16 operands scaled by their amax words
     constexpr int NPL = NP == 1 ? 1 : (H3 ? 2 : 3);      // operand planes in use
     unsigned* Gs = reinterpret_cast<unsigned*>(smem);    // [NPL][PL]
     unsigned* As = Gs + NPL * PL;                        // [NPL][PL]
@@ -494,13 +497,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     unsigned* const st_base = (is_x ? As : Gs) + (oct * 4 * 32 + q) * 4;   // chunk (oct, j, q) at + j * 128 dwords
     unsigned op_bits = 0;            // f16x3: this wave's operand's amax and the scale of its split
     float op_s = 1.f, op_inv = 1.f;
-    if constexpr (H3) {
+    if constexpr (HF) {
         op_bits = is_x ? abr::h3_amax_load(p.x_amax, p.x_epoch) : abr::h3_amax_load(p.gy_amax, p.gy_epoch);
         abr::h3_scales(op_bits, op_s, op_inv);
     }
     const unsigned small_thr = H3 ? abr::h3_small_threshold(op_bits) : 0u;
     unsigned nsmall = 0;
     auto store_tile = [&]() {
+        if constexpr (F16) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                u32x4 o0;
+#pragma unroll
+                for (int pp = 0; pp < 4; pp++) o0[pp] = abr::h3_round2(__uint_as_float(rr[2 * pp][j]), __uint_as_float(rr[2 * pp + 1][j]), op_inv);
+                *reinterpret_cast<u32x4*>(st_base + j * 128) = o0;
+            }
+            return;
+        }
         if constexpr (H3) {
             if (chk) {
 #pragma unroll
@@ -585,7 +598,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
                 for (int i = 0; i < 2; i++)
 #pragma unroll
                     for (int j = 0; j < 2; j++) {
-                        if constexpr (H3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, G[i][pg[t]]), __builtin_bit_cast(f16x8, A[j][pa[t]]), acc[i][j], 0, 0, 0);
+                        if constexpr (HF) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, G[i][pg[t]]), __builtin_bit_cast(f16x8, A[j][pa[t]]), acc[i][j], 0, 0, 0);
                         else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(G[i][pg[t]], A[j][pa[t]], acc[i][j], 0, 0, 0);
                     }
         }
@@ -605,7 +618,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
         }
         compute_tile();
     }
-    if constexpr (H3) {
+    if constexpr (HF) {
         if (chk) abr::h3_report(op_bits, nsmall, p.x6_flags, p.h3_stats);
     } else {
         if (chk) abr::x6_report(bmin, nonfin, p.x6_flags);
@@ -725,11 +738,12 @@ static void launch_wgrad(WgP p, const float* x, const float* gy, float* dw, void
                                   (int)(sizeof(float) * 2 * MR * (TN_ + TK_)));
         attr_set = true;
     }
-    if (p.math == ABR_MATH_BF16X6 || p.math == ABR_MATH_BF16 || p.math == ABR_MATH_F16X3) {   // same split plan (MRX == MR), three-plane (bf16: one-plane, f16x3: two-plane) LDS
-        static bool attr6 = false;
+    if (p.math == ABR_MATH_BF16X6 || p.math == ABR_MATH_BF16 || p.math == ABR_MATH_F16X3 || p.math == ABR_MATH_F16) {   // same split plan (MRX == MR), three-plane
+        static bool attr6 = false;                                                                                     // (bf16 / f16: one-plane, f16x3: two-plane) LDS
         const bool one = p.math == ABR_MATH_BF16;   // round 4: the bf16 mode on the bf16x6 kernel's loader / LDS image, single product
         const bool h3 = p.math == ABR_MATH_F16X3;
-        const size_t lds6 = sizeof(unsigned) * (one ? 1 : (h3 ? 2 : 3)) * (MRX / 2) * (TN_ + TK_);
+        const bool f16 = p.math == ABR_MATH_F16;    // f16x3's scaled operands, rounded to one fp16 plane, single product
+        const size_t lds6 = sizeof(unsigned) * (one || f16 ? 1 : (h3 ? 2 : 3)) * (MRX / 2) * (TN_ + TK_);
         if (!attr6) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_x6_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)(sizeof(unsigned) * 3 * (MRX / 2) * (TN_ + TK_)));
@@ -742,12 +756,13 @@ static void launch_wgrad(WgP p, const float* x, const float* gy, float* dw, void
         // Timed with a HIP-event pair, not with in-kernel stamps: a kernel trace's duration of these kernels includes the write-back of the
         // parked partial tiles at kernel end, which first-workgroup-in / last-workgroup-out stamps miss by ~10 % (the raw event figure is
         // within 3 % of rocprofv3's here; for the forward / dgrad kernels it is the stamps that agree, within 2.5 %).
-        const int pid6 = h3 ? abr::PROF_WGRAD_H3 : abr::PROF_WGRAD_BF16;
+        const int pid6 = h3 ? abr::PROF_WGRAD_H3 : (f16 ? abr::PROF_WGRAD_F16 : abr::PROF_WGRAD_BF16);
         const int rec6 = abr::prof_start(abr::as_stream(stream), pid6, 2.0 * (double)p.M * (double)p.Cout * (double)p.K * nb);
         p.prof_ts = abr::prof_clock_slot(rec6);
         // algorithmic bytes: x and gy once (x at its own size for a direct 3x3), dw written once
         abr::prof_add_bytes(pid6, 4.0 * nb * ((double)p.M * p.Cout + (p.plain ? (double)p.M * p.K : (double)p.B * p.H * p.W * p.Cin) + (double)p.Cout * p.K));
         if (h3) conv_wgrad_x6_kernel<3><<<(unsigned)(tiles * splits), 256, lds6, abr::as_stream(stream)>>>(p, x, gy, dw);
+        else if (f16) conv_wgrad_x6_kernel<1, true><<<(unsigned)(tiles * splits), 256, lds6, abr::as_stream(stream)>>>(p, x, gy, dw);
         else if (one) conv_wgrad_x6_kernel<1><<<(unsigned)(tiles * splits), 256, lds6, abr::as_stream(stream)>>>(p, x, gy, dw);
         else conv_wgrad_x6_kernel<6><<<(unsigned)(tiles * splits), 256, lds6, abr::as_stream(stream)>>>(p, x, gy, dw);
         abr::prof_stop(abr::as_stream(stream), rec6);
@@ -789,10 +804,11 @@ extern "C" int abr_conv_wgrad(const abr_conv_desc* d, const float* x, const floa
     static const int tile_fast = !(getenv("ABR_WGRAD_TILE_FAST") && atoi(getenv("ABR_WGRAD_TILE_FAST")) == 0);
     p.tile_fast = tile_fast;
     hipStream_t st = abr::as_stream(stream);
-    ABR_REQUIRE(d->math == ABR_MATH_F32 || d->math == ABR_MATH_BF16 || d->math == ABR_MATH_BF16X6 || d->math == ABR_MATH_F16X3, "conv_wgrad: unknown math mode");
+    ABR_REQUIRE(d->math == ABR_MATH_F32 || d->math == ABR_MATH_BF16 || d->math == ABR_MATH_BF16X6 || d->math == ABR_MATH_F16X3 || d->math == ABR_MATH_F16,
+                "conv_wgrad: unknown math mode");
     const abr::ConvRoute route = abr::conv_route(*d);
     p.math = route.wgrad_math;   // (bf16: the bf16x6 kernel's loader / LDS image and split plan, one product)
-    const bool h3 = p.math == ABR_MATH_F16X3;
+    const bool h3 = p.math == ABR_MATH_F16X3 || p.math == ABR_MATH_F16;   // operands scaled by their amax words (f16: never Winograd)
     // f16x3: amax words of the two operands -- the caller's (written by the producers of x / gy), else reduced here
     abr::AmaxRef gy_ref{reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(d->gy_amax)), d->gy_amax_epoch};
     abr::AmaxRef x_ref{reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(d->x_amax)), d->x_amax_epoch};

@@ -34,7 +34,7 @@ class EvalRangeGuard(object):
         self._clean = False
 
     def active(self):
-        return EVAL_GUARD and getattr(self.model, "conv_math", None) in ("f16x3", "bf16x6") and hasattr(self.model, "set_conv_math")
+        return EVAL_GUARD and getattr(self.model, "conv_math", None) in ("f16x3", "bf16x6", "f16") and hasattr(self.model, "set_conv_math")
 
     def forward(self, images):
         ops, model = self.ops, self.model

@@ -136,8 +136,11 @@ def _x6_guard(model_source, model_target, log=None):
     input gradients of a zero-padded image of a ragged batch reach 1e-36 next to 1e-5 (tools/x6_flag_hunt.py) -- so leaving the fast
     arithmetic for them would silently cost 25 % of the throughput for nothing.  It is logged once; ABR_X6_STRICT=1 switches on it too.
 
+    f16 (cfg.DTYPE "float16"): NONFINITE moves both models to "f32" as above and STALE raises; there is no small-element fall-back -- the
+    operands are rounded to fp16 by the mode's definition, so elements far below their tensor's amax are part of what it computes.
+
     Under data parallelism the flag is MAX-reduced over the ranks first, so that every rank switches at the same step."""
-    if getattr(model_target, "conv_math", "f32") not in ("bf16x6", "f16x3"):
+    if getattr(model_target, "conv_math", "f32") not in ("bf16x6", "f16x3", "f16"):
         return
     from .. import ops
     st = trainer_state(model_target)
@@ -167,7 +170,7 @@ def _x6_guard(model_source, model_target, log=None):
     if not flags:
         return
     if flags & ops.H3_FLAG_STALE:
-        raise RuntimeError("f16x3: a kernel was handed an amax word that did not carry the epoch it was told (abr_iod_amd.ops amax tags): "
+        raise RuntimeError("f16x3 / f16: a kernel was handed an amax word that did not carry the epoch it was told (abr_iod_amd.ops amax tags): "
                            "the results of that launch are wrong -- a bug in the host plumbing, not in the data")
     if (flags & ops.X6_FLAG_TINY) and not (flags & ops.X6_FLAG_NONFINITE) and not X6_STRICT:
         if not st.x6_tiny_logged:
@@ -176,7 +179,7 @@ def _x6_guard(model_source, model_target, log=None):
                         "absolute error below 2^-119 x the other operand -- staying on the bf16 matrix cores (ABR_X6_STRICT=1 would switch)")
         return
     what = " + ".join(n for b, n in ((ops.X6_FLAG_TINY, "non-zero operand below 2^-110"), (ops.X6_FLAG_NONFINITE, "inf/nan operand")) if flags & b)
-    logger.warning("bf16x6 / f16x3 range guard tripped ({}): switching both models to the fp32 MFMA kernels from the next step on; the last two "
+    logger.warning("bf16x6 / f16x3 / f16 range guard tripped ({}): switching both models to the fp32 MFMA kernels from the next step on; the last two "
                    "updates were computed with operands outside the exact-split domain and are not redone".format(what))
     for m in (model_source, model_target):
         if m is not None and hasattr(m, "set_conv_math"):

@@ -169,7 +169,7 @@ class _FwdPlan(object):
             self.off = (0, n1, n1 + n2)        # o1, o2, identity branch inside the temporaries' buffer (floats)
             self.tmp_floats = n1 + n2 + nd
         self.out_shape = shapes[i3]
-        self.h3 = self.math == ops.MATH_F16X3
+        self.h3 = ops.uses_amax(self.math)
         self.s = s
         # the table is mutable: two host threads running the same model (threaded inference) must not rewrite each other's pointers while
         # abr_conv_run -- which releases the GIL -- still walks them
@@ -478,7 +478,7 @@ def run_stage(x, blocks, first_stride=None, need_dx=True):
 
 
 def set_conv_math(module, math):
-    """Select the contraction arithmetic (ops.MATH_F32 / ops.MATH_BF16) of every bottleneck / conv head under `module`."""
+    """Select the contraction arithmetic (ops.MATH_*) of every bottleneck / conv head under `module`."""
     n = 0
     for m in module.modules():
         if hasattr(m, "math"):
@@ -535,9 +535,11 @@ class ResNet(nn.Module):
         self._freeze_backbone(cfg.MODEL.BACKBONE.FREEZE_CONV_BODY_AT)
         if cfg.DTYPE == "bfloat16":   # BASELINE.json configs[4]: "bf16 MFMA backbone" (fp32 tensors, fp32 accumulate; the stem stays fp32)
             set_conv_math(self, ops.MATH_BF16)
+        elif cfg.DTYPE == "float16":  # one-product fp16 contractions across the detector (GeneralizedRCNN sets the RPN and layer4 head too)
+            set_conv_math(self, ops.MATH_F16)
         elif cfg.DTYPE != "float32":
-            raise NotImplementedError("DTYPE {!r}: this build computes in float32 or with a bfloat16 MFMA backbone "
-                                      "(the reference's float16 = apex amp O1, train_incremental.py:194)".format(cfg.DTYPE))
+            raise NotImplementedError("DTYPE {!r}: this build computes in float32, float16 (one-product fp16 contractions) or with a bfloat16 "
+                                      "MFMA backbone".format(cfg.DTYPE))
 
     def _freeze_backbone(self, freeze_at):
         for stage_index in range(max(freeze_at, 0)):

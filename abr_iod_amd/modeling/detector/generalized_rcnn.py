@@ -84,12 +84,16 @@ class GeneralizedRCNN(nn.Module):
             set_conv_math(self.roi_heads, ops.MATH_F16X3 if env_math == "f16x3" else ops.MATH_BF16X6)
             self.conv_math = env_math      # (the range guard of engine/trainer.py watches the fp32-accurate part)
             self.bf16_backbone = True
+        elif cfg.DTYPE == "float16":
+            # one-product fp16 contractions (ops.MATH_F16) in every bottleneck, the RPN head and the layer4 head: operands rounded once with f16x3's
+            # per-tensor / per-row scales, fp32 accumulation and fp32 tensors.  The route keeps the stem (Cin = 4) on the fp32 MFMA kernels.
+            self.set_conv_math("f16")
         self.flat = None
 
     def set_conv_math(self, name):
-        """'f32', 'bf16x6' or 'f16x3' for every conv of the backbone, RPN head and layer4 head (takes effect at the next call)"""
+        """'f32', 'bf16x6', 'f16x3' or 'f16' for every conv of the backbone, RPN head and layer4 head (takes effect at the next call)"""
         from ..backbone.resnet import set_conv_math
-        math = {"f32": ops.MATH_F32, "bf16x6": ops.MATH_BF16X6, "f16x3": ops.MATH_F16X3}[name]
+        math = {"f32": ops.MATH_F32, "bf16x6": ops.MATH_BF16X6, "f16x3": ops.MATH_F16X3, "f16": ops.MATH_F16}[name]
         # (a "bf16 MFMA backbone" -- configs[4] -- keeps its own arithmetic when the guard moves the rest: rounding to bf16 is defined for every
         #  finite value, and the mode would otherwise silently stop being what its name says)
         for m in ((self.rpn, self.roi_heads) if self.bf16_backbone else (self.backbone, self.rpn, self.roi_heads)):

@@ -204,9 +204,14 @@ def bce_logits_gather(x, y, idx, gscale=1.0, want_grad=False, yidx=None, denom_d
 
 
 # ----------------------------------------------------------------------------------------------- conv
-MATH_F32, MATH_BF16, MATH_BF16X6, MATH_F16X3 = 0, 1, 2, 3   # abr_conv_desc::math (include/abr_iod_hip.h)
+MATH_F32, MATH_BF16, MATH_BF16X6, MATH_F16X3, MATH_F16 = 0, 1, 2, 3, 4   # abr_conv_desc::math (include/abr_iod_hip.h)
 X6_FLAG_TINY, X6_FLAG_NONFINITE = 1, 2       # ABR_X6_FLAG_*
 H3_FLAG_STALE = 8                            # ABR_H3_FLAG_STALE
+
+
+def uses_amax(math):
+    """the arithmetic scales its operands by their amax words (f16x3, and f16 = its one-product rounded form)"""
+    return math == MATH_F16X3 or math == MATH_F16
 
 # ---- f16x3 (MATH_F16X3): amax words.  A tensor's amax word (include/abr_iod_hip.h, abr_conv_desc) rides on the torch.Tensor OBJECT the producing
 # op returned, as `_abr_amax` = (word address, epoch, data_ptr, tensor version, allocation count): valid only while that object still names the
@@ -440,8 +445,8 @@ def conv_forward(x, w, stride=1, pad=0, scale=None, bias=None, residual=None, ma
                  out=None, out_hw=None, out_stride=(1, 1), math=MATH_F32, wino_v=None, w_planes=None, w_version=0, emit_amax=None):
     """x [B,H,W,Cin] NHWC, w [Cout,R,S,Cin] OHWI -> [B,Ho,Wo,Cout] (or scattered into `out` [B,out_H,out_W,Cout]).
     math=MATH_BF16: operands rounded to bf16 inside the kernel, bf16 MFMA, fp32 accumulate (fp32 tensors in and out).
-    math=MATH_F16X3: x's amax word is taken from its tag when it has one (else the library reduces x first); emit_amax (default: under
-    MATH_F16X3) makes the kernel's epilogue write the output's amax word, and the result is tagged with it -- not when the conv accumulates
+    math=MATH_F16X3 / MATH_F16: x's amax word is taken from its tag when it has one (else the library reduces x first); emit_amax (default: under
+    those) makes the kernel's epilogue write the output's amax word, and the result is tagged with it -- not when the conv accumulates
     into a caller's `out` that already holds other pixels (a scattered second pass), whose amax the epilogue cannot know."""
     L.require_cuda(x, w)
     xc, w = L.f32c(x), L.f32c(w)
@@ -449,7 +454,7 @@ def conv_forward(x, w, stride=1, pad=0, scale=None, bias=None, residual=None, ma
     d.wino_v = L.ptr(wino_v)
     d.w_planes = L.ptr(w_planes)   # MATH_BF16X6: the caller's own pack_weights(w) planes (else the library packs (w, w_version) itself)
     d.w_version = int(w_version)   # non-zero: the library may keep data derived from (w, w_version): Winograd-domain weights, packed bf16x3 planes
-    if math == MATH_F16X3:
+    if uses_amax(math):
         aw, ae = amax_of(x) if xc is x else (None, 0)
         if aw is None and H3_TAGS:
             aw, ae = amax_of(amax_compute(xc))
@@ -461,7 +466,7 @@ def conv_forward(x, w, stride=1, pad=0, scale=None, bias=None, residual=None, ma
         else:
             out = _empty((d.B, d.Ho, d.Wo, d.Cout), xc)
     if emit_amax is None:
-        emit_amax = math == MATH_F16X3
+        emit_amax = uses_amax(math)
     # a strided scatter (the dgrad of a stride-2 1x1 conv: rows land on every out_sh-th pixel of a zeroed tensor) writes every non-zero element of
     # its result, so its epilogue's amax IS the tensor's -- in the fresh pass, and in a second pass that adds into exactly that tensor
     strided = d.out_sh != 1 or d.out_sw != 1
@@ -596,14 +601,14 @@ def conv_cache_bytes():
 
 
 def conv_wgrad(x, gy, dw, stride=1, pad=0, scale=None, math=MATH_F32, wino_v=None, amax_refs=None, stream=None):
-    """dw [Cout,R,S,Cin] += scale * gy^T im2col(x) (fp32 atomics; caller zeroes dw once per step).  MATH_F16X3: the amax words of x and
+    """dw [Cout,R,S,Cin] += scale * gy^T im2col(x) (fp32 atomics; caller zeroes dw once per step).  MATH_F16X3 / MATH_F16: the amax words of x and
     gy come from their tags (else the library reduces the operand first); amax_refs = ((word, epoch) of x, of gy) taken by the caller on
     the stream that produced the operands (conv_wgrad_async)."""
     L.require_cuda(x, gy, dw)
     xc, gyc = L.f32c(x), L.f32c(gy)
     d = conv_desc(xc.shape, dw.shape, stride, pad, scale=scale, math=math)
     d.wino_v = L.ptr(wino_v)
-    if math == MATH_F16X3:
+    if uses_amax(math):
         if xc is x:
             d.x_amax, d.x_amax_epoch = amax_refs[0] if amax_refs else amax_of(x)
         if gyc is gy:
@@ -734,7 +739,7 @@ def conv_wgrad_async(x, gy, dw, stride=1, pad=0, scale=None, math=MATH_F32, wino
     # kernel reads, so they are what is kept alive until the join.
     x, gy = L.f32c(x), L.f32c(gy)
     refs = None
-    if math == MATH_F16X3 and H3_TAGS:
+    if uses_amax(math) and H3_TAGS:
         # operands without an amax word get one on this stream: the dgrad that follows here shares gy's, and the side stream (ordered behind
         # this point by the wait below) is handed both -- a word reduced on the side stream would not be ordered before this stream's later readers
         if wino_v is None and amax_of(x)[0] is None:
@@ -807,7 +812,7 @@ def _conv_backward_run(arr, ptr, owner, x, gy, dw, math, wino_v, dgrad, mask, re
         L.lib().abr_prof_mark_overlap(1)
         torch.autograd.Variable._execution_engine.queue_callback(join_side_stream)
     main = L.stream()
-    h3 = math == MATH_F16X3
+    h3 = uses_amax(math)
     xp, gp = x.data_ptr(), gy.data_ptr()
     a0, a1 = arr[0], arr[1]
     a0.stream, a0.other = side, main

@@ -244,6 +244,7 @@ int abr_bce_logits_gather(const float* x, const float* y, const int64_t* idx, co
 #define ABR_MATH_BF16 1
 #define ABR_MATH_BF16X6 2
 #define ABR_MATH_F16X3 3
+#define ABR_MATH_F16 4
 
 typedef struct {
     int B, H, W, Cin;        /* input  [B,H,W,Cin]  (Cin % 4 == 0) */
@@ -263,7 +264,12 @@ typedef struct {
        ABR_MATH_BF16 = both operands rounded to bf16 (RNE) inside the kernel, bf16 MFMA, fp32 accumulate, fp32 tensors in
        memory (BASELINE.json configs[4]); layers whose Cin is not a multiple of 64 (the stem) compute in fp32 either way;
        ABR_MATH_BF16X6 = fp32-ACCURATE arithmetic on the bf16 matrix cores: each fp32 operand split exactly into three bf16
-       terms, the six cross products with i + j <= 2 accumulated in fp32 (same error bound as an fp32 FMA chain; opt-in) */
+       terms, the six cross products with i + j <= 2 accumulated in fp32 (same error bound as an fp32 FMA chain; opt-in);
+       ABR_MATH_F16X3: see x_amax below;
+       ABR_MATH_F16 = REDUCED precision on the fp16 matrix cores: each operand ROUNDED once, x ~ s fp16(x / s) with f16x3's scale s (the amax
+       words below; per output row for weights), ONE v_mfma_f32_32x32x16_f16 product per multiply-add, fp32 accumulation, fp32 tensors in
+       memory.  Relative representation error <= 2^-12 per operand (absolute 2^-25 s below fp16's normal range); never Winograd; layers whose
+       Cin is not a multiple of 32 (the stem) compute in fp32.  Flags as under f16x3 (NONFINITE, STALE), no small-element statistics */
     int math;
     /* Winograd-domain input reuse between a convolution's forward pass and its weight gradient (both transform the SAME input
        with B^T d B).  abr_conv_forward: if wino_v is non-NULL the transformed input V (abr_conv_wino_v_floats floats) is written

@@ -1,0 +1,368 @@
+"""GPU: the one-product fp16 arithmetic (ABR_MATH_F16, cfg.DTYPE "float16").
+
+Definition, restated here with torch CPU ops: each contraction operand is written x ~ s q16(x / s), q16 = round to nearest even in IEEE fp16,
+s = the power of two that puts the operand's largest magnitude in [2^14, 2^15) -- per tensor for activations and gradients, per output row
+(R*S*Cin values) for weights.  One fp16 x fp16 product per multiply-add, fp32 accumulation, the epilogue multiplies by s_x s_w[row].  So:
+  * against float64 on the restated operands q(x), q(w), the only error is fp32 accumulation: it must stay within max(2 x the fp32 MFMA kernel's
+    error on the same q operands, 8 ulp) and below 32 ulp of sum |q(x)||q(w)| (the in-domain criterion of test_gpu_f16x3_admission.py);
+  * against the fp32 operands, an element within fp16's normal range of its scale has relative error <= 2^-12, so a dot product stays within
+    2^-11 sum |x||w| plus the accumulation and the absolute term (2^-25 s per element below the normal range): <= 2^-10 sum |x||w| here.
+The reference bottleneck (modeling/backbone/resnet.py, Bottleneck: 1x1 (stride) -> FrozenBN -> ReLU -> 3x3 -> FrozenBN -> ReLU -> 1x1 ->
+FrozenBN -> + identity (1x1 (stride) -> FrozenBN when the width changes) -> ReLU) is restated in float64 on the same rounded operands."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+EPS = 2.0 ** -24
+
+
+def _gen(seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return (lambda *s: torch.randn(*s, device="cuda", generator=g)), (lambda *s: torch.rand(*s, device="cuda", generator=g))
+
+
+def _q(t, per_row=False):
+    """s q16(t / s) in float64 on the CPU; per_row: one scale per output row of a [Cout, R, S, Cin] weight"""
+    t64 = t.detach().double().cpu()
+    a = t64.abs().flatten(1).amax(1).view(-1, *([1] * (t64.dim() - 1))) if per_row else t64.abs().max()
+    _, e = torch.frexp(a)                                   # a = m 2^e, m in [0.5, 1)
+    s = torch.where(a > 0, torch.exp2((e - 15).double()), torch.ones_like(a, dtype=torch.float64))
+    return (t64 / s).to(torch.float16).double() * s
+
+
+def _conv64(x, w, stride, pad):
+    """NHWC x, OHWI w (float64) -> NHWC"""
+    return F.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), stride=stride, padding=pad).permute(0, 2, 3, 1)
+
+
+def _wgrad64(x, gy, R, stride, pad):
+    """dW[n, r, s, c] = sum_{b, ho, wo} gy[b, ho, wo, n] x[b, ho * stride - pad + r, wo * stride - pad + s, c] (NHWC, float64)"""
+    Ho, Wo = gy.shape[1], gy.shape[2]
+    xp = F.pad(x, (0, 0, pad, pad, pad, pad))
+    out = torch.zeros(gy.shape[3], R, R, x.shape[3], dtype=torch.float64)
+    g2 = gy.reshape(-1, gy.shape[3])
+    for r in range(R):
+        for s in range(R):
+            xs = xp[:, r:r + stride * (Ho - 1) + 1:stride, s:s + stride * (Wo - 1) + 1:stride, :].reshape(-1, x.shape[3])
+            out[:, r, s, :] = g2.t() @ xs
+    return out
+
+
+def _err(y, y64, scale):
+    ok = scale > 0
+    return float(((y.detach().double().cpu() - y64).abs()[ok] / scale[ok]).max())
+
+
+def _check(name, e16, e32):
+    print(f"{name}: f32 on q operands {e32 / EPS:.1f} ulp, f16 {e16 / EPS:.1f} ulp of sum|q(x)||q(w)|")
+    assert e16 <= max(2.0 * e32, 8 * EPS), (name, e16, e32)
+    assert e16 <= 32 * EPS, (name, e16)
+
+
+# forward / dgrad cases: (name, B, H, W, Cin, Cout, k, stride, pad)
+FWD = [("1x1 GEMM 384x256x1024", 1, 384, 1, 1024, 256, 1, 1, 0),
+       ("1x1 stride 2", 2, 20, 24, 256, 128, 1, 2, 0),
+       ("3x3 256 -> 256 (Winograd under f16x3)", 2, 20, 24, 256, 256, 3, 1, 1),
+       ("3x3 64 -> 64", 2, 20, 24, 64, 64, 3, 1, 1)]
+
+
+@pytest.mark.parametrize("case", FWD, ids=[c[0] for c in FWD])
+def test_forward_exact_to_the_definition(case):
+    from abr_iod_amd import ops
+    name, B, H, W, Cin, Cout, k, st, pad = case
+    rn, _ = _gen(FWD.index(case))
+    x, w = rn(B, H, W, Cin), rn(Cout, k, k, Cin) / (k * k * Cin) ** 0.5
+    qx, qw = _q(x), _q(w, per_row=True)
+    y64, s64 = _conv64(qx, qw, st, pad), _conv64(qx.abs(), qw.abs(), st, pad)
+    ops.x6_range_flags(reset=True)
+    for ver in (0, 5):     # planes packed into scratch per call, and the per-version cache
+        y16 = ops.conv_forward(x, w, st, pad, math=ops.MATH_F16, w_version=ver)
+        e16 = _err(y16, y64, s64)
+        e32 = _err(ops.conv_forward(qx.float().cuda(), qw.float().cuda(), st, pad, math=ops.MATH_F32), y64, s64)
+        _check(name + (" (cached planes)" if ver else ""), e16, e32)
+    assert ops.x6_range_flags(reset=True) == 0
+
+
+def test_residual_relu_epilogue_exact_to_the_definition():
+    from abr_iod_amd import ops
+    rn, ru = _gen(11)
+    B, H, W, Cin, Cout = 2, 16, 20, 256, 512
+    x, w = torch.relu(rn(B, H, W, Cin)), rn(Cout, 1, 1, Cin) / 16
+    sc, bi, res = ru(Cout) + 0.5, rn(Cout) * 0.1, rn(B, H, W, Cout)
+    qx, qw = _q(x), _q(w, per_row=True)
+    sc64, bi64, res64 = sc.double().cpu(), bi.double().cpu(), res.double().cpu()
+    y64 = torch.relu(_conv64(qx, qw, 1, 0) * sc64 + bi64 + res64)
+    s64 = _conv64(qx.abs(), qw.abs(), 1, 0) * sc64.abs() + bi64.abs() + res64.abs()
+    y16 = ops.conv_forward(x, w, 1, 0, scale=sc, bias=bi, residual=res, relu=True, math=ops.MATH_F16, w_version=3)
+    y32 = ops.conv_forward(qx.float().cuda(), qw.float().cuda(), 1, 0, scale=sc, bias=bi, residual=res, relu=True, math=ops.MATH_F32)
+    _check("1x1 + scale, bias, residual, ReLU", _err(y16, y64, s64), _err(y32, y64, s64))
+
+
+@pytest.mark.parametrize("which", ["3x3", "1x1 stride 2"])
+def test_dgrad_exact_to_the_definition(which):
+    """dL/dx = conv(gy, wt): the transposed, flipped weight copy is packed like any weight (its own per-row scales)"""
+    from abr_iod_amd import ops
+    rn, _ = _gen(12)
+    B, H, W = 2, 20, 24
+    if which == "3x3":
+        Cin, Cout, k, st, pad = 256, 256, 3, 1, 1
+    else:
+        Cin, Cout, k, st, pad = 256, 512, 1, 2, 0
+    Ho, Wo = (H + 2 * pad - k) // st + 1, (W + 2 * pad - k) // st + 1
+    w, gy = rn(Cout, k, k, Cin) / (k * k * Cin) ** 0.5, rn(B, Ho, Wo, Cout)
+    wt = ops.conv_dgrad_weights(w, None)
+    qg, qwt = _q(gy), _q(wt, per_row=True)
+    kw = dict(out_hw=(H, W), out_stride=(st, st)) if st > 1 else {}
+    g16 = ops.conv_forward(gy, wt, 1, k - 1 - pad, math=ops.MATH_F16, w_version=7, **kw)
+    g32 = ops.conv_forward(qg.float().cuda(), qwt.float().cuda(), 1, k - 1 - pad, math=ops.MATH_F32, **kw)
+    y64, s64 = _conv64(qg, qwt, 1, k - 1 - pad), _conv64(qg.abs(), qwt.abs(), 1, k - 1 - pad)
+    if st > 1:     # rows land on every st-th pixel of a zeroed tensor
+        z64, zs = torch.zeros(B, H, W, Cin, dtype=torch.float64), torch.zeros(B, H, W, Cin, dtype=torch.float64)
+        z64[:, ::st, ::st], zs[:, ::st, ::st] = y64, s64
+        y64, s64 = z64, zs
+    _check("dgrad " + which, _err(g16, y64, s64), _err(g32, y64, s64))
+
+
+@pytest.mark.parametrize("which", ["1x1", "3x3"])
+def test_wgrad_exact_to_the_definition(which):
+    """dW = s_gy s_x sum q16(gy / s_gy) q16(x / s_x): both scales per tensor, from the two amax words"""
+    from abr_iod_amd import ops
+    rn, _ = _gen(13)
+    B, H, W, Cin, Cout = 2, 20, 24, 256, 256
+    k, pad = (1, 0) if which == "1x1" else (3, 1)
+    x, gy = torch.relu(rn(B, H, W, Cin)), rn(B, H, W, Cout) * 1e-3
+    qx, qg = _q(x), _q(gy)
+    d64, s64 = _wgrad64(qx, qg, k, 1, pad), _wgrad64(qx.abs(), qg.abs(), k, 1, pad)
+    ops.x6_range_flags(reset=True)
+    dw16 = torch.zeros(Cout, k, k, Cin, device="cuda")
+    ops.conv_wgrad(x, gy, dw16, 1, pad, math=ops.MATH_F16)
+    dw32 = torch.zeros(Cout, k, k, Cin, device="cuda")
+    ops.conv_wgrad(qx.float().cuda(), qg.float().cuda(), dw32, 1, pad, math=ops.MATH_F32)
+    _check("wgrad " + which, _err(dw16, d64, s64), _err(dw32, d64, s64))
+    assert ops.x6_range_flags(reset=True) == 0
+
+
+BOUNDED = ["N(0,1)", "exponent spread 2^+-20", "70 % exact zeros"]
+
+
+@pytest.mark.parametrize("name", BOUNDED)
+def test_bounded_against_fp32_operands(name):
+    from abr_iod_amd import ops
+    rn, ru = _gen(20 + BOUNDED.index(name))
+    M, N, K = 384, 256, 1024
+    x, w = rn(M, K), rn(N, K)
+    if name.startswith("exponent"):
+        x, w = x * torch.exp2((ru(M, K) * 2 - 1) * 20), w * torch.exp2((ru(N, K) * 2 - 1) * 20)
+    elif name.startswith("70"):
+        x[x < 0.5] = 0.0
+    y = ops.conv_forward(x.view(1, M, 1, K), w.view(N, 1, 1, K), 1, 0, math=ops.MATH_F16).view(M, N)
+    x64, w64 = x.double(), w.double()
+    e = float(((y.double() - x64 @ w64.t()).abs() / (x64.abs() @ w64.abs().t())).max())
+    print(f"{name}: f16 error {e * 2 ** 11:.3f} x 2^-11 of sum|x||w|")
+    assert e <= 2.0 ** -10, (name, e)
+    dw = torch.zeros(N, 1, 1, K, device="cuda")     # the weight gradient's reduction over rows: dW = w'^T x with w' = w^T viewed as [M, N]
+    G = w.t()[:M].contiguous()
+    ops.conv_wgrad(x.view(1, M, 1, K), G.view(1, M, 1, N), dw, 1, 0, math=ops.MATH_F16)
+    d64 = G.double().t() @ x64
+    ew = float(((dw.view(N, K).double() - d64).abs() / (G.double().abs().t() @ x64.abs()).clamp_min(1e-300)).max())
+    assert ew <= 2.0 ** -10, (name, ew)
+
+
+def test_amax_from_the_producers_tag_equals_amax_reduced_by_the_library():
+    from abr_iod_amd import ops
+    rn, ru = _gen(30)
+    x = rn(2, 24, 20, 128)
+    w1, w2 = rn(256, 1, 1, 128) / 11, rn(128, 3, 3, 256) / 48
+    sc, bi = ru(256) + 0.5, rn(256) * 0.1
+    h = ops.conv_forward(x, w1, 1, 0, scale=sc, bias=bi, relu=True, math=ops.MATH_F16)
+    assert ops.amax_of(h)[0] is not None        # the F16 epilogue emitted the output's amax word
+    y_tag = ops.conv_forward(h, w2, 1, 1, math=ops.MATH_F16, w_version=9)
+    h_plain = h.clone()                          # no tag: the library reduces the amax itself
+    assert ops.amax_of(h_plain)[0] is None
+    y_red = ops.conv_forward(h_plain, w2, 1, 1, math=ops.MATH_F16, w_version=9)
+    assert torch.equal(y_tag, y_red)
+    gy = rn(2, 24, 20, 128)
+    dw_tag, dw_red = torch.zeros(128, 3, 3, 256, device="cuda"), torch.zeros(128, 3, 3, 256, device="cuda")
+    ops.conv_wgrad(h, gy, dw_tag, 1, 1, math=ops.MATH_F16)
+    ops.conv_wgrad(h_plain, gy.clone(), dw_red, 1, 1, math=ops.MATH_F16)
+    assert torch.equal(dw_tag, dw_red)
+
+
+def test_nonfinite_operand_flags_and_poisons():
+    from abr_iod_amd import ops
+    rn, _ = _gen(31)
+    x, w = rn(1, 256, 1, 512), rn(128, 1, 1, 512)
+    x[0, 17, 0, 5] = float("inf")
+    ops.x6_range_flags(reset=True)
+    y = ops.conv_forward(x, w, 1, 0, math=ops.MATH_F16)
+    assert ops.x6_range_flags(reset=True) & ops.X6_FLAG_NONFINITE
+    assert not bool(torch.isfinite(y[0, 17]).any())        # the row that holds the inf is poisoned
+    gy = rn(1, 256, 1, 128)
+    dw = torch.zeros(128, 1, 1, 512, device="cuda")
+    ops.conv_wgrad(x, gy, dw, 1, 0, math=ops.MATH_F16)
+    assert ops.x6_range_flags(reset=True) & ops.X6_FLAG_NONFINITE
+    assert not bool(torch.isfinite(dw).all())
+
+
+def test_stale_amax_word_raises_the_flag():
+    import ctypes as C
+    from abr_iod_amd import _lib as L, ops
+    rn, _ = _gen(32)
+    x, w = rn(1, 64, 1, 64), rn(64, 1, 1, 64)
+    word, epoch = ops.amax_new()
+    L.check(L.lib().abr_h3_amax(L.ptr(x), x.numel(), word, epoch, L.stream()), "h3_amax")
+    d = ops.conv_desc(x.shape, w.shape, 1, 0, math=ops.MATH_F16)
+    out = torch.empty(1, 64, 1, 64, device="cuda")
+    ops.x6_range_flags(reset=True)
+    d.x_amax, d.x_amax_epoch = word, epoch
+    L.check(L.lib().abr_conv_forward(C.byref(d), L.ptr(x), L.ptr(w), L.ptr(out), L.stream()), "conv_forward")
+    assert ops.x6_range_flags(reset=True) & ops.H3_FLAG_STALE == 0
+    d.x_amax_epoch = epoch + 1
+    L.check(L.lib().abr_conv_forward(C.byref(d), L.ptr(x), L.ptr(w), L.ptr(out), L.stream()), "conv_forward")
+    assert ops.x6_range_flags(reset=True) & ops.H3_FLAG_STALE
+
+
+TINY = ["MODEL.RESNETS.STEM_OUT_CHANNELS", 16, "MODEL.RESNETS.RES2_OUT_CHANNELS", 32, "MODEL.RESNETS.WIDTH_PER_GROUP", 8,
+        "MODEL.RESNETS.BACKBONE_OUT_CHANNELS", 128]
+
+
+def test_model_wiring_and_a_teacher_forced_bottleneck():
+    from abr_iod_amd import ops
+    from abr_iod_amd.engine.synthetic import build_models, make_cfgs
+    cfg_s, cfg_t = make_cfgs("15-5", overrides=["DTYPE", "float16"])
+    ms, mt = build_models(cfg_s, cfg_t, seed=0)
+    for m in (ms, mt):
+        assert m.conv_math == "f16"
+        blocks = [b for b in m.backbone.modules() if type(b).__name__ == "Bottleneck"] + \
+                 [b for b in m.roi_heads.modules() if type(b).__name__ == "Bottleneck"]
+        assert len(blocks) == 16 and all(b.math == ops.MATH_F16 for b in blocks)      # 13 in the body + 3 in the layer4 head
+        assert m.rpn.head.math == ops.MATH_F16
+        stem = m.backbone.body.stem
+        assert not hasattr(stem, "math")      # the stem always calls the fp32 kernels; its Cin = 4 is outside the route's Cin % 32 rule anyway
+    # teacher-forced: each conv of layer2's first block, restated on the GPU's own input to it
+    blk = mt.backbone.body.layer2[0]
+    x = torch.relu(torch.randn(2, 48, 64, 256, generator=torch.Generator().manual_seed(1))).cuda()
+    with torch.no_grad():
+        out, saved = blk.fwd(x.contiguous(), True)
+    _, o1, o2 = saved[0], saved[1], saved[2]
+
+    def conv_bn(inp, conv, bn, stride, pad):
+        s, b = bn.scale_bias()
+        return _conv64(_q(inp), _q(conv.weight, per_row=True), stride, pad) * s.double().cpu() + b.double().cpu()
+
+    r1 = torch.relu(conv_bn(x, blk.conv1, blk.bn1, blk.stride, 0))
+    r2 = torch.relu(conv_bn(o1, blk.conv2, blk.bn2, 1, 1))
+    idt = conv_bn(x, blk.downsample[0], blk.downsample[1], blk.stride, 0)
+    r3 = torch.relu(conv_bn(o2, blk.conv3, blk.bn3, 1, 0) + idt)
+    for name, got, want in (("conv1", o1, r1), ("conv2", o2, r2), ("conv3 + downsample", out, r3)):
+        rel = float((got.double().cpu() - want).norm() / want.norm())
+        print(f"teacher-forced {name}: rel. distance {rel:.2e}")
+        assert rel < 1e-5, (name, rel)
+
+
+SMALL = ["MODEL.RPN.PRE_NMS_TOP_N_TRAIN", 600, "MODEL.RPN.POST_NMS_TOP_N_TRAIN", 200, "MODEL.RPN.PRE_NMS_TOP_N_TEST", 300,
+         "MODEL.RPN.POST_NMS_TOP_N_TEST", 150, "MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE", 64, "MODEL.RPN.BATCH_SIZE_PER_IMAGE", 64]
+
+
+def _step(dtype, overrides, images, targets):
+    import random
+    from abr_iod_amd import ops
+    from abr_iod_amd.engine import train_step
+    from abr_iod_amd.engine.synthetic import build_models, make_cfgs
+    from abr_iod_amd.solver.build import make_lr_scheduler, make_optimizer
+    cfg_s, cfg_t = make_cfgs(*overrides[0], **overrides[1], overrides=overrides[2] + ["DTYPE", dtype])
+    ms, mt = build_models(cfg_s, cfg_t, seed=0)
+    ops._sample_calls[0] = 0
+    random.seed(0)
+    opt = make_optimizer(cfg_t, mt)
+    sch = make_lr_scheduler(cfg_t, opt)
+    before = mt.flat.params.clone()
+    ld, _ = train_step(ms, mt, images, targets, opt, sch, cfg_t)
+    torch.cuda.synchronize()
+    return {k: float(v.detach()) for k, v in ld.items()}, (mt.flat.params - before).clone(), mt.conv_math
+
+
+def test_training_step_tracks_fp32():
+    """the same seeded tiny step under float32 (the default f16x3 arithmetic) and float16"""
+    from abr_iod_amd.engine.synthetic import synthetic_batch
+    images, targets = synthetic_batch(2, 192, 256, seed=4, label_range=(11, 16), max_boxes=2)
+    for t in targets:
+        t.bbox[:, 0::2].clamp_(max=255); t.bbox[:, 1::2].clamp_(max=191)
+        t.bbox[:, 2] = torch.max(t.bbox[:, 2], t.bbox[:, 0] + 8).clamp(max=255); t.bbox[:, 3] = torch.max(t.bbox[:, 3], t.bbox[:, 1] + 8).clamp(max=191)
+    spec = (("10-5",), dict(dist_type="id", feat="ard", alpha=0.5, beta=1.0), SMALL)
+    l32, d32, _ = _step("float32", spec, images, targets)
+    l16, d16, math = _step("float16", spec, images, targets)
+    assert math == "f16"
+    worst = 0.0
+    for k in l32:
+        assert np.isfinite(l16[k]), k
+        rel = abs(l16[k] - l32[k]) / max(abs(l32[k]), 0.02)
+        worst = max(worst, rel)
+        print(f"{k}: float32 {l32[k]:.6f}  float16 {l16[k]:.6f}  ({rel:.2e})")
+    cos = float((d32 * d16).sum() / (d32.norm() * d16.norm()))
+    print(f"worst loss deviation {worst:.2e}, cosine of the first updates {cos:.6f}")
+    # bounds from the first MI355X run with >= 3x margin (measured: 3.1e-4, 1 - cos = 1.4e-5); the bf16 backbone's test allows 5 % and 0.98
+    assert worst <= 1e-3, worst
+    assert cos > 0.9999, cos
+
+
+def test_full_size_step_tracks_fp32():
+    """one configs[2] step (15-5, ID + ARD, B = 4, 600x1000): the losses are finite and within 2 % of the float32 step on the same batch"""
+    from abr_iod_amd.engine.synthetic import synthetic_batch
+    images, targets = synthetic_batch(4, 600, 1000, seed=7)
+    spec = (("15-5",), dict(dist_type="id", feat="ard", alpha=0.5, beta=1.0), [])
+    l32, _, _ = _step("float32", spec, images, targets)
+    torch.cuda.empty_cache()
+    l16, _, math = _step("float16", spec, images, targets)
+    assert math == "f16" and set(l16) == set(l32), (sorted(l16), sorted(l32))
+    for k in l32:
+        rel = abs(l16[k] - l32[k]) / max(abs(l32[k]), 1e-3)
+        print(f"{k}: float32 {l32[k]:.6f}  float16 {l16[k]:.6f}  ({rel:.2e})")
+        assert np.isfinite(l16[k]) and rel <= 0.02, (k, l32[k], l16[k])
+
+
+def test_trainer_guard_on_f16():
+    """an inf operand moves both models to the fp32 MFMA kernels, and the next step is finite"""
+    import logging
+    from abr_iod_amd import ops
+    from abr_iod_amd.engine import train_step, trainer
+    from abr_iod_amd.engine.synthetic import build_models, make_cfgs, synthetic_batch
+    from abr_iod_amd.solver.build import make_lr_scheduler, make_optimizer
+    cfg_s, cfg_t = make_cfgs("15-5", overrides=TINY + SMALL + ["DTYPE", "float16"])
+    ms, mt = build_models(cfg_s, cfg_t, seed=0)
+    assert mt.conv_math == ms.conv_math == "f16"
+    ops.x6_range_flags(reset=True)
+    trainer.trainer_state(mt).x6_watch = None
+    for _ in range(3):                       # clean polls: nothing happens
+        trainer._x6_guard(ms, mt)
+        torch.cuda.synchronize()
+    assert mt.conv_math == "f16"
+    rn, _ = _gen(40)
+    bad = rn(1, 384, 1, 1024)
+    bad[0, 5, 0, 7] = float("inf")
+    ops.conv_forward(bad, rn(256, 1, 1, 1024), 1, 0, math=ops.MATH_F16)
+    records = []
+    h = logging.Handler()
+    h.emit = records.append
+    log = logging.getLogger("f16test")
+    log.addHandler(h)
+    log.setLevel(logging.INFO)
+    for _ in range(4):                       # the polls are asynchronous: the flag is seen a step or two later
+        trainer._x6_guard(ms, mt, log)
+        torch.cuda.synchronize()
+    assert mt.conv_math == ms.conv_math == "f32"
+    assert all(m.math == ops.MATH_F32 for m in mt.modules() if hasattr(m, "math"))
+    assert len(records) == 1 and "range guard tripped" in records[0].getMessage()
+    ops.x6_range_flags(reset=True)
+    images, targets = synthetic_batch(2, 192, 256, seed=4, max_boxes=2)
+    for t in targets:
+        t.bbox[:, 0::2].clamp_(max=255); t.bbox[:, 1::2].clamp_(max=191)
+        t.bbox[:, 2] = torch.max(t.bbox[:, 2], t.bbox[:, 0] + 8).clamp(max=255); t.bbox[:, 3] = torch.max(t.bbox[:, 3], t.bbox[:, 1] + 8).clamp(max=191)
+    opt = make_optimizer(cfg_t, mt)
+    sch = make_lr_scheduler(cfg_t, opt)
+    ld, _ = train_step(ms, mt, images, targets, opt, sch, cfg_t)
+    torch.cuda.synchronize()
+    assert all(np.isfinite(float(v.detach())) for v in ld.values()), ld

@@ -133,6 +133,7 @@ _SIGS = {
     "abr_nchw_to_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "abr_nhwc_to_nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "abr_maxpool3x3s2": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_maxpool3x3s2_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "abr_avgpool_forward": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "abr_avgpool_backward": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "abr_avgpool_relu_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -84,6 +84,92 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ 
     }
 }
 
+// Backward of max_pool2d(3, 2, 1) o ReLU for the trainable stem, in gather form (no atomics): g_y = relu'(y) * sum of g_pool over the windows whose
+// selected element is this pixel.  One lane owns the 2x2 input quad rows {2ho, 2ho+1} x cols {2wo, 2wo+1} and one 16 B channel group.  Input row 2ho
+// lies only in window row ho, row 2ho+1 in ho and ho+1 (the same for columns): the quad's pixels are selected only by the windows (ho..ho+1) x
+// (wo..wo+1).  Each of them re-scans its 3x3 with maxpool_kernel's rule (torch's: dy, then dx; `v > m || isnan(v)`, the first in-bounds element
+// when nothing replaces -inf) and hands its gradient to the selected pixel if that is in the quad.  Windows are visited in ascending (ho, wo), so a
+// pixel's sum is formed in the order torch's CPU scatter forms it.  The ReLU rule is threshold_backward's: zero where y <= 0 (a NaN passes).
+// Every element of g_y is written.
+__global__ __launch_bounds__(256) void maxpool_relu_bwd_kernel(const float* __restrict__ y, const float* __restrict__ gp, int B, int H, int W,
+                                                                int C, int Ho, int Wo, float* __restrict__ gy) {
+    const int cv = C / 4;
+    const int64_t total = (int64_t)B * Ho * Wo * cv;
+    const float4* yv = reinterpret_cast<const float4*>(y);
+    const float4* gv = reinterpret_cast<const float4*>(gp);
+    float4* ov = reinterpret_cast<float4*>(gy);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = i % cv;
+        const int64_t pix = i / cv;
+        const int wo = pix % Wo, ho = (pix / Wo) % Ho, b = pix / ((int64_t)Wo * Ho);
+        float acc[2][2][4];
+#pragma unroll
+        for (int pr = 0; pr < 2; pr++)
+#pragma unroll
+            for (int pc = 0; pc < 2; pc++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[pr][pc][j] = 0.f;
+#pragma unroll
+        for (int dh = 0; dh < 2; dh++) {
+            const int wh = ho + dh;
+            if (wh >= Ho) continue;
+#pragma unroll
+            for (int dw = 0; dw < 2; dw++) {
+                const int ww = wo + dw;
+                if (ww >= Wo) continue;
+                // argmax of window (wh, ww), as quad-relative (row, col) per channel: window row dy is quad row 2 dh - 1 + dy
+                float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                int sr[4], sc[4];
+                const int h0 = max(wh * 2 - 1, 0), w0 = max(ww * 2 - 1, 0);
+#pragma unroll
+                for (int j = 0; j < 4; j++) { sr[j] = h0 - 2 * ho; sc[j] = w0 - 2 * wo; }
+#pragma unroll
+                for (int dy = 0; dy < 3; dy++) {
+                    const int hi = wh * 2 - 1 + dy;
+                    if ((unsigned)hi >= (unsigned)H) continue;
+#pragma unroll
+                    for (int dx = 0; dx < 3; dx++) {
+                        const int wi = ww * 2 - 1 + dx;
+                        if ((unsigned)wi >= (unsigned)W) continue;
+                        const float4 v4 = yv[(((size_t)b * H + hi) * W + wi) * cv + c];
+                        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            const bool take = v[j] > m[j] || v[j] != v[j];
+                            m[j] = take ? v[j] : m[j];
+                            sr[j] = take ? 2 * dh - 1 + dy : sr[j];
+                            sc[j] = take ? 2 * dw - 1 + dx : sc[j];
+                        }
+                    }
+                }
+                const float4 g4 = gv[(((size_t)b * Ho + wh) * Wo + ww) * cv + c];
+                const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+                for (int pr = 0; pr < 2; pr++)
+#pragma unroll
+                    for (int pc = 0; pc < 2; pc++)
+#pragma unroll
+                        for (int j = 0; j < 4; j++)
+                            if (sr[j] == pr && sc[j] == pc) acc[pr][pc][j] += g[j];
+            }
+        }
+#pragma unroll
+        for (int pr = 0; pr < 2; pr++) {
+            const int hi = 2 * ho + pr;
+            if (hi >= H) continue;
+#pragma unroll
+            for (int pc = 0; pc < 2; pc++) {
+                const int wi = 2 * wo + pc;
+                if (wi >= W) continue;
+                const size_t o = (((size_t)b * H + hi) * W + wi) * cv + c;
+                const float4 v = yv[o];
+                ov[o] = make_float4(v.x <= 0.f ? 0.f : acc[pr][pc][0], v.y <= 0.f ? 0.f : acc[pr][pc][1],
+                                    v.z <= 0.f ? 0.f : acc[pr][pc][2], v.w <= 0.f ? 0.f : acc[pr][pc][3]);
+            }
+        }
+    }
+}
+
 // x [N,HW,C] -> out [N,C] mean over HW
 __global__ __launch_bounds__(256) void avgpool_fwd_kernel(const float* __restrict__ x, int64_t N, int HW, int C,
                                                            float* __restrict__ out) {
@@ -287,6 +373,17 @@ extern "C" int abr_maxpool3x3s2(const float* x, int B, int H, int W, int C, floa
     maxpool_kernel<<<(unsigned)std::min<int64_t>((total + 255) / 256, 16384), 256, 0, abr::as_stream(stream)>>>(x, B, H, W, C,
                                                                                                                   Ho, Wo, out);
     ABR_CHECK_LAUNCH("maxpool3x3s2");
+    return ABR_OK;
+}
+
+extern "C" int abr_maxpool3x3s2_backward(const float* y, const float* g_pool, int B, int H, int W, int C, float* g_y, void* stream) {
+    ABR_REQUIRE(y && g_pool && g_y && B >= 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool3x3s2_backward: bad args (C % 4 == 0)");
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
+    if (total == 0) return ABR_OK;
+    maxpool_relu_bwd_kernel<<<(unsigned)std::min<int64_t>((total + 255) / 256, 16384), 256, 0, abr::as_stream(stream)>>>(y, g_pool, B, H, W, C,
+                                                                                                                           Ho, Wo, g_y);
+    ABR_CHECK_LAUNCH("maxpool3x3s2_backward");
     return ABR_OK;
 }
 

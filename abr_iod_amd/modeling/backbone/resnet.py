@@ -507,12 +507,40 @@ class StemWithFixedBatchNorm(nn.Module):
 
     def forward(self, x):
         """x: [B,3,H,W] plain NCHW image batch -> logical [B,64,H/4,W/4]"""
+        if torch.is_grad_enabled() and self.conv1.weight.requires_grad:   # FREEZE_CONV_BODY_AT = 0: the stem trains
+            return _StemFn.apply(x, self, self.conv1.weight)
+        return from_nhwc(self._run(x)[2])
+
+    def _run(self, x):
+        """(padded NHWC image, conv+FrozenBN+ReLU output y, pooled output)"""
         xh = ops.nchw_to_nhwc(x.contiguous(), cpad=4) if x.shape[1] == 3 else as_nhwc(x)
         s, b = self.bn1.scale_bias()
         # (the stem runs on the fp32 MFMA kernel; its epilogue still writes the output's amax word for layer1's f16x3 convs: the pooled tensor
         #  inherits it as a bound instead of being reduced again)
         y = ops.conv_forward(xh, self.conv1.weight, 2, 3, scale=s, bias=b, relu=True, emit_amax=True)
-        return from_nhwc(ops.maxpool3x3s2(y))
+        return xh, y, ops.maxpool3x3s2(y)
+
+
+class _StemFn(Function):
+    """The trainable stem (FREEZE_CONV_BODY_AT = 0) as one autograd node: the same launches as the frozen stem forward; backward routes the pooled
+    gradient through max-pool and ReLU (ops.maxpool3x3s2_backward) and accumulates the weight gradient, with the FrozenBN scale, into the weight's
+    flat-gradient view on the weight-gradient side stream.  No gradient for the image (ResNet.forward refuses an image that requires one)."""
+
+    @staticmethod
+    def forward(ctx, x, stem, weight):
+        ctx.stem = stem
+        xh, y, pooled = stem._run(x)
+        ctx.xh, ctx.y = xh, y
+        return from_nhwc(pooled)
+
+    @staticmethod
+    def backward(ctx, gout):
+        stem, xh, y = ctx.stem, ctx.xh, ctx.y
+        ctx.xh = ctx.y = None
+        gy = ops.maxpool3x3s2_backward(y, as_nhwc(gout))
+        conv = stem.conv1
+        ops.conv_wgrad_async(xh, gy, _grad_buf(conv.weight), conv.stride, conv.padding, scale=stem.bn1.scale_bias()[0], math=ops.MATH_F32)
+        return None, None, None
 
 
 class ResNet(nn.Module):
@@ -585,11 +613,12 @@ class ResNet(nn.Module):
 
     def forward(self, x, prefix=None):
         """`prefix`: the result of frozen_prefix() on the same input (the same values the inline path computes)"""
-        if torch.is_grad_enabled() and x.requires_grad and self.frozen_prefix is not None and not self._trains("stem"):
-            # the frozen stem / stages run without autograd (their kernels have no backward): a gradient w.r.t. the IMAGE would silently be
-            # dropped.  The reference's training loop never asks for one (images come from the data loader); fail loudly instead.
-            raise NotImplementedError("gradients with respect to the input image are not implemented: the frozen stem (FREEZE_CONV_BODY_AT >= 1) "
-                                      "has no backward pass")
+        if torch.is_grad_enabled() and x.requires_grad:
+            # the frozen stem runs without autograd, and the trainable stem's backward (_StemFn, FREEZE_CONV_BODY_AT = 0) stops at its weight: a
+            # gradient w.r.t. the IMAGE would silently be dropped.  The reference's training loop never asks for one (images come from the data
+            # loader); fail loudly instead.
+            raise NotImplementedError("gradients with respect to the input image are not implemented: the stem's backward pass ends at its weight "
+                                      "(FREEZE_CONV_BODY_AT 0) or does not exist (the frozen stem, FREEZE_CONV_BODY_AT >= 1)")
         outputs, backbone_features = [], []
         if prefix is None:
             prefix = self.frozen_prefix(x)

@@ -932,6 +932,19 @@ def maxpool3x3s2(x):
     return amax_carry_bound(out, x)   # (every input pixel lies in some window: max |pooled| <= max |x|, equal for a ReLU's output)
 
 
+def maxpool3x3s2_backward(y, g_pool):
+    """Backward of maxpool3x3s2 fused with the ReLU that produced its input y [B,H,W,C] (the stem's): g_pool [B,Ho,Wo,C] -> g_y [B,H,W,C],
+    each window's gradient routed to the element maxpool3x3s2 selected (torch's rule), zero where y <= 0.  Deterministic gather, no atomics."""
+    L.require_cuda(y, g_pool)
+    y, g_pool = L.f32c(y), L.f32c(g_pool)
+    B, H, W, Ch = y.shape
+    if tuple(g_pool.shape) != (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Ch):
+        raise RuntimeError(f"maxpool3x3s2_backward: g_pool {tuple(g_pool.shape)} does not match y {tuple(y.shape)}")
+    out = _empty(y.shape, y)
+    L.check(L.lib().abr_maxpool3x3s2_backward(L.ptr(y), L.ptr(g_pool), B, H, W, Ch, L.ptr(out), L.stream()), "maxpool3x3s2_backward")
+    return out
+
+
 def avgpool_forward(x):
     """x [N,h,w,C] -> [N,C]"""
     x = L.f32c(x)

@@ -404,6 +404,9 @@ int abr_nchw_to_nhwc_pad(const float* x, int B, int C, int H, int W, int Cpad, f
 int abr_nhwc_to_nchw(const float* x, int B, int C, int H, int W, float* out, void* stream);
 int abr_nchw_to_nhwc(const float* x, int B, int C, int H, int W, float* out, void* stream);
 int abr_maxpool3x3s2(const float* x, int B, int H, int W, int C, float* out, void* stream); /* resnet.py:367 */
+/* its backward fused with the ReLU that produced x (the stem's y [B,H,W,C]): g_y = (y <= 0 ? 0 : sum of g_pool [B,Ho,Wo,C] over the windows
+ * whose selected element -- maxpool's rule: first maximum in (dy, dx) order, a NaN wins -- is this pixel).  Gather form, deterministic; writes all of g_y */
+int abr_maxpool3x3s2_backward(const float* y, const float* g_pool, int B, int H, int W, int C, float* g_y, void* stream);
 /* AdaptiveAvgPool2d(1)  roi_box_predictors.py:28 : x [N,HW,C] -> out [N,C] ; backward spreads g/HW */
 int abr_avgpool_forward(const float* x, int N, int HW, int C, float* out, void* stream);
 int abr_avgpool_backward(const float* g, int N, int HW, int C, float* gx, void* stream);

@@ -109,6 +109,10 @@ _C.MODEL.RESNETS.RES5_DILATION = 1
 _C.MODEL.RESNETS.BACKBONE_OUT_CHANNELS = 256 * 4
 _C.MODEL.RESNETS.RES2_OUT_CHANNELS = 256
 _C.MODEL.RESNETS.STEM_OUT_CHANNELS = 64
+# deformable conv2 in the body's stages 1..3 (defaults.py:317-319; STAGE_WITH_DCN[3] has no effect on C4: the layer4 head has none)
+_C.MODEL.RESNETS.STAGE_WITH_DCN = (False, False, False, False)
+_C.MODEL.RESNETS.WITH_MODULATED_DCN = False
+_C.MODEL.RESNETS.DEFORMABLE_GROUPS = 1
 
 _C.MODEL.RPN = CN()
 _C.MODEL.RPN.USE_FPN = False

@@ -1,7 +1,8 @@
 """ResNet-50 C4 body and C5 head on the HIP conv engine.
 
 Mirror of maskrcnn_benchmark/modeling/backbone/resnet.py for the one variant every configs/voc YAML uses
-(CONV_BODY "R-50-C4", BottleneckWithFixedBatchNorm, StemWithFixedBatchNorm, STRIDE_IN_1X1=True, no DCN, groups=1):
+(CONV_BODY "R-50-C4", BottleneckWithFixedBatchNorm, StemWithFixedBatchNorm, STRIDE_IN_1X1=True, groups=1), with the deformable conv2 of
+STAGE_WITH_DCN / WITH_MODULATED_DCN / DEFORMABLE_GROUPS in layer1..layer3 (resnet.py:105-125, :289-312; layers/misc.py:114-190):
     ResNet (:81-155)       stem + layer1..layer3, FREEZE_CONV_BODY_AT semantics of _freeze_backbone (:134-143)
     ResNetHead (:158-207)  layer4, used by ResNet50Conv5ROIFeatureExtractor
     Bottleneck (:242-346), BaseStem (:349-368)
@@ -50,15 +51,17 @@ def bump_trained_version():
 
 class Conv2d(nn.Module):
     """nn.Conv2d stand-in (layers/misc.py:30-43) holding an OHWI weight [Cout,R,S,Cin]; `cin_pad` zero-pads input
-    channels (the 3-channel stem runs with Cin=4 so that every gather is a 16 B load)."""
+    channels (the 3-channel stem runs with Cin=4 so that every gather is a 16 B load), `cout_pad` output channels (zero rows and bias
+    entries that no consumer reads: the offset field of a deformable conv, 18 / 27 channels, is computed 32 wide)."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, cin_pad=None):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, cin_pad=None, cout_pad=None):
         super().__init__()
         self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
         self.stride, self.padding = stride, padding
         cin = cin_pad or in_channels
-        self.weight = nn.Parameter(torch.zeros(out_channels, kernel_size, kernel_size, cin))
-        self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
+        cout = cout_pad or out_channels
+        self.weight = nn.Parameter(torch.zeros(cout, kernel_size, kernel_size, cin))
+        self.bias = nn.Parameter(torch.zeros(cout)) if bias else None
         self._wt = None
         self._wt_version = -1
         self._optimised = False   # set by FusedSGD for the convs it updates: their version moves with every optimiser step
@@ -70,17 +73,21 @@ class Conv2d(nn.Module):
         bound = (6.0 / ((1 + a * a) * fan_in)) ** 0.5
         with torch.no_grad():
             self.weight.zero_()
-            self.weight[..., : self.in_channels].uniform_(-bound, bound)
+            self.weight[: self.out_channels, ..., : self.in_channels].uniform_(-bound, bound)
 
     def load_oihw(self, w):
         """copy a reference-layout [Cout,Cin,R,S] tensor in"""
         with torch.no_grad():
             self.weight.zero_()
-            self.weight[..., : w.shape[1]].copy_(w.permute(0, 2, 3, 1))
+            self.weight[: w.shape[0], ..., : w.shape[1]].copy_(w.permute(0, 2, 3, 1))
         self._wt_version = -1
 
+    def ref_layout(self, t):
+        """the reference-layout [Cout,Cin,R,S] view of the real entries of `t`, a tensor shaped like the weight (the weight, its momentum)"""
+        return t[: self.out_channels, ..., : self.in_channels].permute(0, 3, 1, 2)
+
     def oihw(self):
-        return self.weight.detach()[..., : self.in_channels].permute(0, 3, 1, 2).contiguous()
+        return self.ref_layout(self.weight.detach()).contiguous()
 
     def dgrad_weight(self, scale=None):
         """[Cin,R,S,Cout] flipped copy with the FrozenBN scale folded in; rebuilt only after an optimiser step."""
@@ -102,6 +109,50 @@ class Conv2d(nn.Module):
     def version(self):
         """abr_conv_desc::w_version for this conv's weight and for its dgrad copy: non-zero, changes whenever the values may have"""
         return 2 * _PARAM_VERSION[0] + 1 if self._optimised else 2 * _STATIC_VERSION[0] + 2
+
+
+class DeformConv2d(Conv2d):
+    """The contraction of a deformable 3x3 conv (DeformConv / ModulatedDeformConv, layers/dcn/deform_conv_module.py), no bias.  It runs as
+    a 1x1 conv over the column tensor [B,H,W,9 Cin] of ops.deform_im2col (tap outermost), so the weight is held as that 1x1 conv's
+    [Cout,1,1,9 Cin] -- the same bytes as the OHWI [Cout,3,3,Cin] weight -- and every route, derived-weight cache and dgrad copy of the 1x1
+    conv applies unchanged.  The checkpoint boundary sees [Cout,Cin,3,3]."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__(9 * in_channels, out_channels, 1, bias=False)
+        self.in_channels, self.taps = in_channels, 3
+        # reset_parameters of the reference's DeformConv: U(-1/sqrt(n), 1/sqrt(n)), n = Cin * 3 * 3
+        bound = 1.0 / (9 * in_channels) ** 0.5
+        with torch.no_grad():
+            self.weight.uniform_(-bound, bound)
+
+    def load_oihw(self, w):
+        with torch.no_grad():
+            self.weight.copy_(w.permute(0, 2, 3, 1).reshape(self.weight.shape))
+        self._wt_version = -1
+
+    def ref_layout(self, t):
+        return t.view(self.out_channels, 3, 3, self.in_channels).permute(0, 3, 1, 2)
+
+
+class DFConv2d(nn.Module):
+    """DFConv2d (layers/misc.py:114-190) for the 3x3 stride-1 conv2 of a bottleneck: `offset`, a 3x3 conv with bias (C -> 18 dg offsets, or
+    v2 = modulated: 18 offsets + 9 mask logits), and `conv`, the deformable conv itself.  The offset conv's output is computed 32-wide
+    (cout_pad): the extra channels are zero weight rows no kernel reads as offsets, and their gradient is written as zero."""
+
+    def __init__(self, channels, modulated, deformable_groups):
+        super().__init__()
+        if modulated and deformable_groups != 1:
+            # DFConv2d slices om[:, :18] and om[:, -9:] whatever the number of groups: the reference's modulated form only works with one
+            raise NotImplementedError("WITH_MODULATED_DCN with DEFORMABLE_GROUPS = {}: the reference's DFConv2d slices 18 offset and 9 mask "
+                                      "channels whatever the number of deformable groups, so only 1 group is defined".format(deformable_groups))
+        if deformable_groups < 1 or channels % deformable_groups or (channels // deformable_groups) % 4:
+            raise NotImplementedError("DEFORMABLE_GROUPS = {} with {} channels: the groups must split the channels into multiples of 4"
+                                      .format(deformable_groups, channels))
+        com = 27 if modulated else 18 * deformable_groups
+        self.offset = Conv2d(channels, com, 3, stride=1, padding=1, bias=True, cout_pad=(com + 31) // 32 * 32)
+        self.offset.kaiming_uniform_(a=1)     # bias: constant 0
+        self.conv = DeformConv2d(channels, channels)
+        self.modulated, self.deformable_groups = bool(modulated), int(deformable_groups)
 
 
 def _grad_buf(p):
@@ -257,7 +308,8 @@ def _numel(shape):
 class Bottleneck(nn.Module):
     """resnet.py:242-346 (BottleneckWithFixedBatchNorm :371-395): 1x1(stride) -> 3x3 -> 1x1 (+identity / 1x1(stride) downsample) -> ReLU."""
 
-    def __init__(self, in_channels, bottleneck_channels, out_channels, stride):
+    def __init__(self, in_channels, bottleneck_channels, out_channels, stride, dcn=None):
+        """dcn: None, or (modulated, deformable_groups) for a deformable conv2 (DFConv2d)"""
         super().__init__()
         self.downsample = None
         if in_channels != out_channels:
@@ -265,11 +317,15 @@ class Bottleneck(nn.Module):
             self.downsample[0].kaiming_uniform_()
         self.conv1 = Conv2d(in_channels, bottleneck_channels, 1, stride=stride, bias=False)  # STRIDE_IN_1X1
         self.bn1 = FrozenBatchNorm2d(bottleneck_channels)
-        self.conv2 = Conv2d(bottleneck_channels, bottleneck_channels, 3, stride=1, padding=1, bias=False)
+        self.dcn = dcn is not None
+        if self.dcn:   # (STRIDE_IN_1X1: the 3x3 conv is always stride 1, pad 1, dilation 1 here)
+            self.conv2 = DFConv2d(bottleneck_channels, *dcn)
+        else:
+            self.conv2 = Conv2d(bottleneck_channels, bottleneck_channels, 3, stride=1, padding=1, bias=False)
         self.bn2 = FrozenBatchNorm2d(bottleneck_channels)
         self.conv3 = Conv2d(bottleneck_channels, out_channels, 1, bias=False)
         self.bn3 = FrozenBatchNorm2d(out_channels)
-        for l in (self.conv1, self.conv2, self.conv3):
+        for l in (self.conv1, self.conv3) if self.dcn else (self.conv1, self.conv2, self.conv3):
             l.kaiming_uniform_()
         self.stride = stride
         self.math = ops.MATH_F32   # ops.MATH_BF16: bf16 MFMA contractions (cfg.DTYPE == "bfloat16", see set_conv_math)
@@ -286,13 +342,10 @@ class Bottleneck(nn.Module):
         """Rebuild, on the current stream, everything this block derives from its trainable weights: the flipped / BN-scaled dgrad
         copies and, inside the library, what abr_conv_forward derives from the weight and from its dgrad copy (Winograd-domain weights of
         the 3x3 conv, packed bf16x3 planes under bf16x6).  FusedSGD.step runs this on the weight-preparation stream right after the update."""
-        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
-        if self.downsample is not None:
-            pairs.append((self.downsample[0], self.downsample[1]))
-        for conv, bn in pairs:
+        for conv, scale in self._conv_scales():
             if not (conv.weight.requires_grad and conv.weight.is_cuda):
                 continue
-            wt = conv.dgrad_weight(bn.scale_bias()[0])
+            wt = conv.dgrad_weight(scale)
             ops.conv_prepare_weights(conv.weight, conv.stride, conv.padding, self.math, conv.version())
             # the dgrad conv is stride 1 with pad k-1-p (a scatter for the stride-2 1x1 convs): same derived data either way
             ops.conv_prepare_weights(wt, 1, conv.kernel_size - 1 - conv.padding, self.math, conv.version())
@@ -300,15 +353,25 @@ class Bottleneck(nn.Module):
     def prep_entries(self):
         """(conv, FrozenBN scale, stride, pad, math) of the trainable convs: FusedSGD prepares them all in one batched call instead of
         prepare_derived()'s four launches per conv"""
-        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
+        return [(conv, scale, conv.stride, conv.padding, self.math) for conv, scale in self._conv_scales()
+                if conv.weight.requires_grad and conv.weight.is_cuda]
+
+    def _conv_scales(self):
+        """(conv, FrozenBN scale folded into its dgrad copy or None) of every conv of the block; a deformable conv2 is its offset conv
+        (3x3, bias, no FrozenBN) and its contraction (the 1x1 conv over the columns, bn2)"""
+        if self.dcn:
+            pairs = [(self.conv1, self.bn1), (self.conv2.offset, None), (self.conv2.conv, self.bn2), (self.conv3, self.bn3)]
+        else:
+            pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
         if self.downsample is not None:
             pairs.append((self.downsample[0], self.downsample[1]))
-        return [(conv, bn.scale_bias()[0], conv.stride, conv.padding, self.math) for conv, bn in pairs
-                if conv.weight.requires_grad and conv.weight.is_cuda]
+        return [(conv, bn.scale_bias()[0] if bn is not None else None) for conv, bn in pairs]
 
     # x, returns NHWC tensors.  `stride` may be overridden to 1 when the caller already sub-sampled (bin_step=2 ROIAlign)
     def fwd(self, x, save, stride=None):
         s = self.stride if stride is None else stride
+        if self.dcn:
+            return self._fwd_dcn(x, save, s)
         if (BLOCK_PLANS and ops.H3_TAGS and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
                 and (save or not (self.math == ops.MATH_BF16X6 and ops.FUSE_TAIL64 and self.conv2.weight.shape[0] == 64))):
             plans = self.__dict__.setdefault("_fwd_plans", {})
@@ -340,9 +403,30 @@ class Bottleneck(nn.Module):
         out = self._conv(o2, self.conv3, 1, 0, scale=s3, bias=b3, residual=idt, relu=True)
         return out, ((x, o1, o2, out, s, v2) if save else None)
 
+    def _fwd_dcn(self, x, save, s):
+        """conv1 -> offset conv -> deform_im2col -> 1x1 conv over the columns (bn2, relu) -> conv3 + identity: the per-conv path (no _FwdPlan
+        table, no fused 64-wide tail, no Winograd).  Saves (x, o1, o2, out, s, om, cols) -- the columns are kept for conv2's weight gradient."""
+        s1, b1 = self.bn1.scale_bias()
+        s2, b2 = self.bn2.scale_bias()
+        s3, b3 = self.bn3.scale_bias()
+        off, dc = self.conv2.offset, self.conv2.conv
+        o1 = self._conv(x, self.conv1, s, 0, scale=s1, bias=b1, relu=True)
+        if self.downsample is not None:
+            sd, bd = self.downsample[1].scale_bias()
+            idt = self._conv(x, self.downsample[0], s, 0, scale=sd, bias=bd)
+        else:
+            idt = x
+        om = self._conv(o1, off, 1, 1, bias=off.bias)
+        cols = ops.deform_im2col(o1, om, self.conv2.deformable_groups, self.conv2.modulated)
+        o2 = self._conv(cols, dc, 1, 0, scale=s2, bias=b2, relu=True)
+        out = self._conv(o2, self.conv3, 1, 0, scale=s3, bias=b3, residual=idt, relu=True)
+        return out, ((x, o1, o2, out, s, om, cols) if save else None)
+
     def bwd(self, saved, gout, need_dx, g_owned, g_masked=False, mask_dx=None):
         """gout = dL/d(out), not yet masked by out's ReLU unless g_masked.  Writes weight grads into .grad; returns dL/dx or None.
         mask_dx (the producer block's output, = this block's x): fuse THAT block's ReLU backward into the last dgrad launch."""
+        if self.dcn:
+            return self._bwd_dcn(saved, gout, need_dx, g_owned, g_masked, mask_dx)
         x, o1, o2, out, s, v2 = saved
         s1, _ = self.bn1.scale_bias()
         s2, _ = self.bn2.scale_bias()
@@ -383,6 +467,33 @@ def _bwd_pairs(self, x, o1, o2, s, v2, g, need_dx, mask_dx, s1, s2, s3):
     c1, c2, c3 = self.conv1, self.conv2, self.conv3
     g2 = ops.conv_backward(o2, g, _grad_buf(c3.weight), c3.dgrad_weight(s3), 1, 0, scale=s3, math=m, w_version=c3.version(), mask=o2)
     g1 = ops.conv_backward(o1, g2, _grad_buf(c2.weight), c2.dgrad_weight(s2), 1, 1, scale=s2, math=m, w_version=c2.version(), wino_v=v2, mask=o1)
+    return _bwd_head(self, x, g, g1, s, need_dx, mask_dx, s1)
+
+
+def _bwd_dcn(self, saved, gout, need_dx, g_owned, g_masked=False, mask_dx=None):
+    """Bottleneck.bwd of a deformable block: conv3; the 1x1 conv over the columns (weight gradient from the saved columns, input gradient =
+    the columns' gradient); deform_col2im_coord (x's share by atomics, the offset field's gradient); the offset conv (weight and bias
+    gradients, input gradient + x's share through o1's ReLU in one epilogue); then conv1 / downsample as in every block."""
+    x, o1, o2, out, s, om, cols = saved
+    s1, _ = self.bn1.scale_bias()
+    s2, _ = self.bn2.scale_bias()
+    s3, _ = self.bn3.scale_bias()
+    m = self.math
+    c3, off, dc = self.conv3, self.conv2.offset, self.conv2.conv
+    g = gout if g_masked else ops.relu_backward(gout, out, inplace=g_owned)
+    g2 = ops.conv_backward(o2, g, _grad_buf(c3.weight), c3.dgrad_weight(s3), 1, 0, scale=s3, math=m, w_version=c3.version(), mask=o2)
+    dcol = ops.conv_backward(cols, g2, _grad_buf(dc.weight), dc.dgrad_weight(s2), 1, 0, scale=s2, math=m, w_version=dc.version())
+    dx_part, d_om = ops.deform_col2im_coord(dcol, o1, om, self.conv2.deformable_groups, self.conv2.modulated)
+    del dcol
+    g1 = ops.conv_backward(o1, d_om, _grad_buf(off.weight), off.dgrad_weight(None), 1, 1, math=m, w_version=off.version(), residual=dx_part, mask=o1)
+    ops.bias_grad(d_om, _grad_buf(off.bias))
+    return _bwd_head(self, x, g, g1, s, need_dx, mask_dx, s1)
+
+
+def _bwd_head(self, x, g, g1, s, need_dx, mask_dx, s1):
+    """the part of a bottleneck's backward pass that follows conv2: conv1's and the downsample branch's gradients, and dL/dx"""
+    m = self.math
+    c1 = self.conv1
     ds = self.downsample
     sd = ds[1].scale_bias()[0] if ds is not None else None
     if not need_dx:
@@ -409,6 +520,7 @@ def _bwd_pairs(self, x, o1, o2, s, v2, g, need_dx, mask_dx, s1, s2, s3):
 
 
 Bottleneck._bwd_pairs = _bwd_pairs
+Bottleneck._bwd_dcn = _bwd_dcn
 
 
 class _StageFn(Function):
@@ -487,10 +599,10 @@ def set_conv_math(module, math):
     return n
 
 
-def _make_stage(in_channels, bottleneck_channels, out_channels, block_count, first_stride):
+def _make_stage(in_channels, bottleneck_channels, out_channels, block_count, first_stride, dcn=None):
     blocks, stride = [], first_stride
     for _ in range(block_count):
-        blocks.append(Bottleneck(in_channels, bottleneck_channels, out_channels, stride))
+        blocks.append(Bottleneck(in_channels, bottleneck_channels, out_channels, stride, dcn=dcn))
         stride, in_channels = 1, out_channels
     return nn.Sequential(*blocks)
 
@@ -553,10 +665,13 @@ class ResNet(nn.Module):
         in_channels = cfg.MODEL.RESNETS.STEM_OUT_CHANNELS
         out2 = cfg.MODEL.RESNETS.RES2_OUT_CHANNELS
         self.stages, self.return_features = [], {}
+        with_dcn = tuple(cfg.MODEL.RESNETS.STAGE_WITH_DCN)
         for spec in ResNet50StagesTo4:
             name = "layer" + str(spec.index)
             f = 2 ** (spec.index - 1)
-            self.add_module(name, _make_stage(in_channels, width * f, out2 * f, spec.block_count, int(spec.index > 1) + 1))
+            # every block of a stage with STAGE_WITH_DCN[index - 1] gets a deformable conv2 (the layer4 head never does: roi_box_feature_extractors.py:27-36)
+            dcn = (bool(cfg.MODEL.RESNETS.WITH_MODULATED_DCN), int(cfg.MODEL.RESNETS.DEFORMABLE_GROUPS)) if with_dcn[spec.index - 1] else None
+            self.add_module(name, _make_stage(in_channels, width * f, out2 * f, spec.block_count, int(spec.index > 1) + 1, dcn=dcn))
             in_channels = out2 * f
             self.stages.append(name)
             self.return_features[name] = spec.return_features

@@ -906,6 +906,39 @@ def bias_grad(gy, db):
     return db
 
 
+# ---- deformable 3x3 conv (DCNv1 / v2 of the R-50-C4 body): columns for the 1x1 conv route and their gradient (csrc/deform.hip)
+def deform_im2col(x, om, dg=1, modulated=False):
+    """x [B,H,W,C], om [B,H,W,Com] (offsets, v2: + mask logits) -> cols [B,H,W,9C].  Bilinear weights sum to at most 1 and the mask lies in
+    (0, 1): x's amax word bounds cols, which inherits it (no reduction pass for the f16x3 consumer)."""
+    L.require_cuda(x, om)
+    x, om = L.f32c(x), L.f32c(om)
+    B, H, W, Ch = x.shape
+    if tuple(om.shape[:3]) != (B, H, W):
+        raise RuntimeError(f"deform_im2col: offsets {tuple(om.shape)} do not match x {tuple(x.shape)}")
+    cols = _empty((B, H, W, 9 * Ch), x)
+    L.check(L.lib().abr_deform_im2col(L.ptr(x), L.ptr(om), B, H, W, Ch, om.shape[3], int(dg), int(bool(modulated)), L.ptr(cols), L.stream()),
+            "deform_im2col")
+    return amax_carry_bound(cols, x)
+
+
+def deform_col2im_coord(dcol, x, om, dg=1, modulated=False):
+    """Backward of deform_im2col: (dx [B,H,W,C] from fp32 atomics -- not bit-reproducible, d_om [B,H,W,Com], deterministic, its padding
+    channels zero).  d_om carries an amax word written by the kernel."""
+    L.require_cuda(dcol, x, om)
+    dcol, x, om = L.f32c(dcol), L.f32c(x), L.f32c(om)
+    B, H, W, Ch = x.shape
+    if tuple(dcol.shape) != (B, H, W, 9 * Ch) or tuple(om.shape[:3]) != (B, H, W):
+        raise RuntimeError(f"deform_col2im_coord: dcol {tuple(dcol.shape)} / offsets {tuple(om.shape)} do not match x {tuple(x.shape)}")
+    dx = torch.zeros_like(x)
+    d_om = _empty(tuple(om.shape), om)
+    w, e = amax_new() if H3_TAGS else (None, 0)
+    L.check(L.lib().abr_deform_col2im_coord(L.ptr(dcol), L.ptr(x), L.ptr(om), B, H, W, Ch, om.shape[3], int(dg), int(bool(modulated)),
+                                            L.ptr(dx), L.ptr(d_om), w, e, L.stream()), "deform_col2im_coord")
+    if w is not None:
+        amax_tag(d_om, w, e)
+    return dx, d_om
+
+
 # ----------------------------------------------------------------------------------------------- pointwise
 def nchw_to_nhwc(x, cpad=None):
     x = L.f32c(x)

@@ -271,14 +271,20 @@ class FusedSGD(object):
         return dict(signature=self._prep_signature(), forward=forward, rest=rest, backward=backward, convs=[e[0] for e in allent], buckets=buckets)
 
     def _reference_params(self):
-        """(name, parameter, offset into the flat buffer, Conv2d module or None) for every trainable tensor, in the
-        reference optimiser's order = named_parameters() order of the requires_grad tensors (solver/build.py:9-18)."""
+        """(name, parameter, offset into the flat buffer, layout) for every trainable tensor, in the reference optimiser's order =
+        named_parameters() order of the requires_grad tensors (solver/build.py:9-18).  layout: None, or the function giving the
+        reference-layout view of the real entries of a tensor shaped like the parameter (conv weights; the bias of a cout_pad conv)."""
         from ..modeling.backbone.resnet import Conv2d
-        convs = {id(m.weight): m for m in self.model.modules() if isinstance(m, Conv2d)}
+        layouts = {}
+        for m in self.model.modules():
+            if isinstance(m, Conv2d):
+                layouts[id(m.weight)] = m.ref_layout
+                if m.bias is not None and m.bias.shape[0] != m.out_channels:
+                    layouts[id(m.bias)] = (lambda n: (lambda t: t[:n]))(m.out_channels)
         base = self.flat.params.data_ptr()
         for name, p in self.model.named_parameters():
             if p.requires_grad:
-                yield name, p, (p.data_ptr() - base) // 4, convs.get(id(p))
+                yield name, p, (p.data_ptr() - base) // 4, layouts.get(id(p))
 
     def _group_of(self, off):
         for g in self.param_groups:
@@ -290,15 +296,15 @@ class FusedSGD(object):
         """torch.optim.SGD.state_dict() layout -- what the reference's Checkpointer stores under "optimizer"
         (utils/checkpoint.py:41-43): one param group per tensor, momentum buffers in the reference's OIHW layout."""
         groups, state = [], {}
-        for i, (name, p, off, conv) in enumerate(self._reference_params()):
+        for i, (name, p, off, layout) in enumerate(self._reference_params()):
             g = self._group_of(off)
             groups.append({"lr": g["lr"], "momentum": self.momentum, "dampening": 0, "weight_decay": g["weight_decay"],
                            "nesterov": False, "maximize": False, "foreach": None, "differentiable": False, "fused": None,
                            "initial_lr": g["initial_lr"], "params": [i]})
             if self._steps > 0:
                 m = self.momentum_buffer[off:off + p.numel()].view(p.shape)
-                if conv is not None:
-                    m = m[..., : conv.in_channels].permute(0, 3, 1, 2)
+                if layout is not None:
+                    m = layout(m)
                 state[i] = {"momentum_buffer": m.contiguous().clone()}
         return {"state": state, "param_groups": groups}
 
@@ -308,7 +314,7 @@ class FusedSGD(object):
             raise ValueError("loaded state dict has {} parameter groups, the optimizer has {}".format(len(sd["param_groups"]), len(ref)))
         self.momentum_buffer.zero_()
         any_state = False
-        for i, ((name, p, off, conv), g_in) in enumerate(zip(ref, sd["param_groups"])):
+        for i, ((name, p, off, layout), g_in) in enumerate(zip(ref, sd["param_groups"])):
             g = self._group_of(off)
             for k in ("lr", "weight_decay", "initial_lr"):
                 if k in g_in:
@@ -318,9 +324,8 @@ class FusedSGD(object):
                 continue
             v = st["momentum_buffer"].to(self.momentum_buffer.device)
             m = self.momentum_buffer[off:off + p.numel()].view(p.shape)
-            if conv is not None:
-                v = v.permute(0, 2, 3, 1)
-                m = m[..., : conv.in_channels]
+            if layout is not None:
+                m = layout(m)
             if v.shape != m.shape:
                 raise ValueError("momentum buffer of {} has shape {}, expected {}".format(name, tuple(v.shape), tuple(m.shape)))
             m.copy_(v)

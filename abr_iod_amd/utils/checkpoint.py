@@ -10,9 +10,16 @@ from ..modeling.backbone.resnet import Conv2d, bump_param_version
 def reference_state_dict(model):
     out = {}
     convs = {id(m.weight): m for m in model.modules() if isinstance(m, Conv2d)}
+    # (a conv computed wider than it is -- cout_pad, the offset conv of a deformable conv2 -- stores only its real bias entries)
+    biases = {id(m.bias): m for m in model.modules() if isinstance(m, Conv2d) and m.bias is not None and m.bias.shape[0] != m.out_channels}
     for name, p in model.named_parameters():
         m = convs.get(id(p))
-        out[name] = m.oihw().clone() if m is not None else p.detach().clone()
+        if m is not None:
+            out[name] = m.oihw().clone()
+        elif id(p) in biases:
+            out[name] = p.detach()[: biases[id(p)].out_channels].clone()
+        else:
+            out[name] = p.detach().clone()
     for name, b in model.named_buffers():
         if name.endswith("cell_anchors"):
             # the reference registers its cell anchors through a BufferList (rpn/anchor_generator.py:13-31, 61): one buffer per level

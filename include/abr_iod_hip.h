@@ -407,6 +407,17 @@ int abr_maxpool3x3s2(const float* x, int B, int H, int W, int C, float* out, voi
 /* its backward fused with the ReLU that produced x (the stem's y [B,H,W,C]): g_y = (y <= 0 ? 0 : sum of g_pool [B,Ho,Wo,C] over the windows
  * whose selected element -- maxpool's rule: first maximum in (dy, dx) order, a NaN wins -- is this pixel).  Gather form, deterministic; writes all of g_y */
 int abr_maxpool3x3s2_backward(const float* y, const float* g_pool, int B, int H, int W, int C, float* g_y, void* stream);
+/* Deformable 3x3 conv (stride 1, pad 1; DCNv1, and DCNv2 = modulated with one deformable group) as columns for the 1x1 conv route.
+ * x [B,H,W,C], om [B,H,W,Com] (offset / mask field: dh of tap k = 3i+j and group g at 2k+18g, dw at 2k+1+18g; v2: mask logit of tap k at 18+k)
+ * -> cols [B,H,W,9C] (tap outermost): cols = m * bilinear(x, ho-1+i+dh, wo-1+j+dw), 0 outside the open box -1 < h < H, -1 < w < W.
+ * C / dg % 4 == 0. */
+int abr_deform_im2col(const float* x, const float* om, int B, int H, int W, int C, int Com, int dg, int modulated, float* cols, void* stream);
+/* its backward from dcol [B,H,W,9C]: dx [B,H,W,C] += the bilinear scatter of m * dcol (fp32 atomics: the caller zeroes dx; the order of the adds
+ * varies from run to run), d_om [B,H,W,Com] = d/d(dh, dw) and, under v2, d/d(mask logit), summed over each group's channels in a fixed order
+ * (deterministic); channels past the field's 18 dg (v2: 27) are written as 0.  d_om_amax (optional): max |d_om| into that amax word.
+ * C a power of two in [4, 1024]. */
+int abr_deform_col2im_coord(const float* dcol, const float* x, const float* om, int B, int H, int W, int C, int Com, int dg, int modulated,
+                            float* dx, float* d_om, uint64_t* d_om_amax, uint32_t d_om_amax_epoch, void* stream);
 /* AdaptiveAvgPool2d(1)  roi_box_predictors.py:28 : x [N,HW,C] -> out [N,C] ; backward spreads g/HW */
 int abr_avgpool_forward(const float* x, int N, int HW, int C, float* out, void* stream);
 int abr_avgpool_backward(const float* g, int N, int HW, int C, float* gx, void* stream);

@@ -264,7 +264,10 @@ DetWs det_ws(hipStream_t st, size_t nfloats) {
     if (!r.part) {
         if (hipMalloc(&r.part, kFloats * sizeof(float)) != hipSuccess) { r.part = nullptr; return DetWs{nullptr, nullptr}; }
         if (hipMalloc(&r.tick, kTickets * sizeof(unsigned)) != hipSuccess) { (void)hipFree(r.part); r.part = nullptr; return DetWs{nullptr, nullptr}; }
-        (void)hipMemset(r.tick, 0, kTickets * sizeof(unsigned));
+        // zeroed on `st` itself: a plain hipMemset goes to the null stream, which a non-blocking stream's first kernels do not wait for
+        if (hipMemsetAsync(r.tick, 0, kTickets * sizeof(unsigned), st) != hipSuccess) {
+            (void)hipFree(r.tick); (void)hipFree(r.part); r.part = nullptr; r.tick = nullptr; return DetWs{nullptr, nullptr};
+        }
     }
     if (r.head + nfloats > kFloats) r.head = 0;
     DetWs w{r.part + r.head, r.tick + (r.thead++ % kTickets)};

@@ -2072,7 +2072,8 @@ extern "C" int abr_bias_grad(const float* gy, int64_t M, int C, float* db, void*
     if (ws.part) {
         std::lock_guard<std::mutex> g(tick_mu);
         unsigned*& t = tick[abr::as_stream(stream)];
-        if (!t && (hipMalloc(&t, 64 * sizeof(unsigned)) != hipSuccess || hipMemset(t, 0, 64 * sizeof(unsigned)) != hipSuccess)) t = nullptr;
+        // (zeroed on the launch stream, as det_ws does: a non-blocking stream does not wait for a null-stream hipMemset)
+        if (!t && (hipMalloc(&t, 64 * sizeof(unsigned)) != hipSuccess || hipMemsetAsync(t, 0, 64 * sizeof(unsigned), abr::as_stream(stream)) != hipSuccess)) t = nullptr;
         tk = t;
     }
     bias_grad_kernel<<<grid, 256, 0, abr::as_stream(stream)>>>(gy, M, C, rows_per_block, db, tk ? ws.part : nullptr, tk);

@@ -162,15 +162,20 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     {
         const float* z = logits + (size_t)ii * ldz;
         const int64_t lab = labels[ii];
-        float mx = -INFINITY;
-        for (int c = l; c < K; c += G) mx = fmaxf(mx, z[c]);
+        float mx = -INFINITY, mo = -INFINITY;
+        for (int c = l; c < K; c += G) {
+            mx = fmaxf(mx, z[c]);
+            if (c <= n_old) mo = fmaxf(mo, z[c]);
+        }
 #pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, G));
+        for (int o = G / 2; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o, G)); mo = fmaxf(mo, __shfl_xor(mo, o, G)); }
+        // the inclusive background term's own shift: the row maximum while the old-class slice lies within 64 of it (the sum cannot
+        // underflow there), else the slice's maximum -- exp(z - mx) of a slice 88+ below the row maximum is 0 and lse(z[0..n_old]) -inf
+        const float mref = mx - mo < 64.f ? mx : mo;
         float se = 0.f, se_old = 0.f;
         for (int c = l; c < K; c += G) {
-            const float e = expf(z[c] - mx);
-            se += e;
-            if (c <= n_old) se_old += e;
+            se += expf(z[c] - mx);
+            if (c <= n_old) se_old += expf(z[c] - mref);
         }
 #pragma unroll
         for (int o = G / 2; o > 0; o >>= 1) { se += __shfl_xor(se, o, G); se_old += __shfl_xor(se_old, o, G); }
@@ -180,7 +185,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
             if (!inclusive) {
                 li = -(z[lab] - lse);
             } else if (lab == 0) {
-                li = -((logf(se_old) + mx) - lse);      // :155 outputs[:,0] = lse(z[0..n_old]) - den
+                li = -((logf(se_old) + mref) - lse);    // :155 outputs[:,0] = lse(z[0..n_old]) - den
             } else if (lab > n_old) {
                 li = -(z[lab] - lse);                   // :156
             } else {
@@ -195,7 +200,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
                 if (lab >= 0) {
                     const float p = expf(z[c] - lse);
                     if (!inclusive) v = p - (c == lab);
-                    else if (lab == 0) v = p - (c <= n_old ? expf(z[c] - mx) / se_old : 0.f);
+                    else if (lab == 0) v = p - (c <= n_old ? expf(z[c] - mref) / se_old : 0.f);
                     else if (lab > n_old) v = p - (c == lab);
                 }
                 g[c] = v * s;
@@ -248,21 +253,26 @@ __global__ __launch_bounds__(256) void roi_distill_kernel(const float* __restric
         const float* zt = z_t + (size_t)ii * ld_zt;
         const float inv_n = 1.f / (float)n;
         if (dist_id) {
-            float mt = -INFINITY, ms = -INFINITY;
-            for (int c = l; c < K_all; c += G) mt = fmaxf(mt, zt[c]);
+            float mt = -INFINITY, mb = -INFINITY, ms = -INFINITY;
+            for (int c = l; c < K_all; c += G) {
+                mt = fmaxf(mt, zt[c]);
+                if (c == 0 || c >= K_old) mb = fmaxf(mb, zt[c]);
+            }
             for (int c = l; c < K_old; c += G) ms = fmaxf(ms, zs[c]);
             mt = gmax(mt);
+            mb = gmax(mb);
             ms = gmax(ms);
+            // the background set's own shift, as in softmax_ce: mt unless the set lies 64+ below it (sebg would underflow to 0)
+            const float mref = mt - mb < 64.f ? mt : mb;
             float set = 0.f, sebg = 0.f, ses = 0.f;
             for (int c = l; c < K_all; c += G) {
-                const float e = expf(zt[c] - mt);
-                set += e;
-                if (c == 0 || c >= K_old) sebg += e;
+                set += expf(zt[c] - mt);
+                if (c == 0 || c >= K_old) sebg += expf(zt[c] - mref);
             }
             for (int c = l; c < K_old; c += G) ses += expf(zs[c] - ms);
             set = gsum(set); sebg = gsum(sebg); ses = gsum(ses);
             const float den = logf(set) + mt;
-            const float out_bg = (logf(sebg) + mt) - den;                       // :196
+            const float out_bg = (logf(sebg) + mref) - den;                     // :196
             const float lab0 = expf(zs[0] - ms) / ses;
             float acc = l == 0 ? lab0 * out_bg : 0.f;
             for (int c = l; c < K_old; c += G)
@@ -273,9 +283,8 @@ __global__ __launch_bounds__(256) void roi_distill_kernel(const float* __restric
                 float* g = d_zt + (size_t)i * ld_dzt;
                 const float s = -gscale * inv_n / (float)K_old;
                 for (int c = l; c < K_all; c += G) {
-                    const float e = expf(zt[c] - mt);
-                    float v = -e / set;
-                    if (c == 0 || c >= K_old) v += lab0 * e / sebg;
+                    float v = -expf(zt[c] - mt) / set;
+                    if (c == 0 || c >= K_old) v += lab0 * expf(zt[c] - mref) / sebg;
                     if (c >= 1 && c < K_old) v += expf(zs[c] - ms) / ses;
                     g[c] = v * s;
                 }

@@ -203,10 +203,6 @@ extern "C" int abr_prof_event_overhead_ms(double* out_host, void* stream) {
 }
 
 namespace abr {
-bool x6_guard_enabled() {
-    static const bool on = !(getenv("ABR_X6_GUARD") && atoi(getenv("ABR_X6_GUARD")) == 0);
-    return on;
-}
 unsigned* x6_flags_ptr() {
     static unsigned* p = nullptr;
     if (!p) {

@@ -1086,7 +1086,7 @@ static int64_t x6_packed_bytes(int64_t rows, int64_t K) { return (rows + 31) / 3
 
 static int x6_pack(const float* w, int64_t rows, int K, void* planes, hipStream_t st) {
     dim3 grid((unsigned)((K + 63) / 64), (unsigned)((rows + 31) / 32));
-    x6_pack_kernel<<<grid, 256, 0, st>>>(w, (int)rows, K, reinterpret_cast<uint4*>(planes), abr::x6_guard_enabled() ? abr::x6_flags_ptr() : nullptr);
+    x6_pack_kernel<<<grid, 256, 0, st>>>(w, (int)rows, K, reinterpret_cast<uint4*>(planes), abr::x6_flags_ptr());
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
@@ -1178,7 +1178,7 @@ __global__ __launch_bounds__(256) void h3_pack_multi_kernel(const abr::PrepJob* 
 }
 static int h3_pack(const float* w, int64_t rows, int K, void* planes, hipStream_t st) {
     const unsigned rb = (unsigned)((rows + 31) / 32);
-    h3_rowscale_kernel<<<rb * 8u, 256, 0, st>>>(w, (int)rows, K, reinterpret_cast<uint4*>(planes), abr::x6_guard_enabled() ? abr::x6_flags_ptr() : nullptr);
+    h3_rowscale_kernel<<<rb * 8u, 256, 0, st>>>(w, (int)rows, K, reinterpret_cast<uint4*>(planes), abr::x6_flags_ptr());
     h3_pack_kernel<<<dim3((unsigned)((K + 63) / 64), rb), 256, 0, st>>>(w, (int)rows, K, reinterpret_cast<uint4*>(planes));
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -1211,7 +1211,7 @@ int launch_x6w_np(const ConvP& p, const float* x, float* out, hipStream_t st) {
         else if (col_bytes * q.tiles_n > 3.0 * 1048576.0) g = col_bytes <= 1.6 * 1048576.0 ? 4 : (col_bytes <= 3.2 * 1048576.0 ? 2 : 0);   // (measured: tools/dbg/ngroup_time.py)
         q.ngroup = (g > 0 && g < q.tiles_n) ? g : 0;
     }
-    q.x6_flags = ((NP != 1 || F16) && abr::x6_guard_enabled()) ? abr::x6_flags_ptr() : nullptr;   // (rounding to bf16 is defined for every finite value: no guard)
+    q.x6_flags = (NP != 1 || F16) ? abr::x6_flags_ptr() : nullptr;   // (rounding to bf16 is defined for every finite value: no guard)
     q.h3_stats = (NP == 3 && q.x6_flags) ? abr::h3_stats_ptr() : nullptr;
     if (q.h3_stats) abr::h3_stats_inspected((double)q.tiles_m * BM * (double)p.K * q.nbatch);   // (the first n-tile column's workgroups inspect their A rows)
     constexpr size_t lds_op = sizeof(__bf16) * (NP == 1 ? 1 : (NP == 3 ? 2 : 3)) * BM * LDX;
@@ -1495,10 +1495,8 @@ static void dispatch_igemm(const ConvP& p, const float* x, const float* w, float
     // 128x128 tile, single- vs double-buffered operand LDS: one buffer (36.9 KB) lets a third workgroup share the CU, which pays
     // when prologue/epilogue are a large part of a tile's life (K <= 512: +2..5 %) or when the grid fits 3 but not 2 workgroups
     // per CU (the 600-tile RPN GEMM); longer-K GEMMs are faster double-buffered (one barrier per k-tile, fetch two tiles ahead).
-    static const int sb_mode = getenv("ABR_IGEMM_SB") ? atoi(getenv("ABR_IGEMM_SB")) : -1;
     const int64_t wgs128 = take_split128 ? best_nfull + (t128 - best_nfull) * best_s : t128;
-    static const int sb_maxk = getenv("ABR_IGEMM_SB_MAXK") ? atoi(getenv("ABR_IGEMM_SB_MAXK")) : 512;
-    const bool sb = sb_mode >= 0 ? sb_mode != 0 : (p.K <= sb_maxk || (wgs128 > 2 * cus && wgs128 <= 3 * cus) || take_split128);
+    const bool sb = p.K <= 512 || (wgs128 > 2 * cus && wgs128 <= 3 * cus) || take_split128;
     // Small grid + long K (the predictor FCs: 2304 x 108 x 2048 is 72 tiles of 64 x 64 walking 64 k-tiles each, 256 x 80 x 2048 is 8): EVERY tile
     // split along K over enough workgroups to cover the chip about twice, >= 4 k-tiles per unit; the partial sums meet in the last arrival in
     // index order (deterministic).  Narrow outputs only (Cout <= 128): wider small-grid GEMMs keep the sequential-K kernel, whose error is the
@@ -1533,29 +1531,18 @@ static void dispatch_igemm_x6(const ConvP& p, const float* x, const float* /*w*/
     const int64_t nb = p.nbatch > 1 ? p.nbatch : 1;
     const int64_t t128 = (int64_t)((p.M + 127) / 128) * ((p.Cout + 127) / 128) * nb;
     const int64_t t12864 = (int64_t)((p.M + 127) / 128) * ((p.Cout + 63) / 64) * nb;
-    static const int force = getenv("ABR_X6_TILE") ? atoi(getenv("ABR_X6_TILE")) : 0;   // experiments: 1 = 128x128, 2 = 128x64, 3 = 64x64
-    static const int force_maxk = getenv("ABR_X6_TILE_MAXK") ? atoi(getenv("ABR_X6_TILE_MAXK")) : 1 << 30;
     // Short-K convs (K <= 256: the 1x1 convs of layer1-3 and their dgrads) take 64x64 tiles whatever the grid size: alone they are
     // as fast as with 128x128 tiles (+-8 % per shape), but in the training step, where two or three other streams' kernels share the CUs,
-    // the small workgroups (four per CU, 31 KB of LDS) interleave better -- step -0.3 ms in a same-session A/B.  ABR_X6_SHORTK_MAXK=0: off.
-    static const int shortk = getenv("ABR_X6_SHORTK_MAXK") ? atoi(getenv("ABR_X6_SHORTK_MAXK")) : 256;
-    // grid-size rules: the biggest tile whose grid still gives every CU t*_min10 / 10 workgroups (experiments: ABR_X6_T128_MIN10, ABR_X6_T12864_MIN10)
-    static const int t128_min10 = getenv("ABR_X6_T128_MIN10") ? atoi(getenv("ABR_X6_T128_MIN10")) : 20;
-    static const int t12864_min10 = getenv("ABR_X6_T12864_MIN10") ? atoi(getenv("ABR_X6_T12864_MIN10")) : 20;
-    int tile;   // 1 = 128x128, 2 = 128x64, 3 = 64x64
-    if (force && p.K <= force_maxk && nb == 1) tile = force;
-    else if (shortk > 0 && p.K <= shortk && nb == 1 && p.nprod != 3) tile = 3;   // (f16x3: the grid-size rule alone is 0.1 ms per step better -- same-session A/B, two rounds: 18.23 vs 18.34)
-    else if (p.Cout > 64 && t128 * 10 >= (int64_t)t128_min10 * cus) tile = 1;
-    else if (t12864 * 10 >= (int64_t)t12864_min10 * cus || p.Cout <= 64) tile = 2;
-    else tile = 3;
-    {
-        // Wave layouts chosen so that every weight fragment (global -> registers) is fetched by as few waves as possible: the 128x128 tile as four
-        // waves of 128 x 32 (2x2 waves of 64 x 64 fetched each fragment twice; the A fragments, LDS reads, double instead: +1.3 % alone, -0.19 ms
-        // per step), the 128x64 tile as 2x2 waves of 64 x 32 (4x1 waves of 32 x 64 fetched each four times: +4.7 % alone, -0.12 ms per step)
-        if (tile == 1) launch_x6w<128, 128, 1, 4>(p, x, out, st);
-        else if (tile == 2) launch_x6w<128, 64, 2, 2>(p, x, out, st);
-        else launch_x6w<64, 64, 2, 2>(p, x, out, st);
-    }
+    // the small workgroups (four per CU, 31 KB of LDS) interleave better -- step -0.3 ms in a same-session A/B.  f16x3 takes the grid-size
+    // rules alone: 0.1 ms per step better (same-session A/B, two rounds: 18.23 vs 18.34).
+    // Grid-size rules: the biggest tile whose grid still gives every CU two workgroups.
+    // Wave layouts chosen so that every weight fragment (global -> registers) is fetched by as few waves as possible: the 128x128 tile as four
+    // waves of 128 x 32 (2x2 waves of 64 x 64 fetched each fragment twice; the A fragments, LDS reads, double instead: +1.3 % alone, -0.19 ms
+    // per step), the 128x64 tile as 2x2 waves of 64 x 32 (4x1 waves of 32 x 64 fetched each four times: +4.7 % alone, -0.12 ms per step)
+    if (p.K <= 256 && nb == 1 && p.nprod != 3) launch_x6w<64, 64, 2, 2>(p, x, out, st);
+    else if (p.Cout > 64 && t128 >= 2 * cus) launch_x6w<128, 128, 1, 4>(p, x, out, st);
+    else if (t12864 >= 2 * cus || p.Cout <= 64) launch_x6w<128, 64, 2, 2>(p, x, out, st);
+    else launch_x6w<64, 64, 2, 2>(p, x, out, st);
 }
 
 namespace abr {
@@ -1766,7 +1753,7 @@ static void convp_from_desc(const abr_conv_desc* d, ConvP& p) {
     p.d_howo.init((unsigned)(p.Ho * p.Wo)); p.d_wo.init((unsigned)p.Wo); p.d_cin.init((unsigned)p.Cin); p.d_s.init((unsigned)p.S);
     p.math = d->math;
     p.nprod = 6;
-    p.x6_flags = abr::x6_guard_enabled() ? abr::x6_flags_ptr() : nullptr;
+    p.x6_flags = abr::x6_flags_ptr();
     p.prof_ts = nullptr;
 }
 
@@ -1832,13 +1819,13 @@ int prep_transpose_multi(const PrepJob* jobs_dev, int njobs, int blocks, hipStre
 }
 int prep_pack_h3_multi(const PrepJob* jobs_dev, int njobs, int blocks, int scale_blocks, hipStream_t st) {
     if (njobs <= 0 || blocks <= 0) return 0;
-    h3_rowscale_multi_kernel<<<(unsigned)scale_blocks, 256, 0, st>>>(jobs_dev, njobs, abr::x6_guard_enabled() ? abr::x6_flags_ptr() : nullptr);
+    h3_rowscale_multi_kernel<<<(unsigned)scale_blocks, 256, 0, st>>>(jobs_dev, njobs, abr::x6_flags_ptr());
     h3_pack_multi_kernel<<<(unsigned)blocks, 256, 0, st>>>(jobs_dev, njobs);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 int prep_pack_multi(const PrepJob* jobs_dev, int njobs, int blocks, hipStream_t st) {
     if (njobs <= 0 || blocks <= 0) return 0;
-    x6_pack_multi_kernel<<<(unsigned)blocks, 256, 0, st>>>(jobs_dev, njobs, abr::x6_guard_enabled() ? abr::x6_flags_ptr() : nullptr);
+    x6_pack_multi_kernel<<<(unsigned)blocks, 256, 0, st>>>(jobs_dev, njobs, abr::x6_flags_ptr());
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 }  // namespace abr
@@ -1994,7 +1981,7 @@ extern "C" int abr_conv_prepare_batch(const abr_prep_item* items, int n, void* s
         bad |= abr::prep_pack_multi(d + tj.size() + uj.size(), (int)pj.size(), pb, st);
         bad |= abr::prep_pack_h3_multi(d + tj.size() + uj.size() + pj.size(), (int)hj.size(), hb, hsb, st);
         bad |= abr::prep_wino_h3_direct_multi(d + tj.size() + uj.size() + pj.size() + hj.size(), (int)wj.size(), wb, wsb,
-                                              abr::x6_guard_enabled() ? abr::x6_flags_ptr() : nullptr, st);
+                                              abr::x6_flags_ptr(), st);
         ABR_REQUIRE(!bad, "conv_prepare_batch: launch failed");
         abr::derived_commit(tokens.data(), (int)tokens.size(), st);
         token_guard.committed = true;

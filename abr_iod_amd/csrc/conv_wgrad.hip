@@ -10,8 +10,8 @@
 // Shape of the problem on this path: the OUTPUT is small (<= 1024 x 9216) and the REDUCTION axis m is huge
 // (9.5k-37k pixels/RoI-cells), the opposite of forward.  So: a workgroup owns a 128(n) x 128(k) tile of dW
 // and a contiguous slice of m (split-M); partial tiles are parked in a scratch with plain coalesced stores and summed in
-// split order by wgrad_reduce_kernel (deterministic; ABR_WGRAD_REDUCE=0: fp32 atomics straight into the gradient buffer, the
-// round-1 scheme).  `dw +=` also folds in the accumulation over the two RoI passes of one step (the 512-RoI detection pass and
+// split order by wgrad_reduce_kernel (deterministic; fp32 atomics straight into the gradient buffer only when the scratch cannot
+// be allocated).  `dw +=` also folds in the accumulation over the two RoI passes of one step (the 512-RoI detection pass and
 // the 64-RoI distillation pass share the head weights).
 // Both operands arrive m-major (gy rows, NHWC pixels), i.e. the MFMA's reduction index is the SLOW axis in memory.
 // fp32 kernel: rows are staged as-is into LDS ([m][128], 512 B coalesced per row) and a lane picks its operand with one
@@ -66,7 +66,6 @@ struct WgP {
     long x_bs, gy_bs, dw_bs;
     int math;                    // ABR_MATH_* (abr::ConvRoute::wgrad_math)
     unsigned* x6_flags;          // bf16x6: device word of the range guard (abr::x6_flags_ptr)
-    int tile_fast;               // workgroup order: output tile fastest (1, default) or row slice fastest (0)
     // split-M partial sums (splits > 1): parked in `ws` (one 64 KB unit per workgroup, plain coalesced stores) and summed in split order by
     // wgrad_reduce_kernel right behind this launch -- deterministic, and one write per output element instead of `splits` fp32 atomics
     // (256 workgroups x 16 K atomics = 4 M per launch cost ~30 us whatever the shape).  nullptr: atomics into dw
@@ -78,11 +77,6 @@ struct WgP {
     const unsigned long long* x_amax;
     unsigned gy_epoch, x_epoch;
     unsigned long long* h3_stats;   // f16x3 range statistics (abr::h3_stats_ptr) or nullptr
-    // round 5: with tickets the partial tiles are summed by the LAST workgroup of each output tile to arrive (in split order, its own partial
-    // included: the same sum whoever is last) instead of by a wgrad_reduce_kernel launch behind every split launch (41 launches per step).
-    // One counter per output tile, zero on entry, left zero.  nullptr: the reduction kernel follows.
-    unsigned* tickets;
-    unsigned ws_bytes;              // extent of `ws` for the coherent buffer accesses
 };
 
 // f16x3: the factors s_gy, s_x the accumulators carry (1, 1 in every other arithmetic); applied one after the other: their PRODUCT could leave
@@ -120,7 +114,7 @@ __device__ __forceinline__ void wgrad_store_tile(const WgP& p, const float (&v)[
 
 __device__ __forceinline__ void wgrad_finish(const WgP& p, f32x16 (&acc)[2][2], int n0, int k0, int wm, int wn, int l31, int lh, int tid,
                                              int gtile, int split, float* __restrict__ dw) {
-    if (p.ws && !p.tickets) {   // park the partial sums; wgrad_reduce_kernel adds them up
+    if (p.ws) {   // park the partial sums; wgrad_reduce_kernel adds them up
         float4* dst = reinterpret_cast<float4*>(reinterpret_cast<char*>(p.ws) + ((size_t)gtile * p.splits + split) * kPartBytes) + tid;
 #pragma unroll
         for (int t = 0; t < 4; t++)
@@ -130,56 +124,6 @@ __device__ __forceinline__ void wgrad_finish(const WgP& p, f32x16 (&acc)[2][2], 
                 dst[(t * 4 + c) * 256] = make_float4(a[4 * c], a[4 * c + 1], a[4 * c + 2], a[4 * c + 3]);
             }
         return;   // (the caller stamps the end: wgrad_finish is the kernel's last statement)
-    }
-    if (p.ws) {
-        // park through system-coherent buffer stores (written through the XCD-local L2: no cache maintenance around the ticket, as in
-        // conv_igemm_kernel's split-K), take the tile's ticket; the last arrival re-reads ALL partials in split order and finishes the tile
-        constexpr int kCoherent = 0x11;   // sc0 | sc1
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(p.ws, 0, p.ws_bytes, 0x00020000);
-        const unsigned my_off = (unsigned)(((size_t)gtile * p.splits + split) * kPartBytes) + (unsigned)tid * 16u;
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const f32x16& a = acc[t >> 1][t & 1];
-                const u32x4 v = {__float_as_uint(a[4 * c]), __float_as_uint(a[4 * c + 1]), __float_as_uint(a[4 * c + 2]), __float_as_uint(a[4 * c + 3])};
-                __builtin_amdgcn_raw_buffer_store_b128(v, rws, (int)(my_off + (unsigned)(t * 4 + c) * 4096u), 0, kCoherent);
-            }
-        // every write-through store of this wave has landed before the ticket is taken.  The explicit wait matters: a workgroup-scope release
-        // alone need not drain vmcnt (all waves of a workgroup share one L1), and with 16 short units per tile the last arrival then read partials
-        // still in flight (round 5: wrong sums in 7-65 % of a tiny model's outputs, run to run).  No cache maintenance: sc0|sc1 on both sides.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        __shared__ int s_last;
-        if (tid == 0) s_last = atomicAdd(p.tickets + gtile, 1u) == (unsigned)p.splits - 1u;
-        __syncthreads();
-        if (!s_last) return;
-        if (tid == 0) p.tickets[gtile] = 0u;
-        const float2 osc = wg_operand_scale(p);
-        const unsigned base = (unsigned)((size_t)gtile * p.splits * kPartBytes) + (unsigned)tid * 16u;
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-                int q = 0;
-                for (; q + 4 <= p.splits; q += 4) {   // four loads in flight; the additions stay in split order
-                    u32x4 v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; e++) v[e] = __builtin_amdgcn_raw_buffer_load_b128(rws, (int)(base + (unsigned)(q + e) * kPartBytes + (unsigned)(t * 4 + c) * 4096u), 0, kCoherent);
-#pragma unroll
-                    for (int e = 0; e < 4; e++) { sum.x += __uint_as_float(v[e].x); sum.y += __uint_as_float(v[e].y); sum.z += __uint_as_float(v[e].z); sum.w += __uint_as_float(v[e].w); }
-                }
-                for (; q < p.splits; q++) {
-                    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rws, (int)(base + (unsigned)q * kPartBytes + (unsigned)(t * 4 + c) * 4096u), 0, kCoherent);
-                    sum.x += __uint_as_float(v.x); sum.y += __uint_as_float(v.y); sum.z += __uint_as_float(v.z); sum.w += __uint_as_float(v.w);
-                }
-                const float vv[4] = {sum.x, sum.y, sum.z, sum.w};
-                wgrad_store_tile(p, vv, t >> 1, t & 1, c, n0, k0, wm, wn, l31, lh, p.final_store != 0, dw, osc);
-            }
-        return;
     }
     const float2 osc = wg_operand_scale(p);
 #pragma unroll
@@ -225,7 +169,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgP p, float* _
     wgrad_store_tile(p, v, t >> 1, t & 1, c, n0, k0, wave >> 1, wave & 1, lane & 31, lane >> 5, p.final_store != 0, dw, wg_operand_scale(p));
 }
 
-// SB: single-buffered operand LDS (two barriers per stage, 32 KB instead of 64 KB -> a third resident workgroup per CU)
+// Single-buffered operand LDS (two barriers per stage, 32 KB instead of 64 KB -> a third resident workgroup per CU): every shape of the step
+// is as fast or faster with three resident workgroups per CU (RPN 3x3 101 -> 109 TF, layer2 3x3 50 -> 62 TF, layer4 +2..3 %) than the
+// double-buffered form, retired since.  SB is always true; it stays in the name so that kernel traces compare with the earlier profiles.
 template <bool SB>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgP p, const float* __restrict__ x_,
                                                           const float* __restrict__ gy_, float* __restrict__ dw_) {
@@ -233,20 +179,20 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgP p, const floa
     const float* gy = gy_;
     float* dw = dw_;
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    static_assert(SB, "single-buffered only");
     abr::prof_stamp_begin(p.prof_ts);
-    constexpr int NBUF = SB ? 1 : 2;
-    float* Gs = smem;                       // [NBUF][MR][TN_]
-    float* As = smem + NBUF * MR * TN_;     // [NBUF][MR][TK_]
+    float* Gs = smem;                       // [MR][TN_]
+    float* As = smem + MR * TN_;            // [MR][TK_]
 
     const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
     // workgroup -> (row slice, output tile): the output tile is the FAST index, so the workgroups one XCD runs side by side (a
     // contiguous bid range, abr::xcd_remap) cover ALL output tiles of a few row slices.  They stream the same rows of gy and x in
     // lockstep: every operand element is then fetched from HBM once per XCD and served to the other tiles from that XCD's L2,
     // instead of being re-fetched by each of the N/128 (resp. K/128) tiles that need it (slice-fast order: ~3x the HBM traffic on the
-    // 9576 x {1024 x 256} gradients, which made them bandwidth-bound).  ABR_WGRAD_TILE_FAST=0 restores the old order.
+    // 9576 x {1024 x 256} gradients, which made them bandwidth-bound).
     const int total_tiles = p.tiles_pb * (p.nbatch > 1 ? p.nbatch : 1);
-    const int split = p.tile_fast ? bid / total_tiles : bid % p.splits;
-    int tile = p.tile_fast ? bid % total_tiles : bid / p.splits;
+    const int split = bid / total_tiles;
+    int tile = bid % total_tiles;
     const int gtile = tile;
     if (p.nbatch > 1) {
         const int bt = tile / p.tiles_pb;
@@ -309,11 +255,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgP p, const floa
             }
         }
     };
-    auto store_tile = [&](int buf) {
+    auto store_tile = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            *reinterpret_cast<float4*>(Gs + (buf * MR + r8 + 8 * i) * TN_ + q * 4) = rg[i];
-            *reinterpret_cast<float4*>(As + (buf * MR + r8 + 8 * i) * TK_ + q * 4) = ra[i];
+            *reinterpret_cast<float4*>(Gs + (r8 + 8 * i) * TN_ + q * 4) = rg[i];
+            *reinterpret_cast<float4*>(As + (r8 + 8 * i) * TK_ + q * 4) = ra[i];
         }
     };
 
@@ -326,9 +272,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgP p, const floa
             for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
 
     const int l31 = lane & 31, lh = lane >> 5;
-    auto compute_tile = [&](int cur) {
-        const float* g = Gs + cur * MR * TN_ + wm * 64 + 2 * l31;
-        const float* a = As + cur * MR * TK_ + wn * 64 + 2 * l31;
+    auto compute_tile = [&]() {
+        const float* g = Gs + wm * 64 + 2 * l31;
+        const float* a = As + wn * 64 + 2 * l31;
 #pragma unroll
         for (int s = 0; s < MR / 2; s++) {
             const float2 fg = *reinterpret_cast<const float2*>(g + (2 * s + lh) * TN_);
@@ -341,37 +287,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgP p, const floa
     };
     if (mt0 < mt1) {
         load_tile(mt0);
-        store_tile(0);
+        store_tile();
         __syncthreads();
-        int mt = mt0;
-        if (SB) {
-            for (; mt + 1 < mt1; mt++) {  // steady state: one basic block; the last stage is peeled (nothing to fetch for it)
-                load_tile(mt + 1);
-                __builtin_amdgcn_sched_barrier(0);  // fetches stay ahead of the MFMA stream
-                compute_tile(0);
-                __syncthreads();
-                store_tile(0);
-                __syncthreads();
-            }
-            compute_tile(0);
-        } else {  // double-buffered: stage mt+2 is fetched right behind the ds_writes of stage mt+1 (see conv_igemm.hip)
-            if (mt + 1 < mt1) load_tile(mt + 1);
-            for (; mt + 2 < mt1; mt++) {
-                const int cur = (mt - mt0) & 1;
-                compute_tile(cur);
-                store_tile(cur ^ 1);
-                load_tile(mt + 2);
-                __syncthreads();
-            }
-            if (mt + 1 < mt1) {
-                const int cur = (mt - mt0) & 1;
-                compute_tile(cur);
-                store_tile(cur ^ 1);
-                __syncthreads();
-                mt++;
-            }
-            compute_tile((mt - mt0) & 1);
+        for (int mt = mt0; mt + 1 < mt1; mt++) {  // steady state: one basic block; the last stage is peeled (nothing to fetch for it)
+            load_tile(mt + 1);
+            __builtin_amdgcn_sched_barrier(0);  // fetches stay ahead of the MFMA stream
+            compute_tile();
+            __syncthreads();
+            store_tile();
+            __syncthreads();
         }
+        compute_tile();
     }
 
     // epilogue: tile (tm,tn) element (row i, col j) is dW[n0 + wm*64 + 2i + tm][k0 + wn*64 + 2j + tn]
@@ -426,10 +352,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     // contiguous bid range, abr::xcd_remap) cover ALL output tiles of a few row slices.  They stream the same rows of gy and x in
     // lockstep: every operand element is then fetched from HBM once per XCD and served to the other tiles from that XCD's L2,
     // instead of being re-fetched by each of the N/128 (resp. K/128) tiles that need it (slice-fast order: ~3x the HBM traffic on the
-    // 9576 x {1024 x 256} gradients, which made them bandwidth-bound).  ABR_WGRAD_TILE_FAST=0 restores the old order.
+    // 9576 x {1024 x 256} gradients, which made them bandwidth-bound).
     const int total_tiles = p.tiles_pb * (p.nbatch > 1 ? p.nbatch : 1);
-    const int split = p.tile_fast ? bid / total_tiles : bid % p.splits;
-    int tile = p.tile_fast ? bid % total_tiles : bid / p.splits;
+    const int split = bid / total_tiles;
+    int tile = bid % total_tiles;
     const int gtile = tile;
     if (p.nbatch > 1) {
         const int bt = tile / p.tiles_pb;
@@ -630,12 +556,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 
 }  // namespace
 
-// ABR_WGRAD_REDUCE=0: fp32 atomics into dw for the split-M partial sums (the round-1 scheme) instead of parked partials + reduction kernel
-static bool wgrad_ticket_enabled() {
-    static const bool on = !(getenv("ABR_WGRAD_REDUCE") && atoi(getenv("ABR_WGRAD_REDUCE")) == 0);
-    return on;
-}
-
 // scratch of the partial-sum reduction: `units` partial tiles of 64 KB, grow-only, one buffer per stream (launches on a stream are ordered)
 static float* wgrad_scratch(hipStream_t st, size_t units) {
     struct Ws { float* ws = nullptr; size_t units = 0; };
@@ -651,40 +571,15 @@ static float* wgrad_scratch(hipStream_t st, size_t units) {
     return w.ws;
 }
 
-// per-stream ticket counters of the in-kernel reduction (one per output tile; zeroed once, the kernels leave them zero)
-static unsigned* wgrad_tickets(hipStream_t st, int tiles) {
-    constexpr int kMaxTiles = 8192;
-    // OPT-IN (ABR_WGRAD_INKERNEL_REDUCE=1).  Measured in the step (same session, two rounds): 19.38 ms with it against 18.62 with the reduction
-    // kernel -- the write-through stores of the 64 KB partial tiles and the last arrival's 16 x splits coherent loads cost more than the 41
-    // short launches they replace, which run beside other streams' kernels anyway.  Results are identical either way.
-    static const bool on = getenv("ABR_WGRAD_INKERNEL_REDUCE") && atoi(getenv("ABR_WGRAD_INKERNEL_REDUCE")) != 0;
-    if (!on || tiles > kMaxTiles) return nullptr;
-    static std::map<hipStream_t, unsigned*> pool;
-    static std::mutex mu;
-    std::lock_guard<std::mutex> g(mu);
-    unsigned*& t = pool[st];
-    if (!t) {
-        if (hipMalloc(&t, kMaxTiles * sizeof(unsigned)) != hipSuccess) { t = nullptr; return nullptr; }
-        (void)hipMemset(t, 0, kMaxTiles * sizeof(unsigned));
-    }
-    return t;
-}
-
 // fills p.ws for a split launch (left null -> the kernel falls back to atomics; the caller must then have zeroed a final_store dw)
 static void wgrad_plan_reduction(WgP& p, int tiles, hipStream_t st) {
     p.ws = nullptr;
-    p.tickets = nullptr;
-    p.ws_bytes = 0;
     if (p.splits <= 1) { if (p.final_store) p.overwrite = 1; return; }
-    if (wgrad_ticket_enabled()) p.ws = wgrad_scratch(st, (size_t)tiles * p.splits);
-    if (p.ws && (size_t)tiles * p.splits * 65536 < (size_t)0x7FFFFFF0) {
-        p.tickets = wgrad_tickets(st, tiles);
-        p.ws_bytes = (unsigned)((size_t)tiles * p.splits * 65536);
-    }
+    p.ws = wgrad_scratch(st, (size_t)tiles * p.splits);
 }
 
 static void wgrad_reduce(const WgP& p, int tiles, float* dw, hipStream_t st) {
-    if (p.ws && !p.tickets) wgrad_reduce_kernel<<<(unsigned)tiles * 16u, 256, 0, st>>>(p, dw);
+    if (p.ws) wgrad_reduce_kernel<<<(unsigned)tiles * 16u, 256, 0, st>>>(p, dw);
 }
 
 // split choice + launch for one (possibly batched) weight-gradient GEMM described by p (tiles_n / tiles_k / M / K filled in)
@@ -699,12 +594,10 @@ static void launch_wgrad(WgP p, const float* x, const float* gy, float* dw, void
     // (workgroups / (ceil(workgroups / CUs) * CUs)), preferring fewer splits (less atomic traffic) on ties; every
     // workgroup keeps at least 8 stages (256 rows) of work.
     // Prefer two workgroups per CU when each still gets >= 64 stages: a lone workgroup cannot hide its own prologue / atomics
-    // epilogue (head 1x1 gradients: 113 -> 126..134 TF alone; -1.0 ms per training step).  ABR_WGRAD_OCC2=0 turns it off.
+    // epilogue (head 1x1 gradients: 113 -> 126..134 TF alone; -1.0 ms per training step).
     // Round 2 had this off (next to the heavier dgrad kernels of that round two concurrent 512-workgroup grids oversubscribed the CUs: +0.13 ms);
     // with the weights-direct dgrad kernels (35 KB of LDS, 3 waves / SIMD) it is worth -0.25 ms per step in four same-session A/B rounds and
-    // lifts the kernel's own rate 132 -> 148 TF-eq, so it is ON by default since round 3.
-    static const bool occ2 = !(getenv("ABR_WGRAD_OCC2") && atoi(getenv("ABR_WGRAD_OCC2")) == 0);
-    static const int occ2_min_stages = getenv("ABR_WGRAD_OCC2_MINSTAGES") ? atoi(getenv("ABR_WGRAD_OCC2_MINSTAGES")) : 64;
+    // lifts the kernel's own rate 132 -> 148 TF-eq, so it is ON since round 3.
     const int max_splits = std::max(1, (m_tiles + 7) / 8);
     int splits = 1;
     double best = -1.0;
@@ -714,7 +607,7 @@ static void launch_wgrad(WgP p, const float* x, const float* gy, float* dw, void
         const long rounds = (wgs + cus - 1) / cus;
         double eff = (double)wgs / (double)(rounds * cus);
         if (wgs < cus) eff *= 0.5;                 // not even one workgroup per CU
-        else if (occ2 && wgs < 2L * cus && m_tiles / (2 * sp) >= occ2_min_stages) eff *= 0.85;  // a lone workgroup per CU cannot hide its own prologue /
+        else if (wgs < 2L * cus && m_tiles / (2 * sp) >= 64) eff *= 0.85;  // a lone workgroup per CU cannot hide its own prologue /
                                                    // atomics epilogue: take two when each still gets >= 64 stages (head 1x1s: +11..15 %)
         eff -= 0.0002 * sp;                        // tie-break: fewer partial sums
         if (eff > best) { best = eff; splits = sp; }
@@ -726,17 +619,6 @@ static void launch_wgrad(WgP p, const float* x, const float* gy, float* dw, void
     if (p.final_store && splits > 1 && !p.ws) {   // no scratch: atomics into a zeroed dw after all
         (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)nb * p.Cout * p.K, abr::as_stream(stream));
         p.final_store = 0;
-    }
-    // single-buffered by default: every shape of the step is as fast or faster with three resident workgroups per CU (RPN 3x3
-    // 101 -> 109 TF, layer2 3x3 50 -> 62 TF, layer4 +2..3 %); ABR_WGRAD_SB=0 selects the double-buffered variant for comparison
-    static const int sb_mode = getenv("ABR_WGRAD_SB") ? atoi(getenv("ABR_WGRAD_SB")) : 1;
-    const bool sb = sb_mode != 0;
-    const size_t lds = sizeof(float) * (sb ? 1 : 2) * MR * (TN_ + TK_);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(sizeof(float) * 2 * MR * (TN_ + TK_)));
-        attr_set = true;
     }
     if (p.math == ABR_MATH_BF16X6 || p.math == ABR_MATH_BF16 || p.math == ABR_MATH_F16X3 || p.math == ABR_MATH_F16) {   // same split plan (MRX == MR), three-plane
         static bool attr6 = false;                                                                                     // (bf16 / f16: one-plane, f16x3: two-plane) LDS
@@ -750,7 +632,7 @@ static void launch_wgrad(WgP p, const float* x, const float* gy, float* dw, void
             attr6 = true;
         }
         p.map4 = 1;
-        p.x6_flags = (!one && abr::x6_guard_enabled()) ? abr::x6_flags_ptr() : nullptr;
+        p.x6_flags = !one ? abr::x6_flags_ptr() : nullptr;
         p.h3_stats = (h3 && p.x6_flags) ? abr::h3_stats_ptr() : nullptr;
         if (p.h3_stats) abr::h3_stats_inspected((double)nb * p.M * ((double)p.Cout + (double)p.K));   // gy by the first k-tile column, x by the first n-tile row
         // Timed with a HIP-event pair, not with in-kernel stamps: a kernel trace's duration of these kernels includes the write-back of the
@@ -771,8 +653,7 @@ static void launch_wgrad(WgP p, const float* x, const float* gy, float* dw, void
     }
     const int rec = abr::prof_start(abr::as_stream(stream), abr::PROF_WGRAD, 2.0 * (double)p.M * (double)p.Cout * (double)p.K * nb);
     p.prof_ts = abr::prof_clock_slot(rec);
-    if (sb) conv_wgrad_kernel<true><<<(unsigned)(tiles * splits), 256, lds, abr::as_stream(stream)>>>(p, x, gy, dw);
-    else conv_wgrad_kernel<false><<<(unsigned)(tiles * splits), 256, lds, abr::as_stream(stream)>>>(p, x, gy, dw);
+    conv_wgrad_kernel<true><<<(unsigned)(tiles * splits), 256, sizeof(float) * MR * (TN_ + TK_), abr::as_stream(stream)>>>(p, x, gy, dw);
     abr::prof_stop(abr::as_stream(stream), rec);
     wgrad_reduce(p, tiles, dw, abr::as_stream(stream));
 }
@@ -800,9 +681,6 @@ extern "C" int abr_conv_wgrad(const abr_conv_desc* d, const float* x, const floa
     p.ws = nullptr; p.final_store = 0; p.map4 = 0;
     p.x6_flags = nullptr;
     p.gy_amax = p.x_amax = nullptr; p.gy_epoch = p.x_epoch = 0; p.h3_stats = nullptr;
-    p.tickets = nullptr; p.ws_bytes = 0;
-    static const int tile_fast = !(getenv("ABR_WGRAD_TILE_FAST") && atoi(getenv("ABR_WGRAD_TILE_FAST")) == 0);
-    p.tile_fast = tile_fast;
     hipStream_t st = abr::as_stream(stream);
     ABR_REQUIRE(d->math == ABR_MATH_F32 || d->math == ABR_MATH_BF16 || d->math == ABR_MATH_BF16X6 || d->math == ABR_MATH_F16X3 || d->math == ABR_MATH_F16,
                 "conv_wgrad: unknown math mode");
@@ -840,19 +718,16 @@ extern "C" int abr_conv_wgrad(const abr_conv_desc* d, const float* x, const floa
             int bad = vin ? 0 : abr::wino_input_transform(x, d->B, d->H, d->W, d->Cin, V, st, h3 ? &v_ref : nullptr);
             bad |= abr::wino_outgrad_transform(gy, d->B, d->H, d->W, d->Cout, Mg, st, h3 ? &m_ref : nullptr);
             // enough output tiles to fill the chip without splitting the tile axis -> each workgroup owns its dU tile and writes
-            // it directly; otherwise split-M with atomics into a zeroed dU
+            // it directly; otherwise split-M, whose partial sums go through the reduction kernel, which STORES the tile: no zero-fill
+            // of dU (launch_wgrad zero-fills dU itself when it has to fall back to atomics)
             int32_t info[3];
             const int cus_ = abr_device_info(info) == ABR_OK ? info[0] : 256;
             const long out_tiles = 36L * ((d->Cout + TN_ - 1) / TN_) * ((d->Cin + TK_ - 1) / TK_);
             const int own = out_tiles >= 2L * cus_;
-            // split-M partial sums of dU go through the reduction kernel, which STORES the tile: no zero-fill of dU
-            // (launch_wgrad zero-fills dU itself when it has to fall back to atomics)
-            const bool ticket = wgrad_ticket_enabled();
-            if (!own && !ticket) bad |= hipMemsetAsync(dU, 0, nU * sizeof(float), st) != hipSuccess;
             if (!bad) {
                 WgP g = p;
                 g.overwrite = own;
-                g.final_store = (!own && ticket) ? 1 : 0;
+                g.final_store = !own;
                 g.B = (int)T; g.H = g.W = 1; g.R = g.S = 1; g.stride = 1; g.pad = 0; g.Ho = g.Wo = 1;
                 g.M = (int)T; g.K = d->Cin; g.plain = 1; g.scale = nullptr;
                 g.d_howo.init(1u); g.d_wo.init(1u);

@@ -571,9 +571,6 @@ namespace abr {
 // only taken when it still leaves >= 4 workgroups per CU: the small layers (layer3: 640 tiles x 256 channels) are bound by launch
 // latency / parallelism, not by access width, and run better with twice the threads
 static inline bool wide(int64_t tiles, int C) {
-    static const int force = getenv("ABR_WINO_VEC") ? atoi(getenv("ABR_WINO_VEC")) : 0;
-    if (force == 2) return false;
-    if (force == 4) return C % 4 == 0;
     return C % 4 == 0 && tiles * (C / 4) >= (int64_t)256 * 4 * 256;
 }
 
@@ -582,9 +579,7 @@ int wino_input_transform(const float* x, int B, int H, int W, int C, float* V, h
     unsigned long long* aw = amax ? amax->word : nullptr;
     const unsigned ae = amax ? amax->epoch : 0u;
     // (measured: the input transform is never faster with 16 B accesses -- 0.95 ms / step at V = 2 against 1.07 mixed and 1.13 at V = 4)
-    static const bool in4 = getenv("ABR_WINO_VEC") && atoi(getenv("ABR_WINO_VEC")) == 4;
-    if (in4 && C % 4 == 0) wino_input_kernel<4><<<grid_for((int64_t)B * th_n * tw_n * (C / 4), aw != nullptr), 256, 0, st>>>(x, B, H, W, C, th_n, tw_n, V, aw, ae);
-    else wino_input_kernel<2><<<grid_for((int64_t)B * th_n * tw_n * (C / 2), aw != nullptr), 256, 0, st>>>(x, B, H, W, C, th_n, tw_n, V, aw, ae);
+    wino_input_kernel<2><<<grid_for((int64_t)B * th_n * tw_n * (C / 2), aw != nullptr), 256, 0, st>>>(x, B, H, W, C, th_n, tw_n, V, aw, ae);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

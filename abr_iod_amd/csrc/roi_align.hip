@@ -472,10 +472,10 @@ __global__ __launch_bounds__(256) void roi_tile_lists_kernel(const RoiRect* __re
     if (threadIdx.x == 0) counts[lid] = base;
 }
 
-// NS > 1 (round 4): the workgroup is NS waves on the SAME 256 channels, wave s walking list entries s, s + NS, ... -- a tile's list (~100 RoIs at
+// NS waves (round 4) per workgroup on the SAME 64 x 16 B channels, wave s walking list entries s, s + NS, ... -- a tile's list (~100 RoIs at
 // 512 RoIs per image) is a chain of dependent L2 round trips per entry (weights, then gradient rows), and the kernel's time was the longest chain;
 // the partial sums meet in LDS and are added in wave order (fixed order: still deterministic).  blockDim.x = 64 NS.
-template <int PO, int NS = 1>  // PO = compile-time bound on PHo and PWo (4 for bin_step=2 on 7x7, 8 otherwise)
+template <int PO, int NS>  // PO = compile-time bound on PHo and PWo (4 for bin_step=2 on 7x7, 8 otherwise)
 __global__ __launch_bounds__(256) void roi_align_bwd_gather_kernel(const float* __restrict__ grad, int K, int C, int H, int W, int Wp,
                                                                     int PHo, int PWo, const float* __restrict__ Wy,
                                                                     const float* __restrict__ Wx, const RoiRect* __restrict__ rect,
@@ -503,8 +503,8 @@ __global__ __launch_bounds__(256) void roi_align_bwd_gather_kernel(const float* 
         y = blockIdx.y; b = blockIdx.z;
     }
     const int x0 = xt * kXT;
-    const int ws = NS > 1 ? (int)(threadIdx.x >> 6) : 0;                       // which share of the list this wave walks
-    const int cv = NS > 1 ? chunk * 64 + (int)(threadIdx.x & 63) : chunk * (int)blockDim.x + (int)threadIdx.x;
+    const int ws = (int)(threadIdx.x >> 6);          // which share of the list this wave walks
+    const int cv = chunk * 64 + (int)(threadIdx.x & 63);
     const bool c_ok = cv < C / 4;
     float4 acc[kXT];
 #pragma unroll
@@ -840,10 +840,9 @@ extern "C" int abr_roi_align_forward(const float* feat, const float* rois, int K
         const int PHo = (PH + bin_step - 1) / bin_step, PWo = (PW + bin_step - 1) / bin_step;
         const int nbins = PHo * PWo;
         int tx, bpb;
-        static const bool slice_on = !(getenv("ABR_ROIALIGN_CSLICES") && atoi(getenv("ABR_ROIALIGN_CSLICES")) == 0);
         if (C % 4 == 0) {
             // one channel slice per XCD when a slice still fills 32 lanes of 16 B (C >= 1024) and the map is too big for one L2
-            const int cslices = (slice_on && (C / 4) % 8 == 0 && C / 4 / 8 >= 32 && (int64_t)H * W * C * 4 > (2 << 20)) ? 8 : 1;
+            const int cslices = ((C / 4) % 8 == 0 && C / 4 / 8 >= 32 && (int64_t)H * W * C * 4 > (2 << 20)) ? 8 : 1;
             pick_shape(C / 4 / cslices, nbins, &tx, &bpb);
             const int bpr = (nbins + bpb - 1) / bpb;
             roi_align_fwd_nhwc<4><<<(unsigned)(K * bpr * cslices), 256, 0, st>>>(feat, rois, K, C, H, W, scale, PH, PW, sr,
@@ -885,7 +884,7 @@ extern "C" int abr_roi_align_backward(const float* grad, const float* rois, int 
         const int nbins = PHo * PWo;
         int tx, bpb;
         const size_t sep_lds = sizeof(float) * ((size_t)PHo * H + (size_t)PWo * W) + 16;
-        if (PHo <= kMaxPo && PWo <= kMaxPo && sep_lds <= 60 * 1024 && !getenv("ABR_ROIALIGN_BWD_DIRECT")) {
+        if (PHo <= kMaxPo && PWo <= kMaxPo && sep_lds <= 60 * 1024) {
             const int vec = (C % 4 == 0) ? 4 : 1;
             const int cvecs = C / vec;
             int t = 1;
@@ -979,38 +978,20 @@ extern "C" int abr_roi_align_backward_gather(const float* grad, const float* roi
     const int n_xt = (W + kXT - 1) / kXT;
     int32_t* counts = lists + (size_t)B * H * n_xt * K;
     roi_tile_lists_kernel<<<dim3((unsigned)n_xt, (unsigned)H, (unsigned)B), 256, 0, st>>>(rect, K, H, n_xt, lists, counts);
-    // one wave per workgroup (64 lanes x 16 B = 256 channels): four times the workgroups of a 256-thread block, so that the dependent
-    // chain of each (list entry -> weights -> gradient rows) has more neighbours to hide behind (ABR_ROIALIGN_BWD_TB=256: round 2's blocks)
-    static const int tb = getenv("ABR_ROIALIGN_BWD_TB") ? atoi(getenv("ABR_ROIALIGN_BWD_TB")) : 64;
-    // ABR_ROIALIGN_BWD_SPLIT (default 4; 1 = round 3's one wave per list): waves per workgroup sharing a tile's RoI list (see the kernel)
-    static const int ns = getenv("ABR_ROIALIGN_BWD_SPLIT") ? atoi(getenv("ABR_ROIALIGN_BWD_SPLIT")) : 4;
+    // four waves per workgroup share a tile's RoI list (see the kernel), each wave on the same 64 lanes x 16 B = 256 channels
+    const int cchunks = (C / 4 + 63) / 64;
     const int rec = abr::prof_start(st, abr::PROF_ROIALIGN_BWD, 0.0);
-    // ABR_ROIALIGN_BWD_XCD (default 1; 0 = rounds 2-5's 3-D grid): channel chunk and spatial range of a workgroup chosen by the XCD it runs on
-    static const int xcd_on = getenv("ABR_ROIALIGN_BWD_XCD") ? atoi(getenv("ABR_ROIALIGN_BWD_XCD")) : 1;
-    auto grid_of = [&](int cchunks, int* xcd_map) {
-        *xcd_map = xcd_on && (cchunks == 1 || cchunks == 2 || cchunks == 4 || cchunks == 8) ? 1 : 0;
-        if (!*xcd_map) return dim3((unsigned)(n_xt * cchunks), (unsigned)H, (unsigned)B);
+    // channel chunk and spatial range of a workgroup chosen by the XCD it runs on where the chunks divide the 8 XCDs; otherwise the 3-D grid
+    const int xm = cchunks == 1 || cchunks == 2 || cchunks == 4 || cchunks == 8 ? 1 : 0;
+    dim3 grid((unsigned)(n_xt * cchunks), (unsigned)H, (unsigned)B);
+    if (xm) {
         const int64_t P = 8 / cchunks, S = (int64_t)n_xt * H * B;
-        return dim3((unsigned)(8 * ((S + P - 1) / P)), 1u, 1u);
-    };
-    if (ns == 4) {
-        const int cchunks = (C / 4 + 63) / 64;
-        int xm = 0;
-        const dim3 grid = grid_of(cchunks, &xm);
-        if (PHo <= 4 && PWo <= 4)
-            roi_align_bwd_gather_kernel<4, 4><<<grid, 256, 0, st>>>(grad, K, C, H, W, Wp, PHo, PWo, Wy, Wx, rect, lists, counts, cchunks, accumulate, gfeat, n_xt, B, xm);
-        else
-            roi_align_bwd_gather_kernel<8, 4><<<grid, 256, 0, st>>>(grad, K, C, H, W, Wp, PHo, PWo, Wy, Wx, rect, lists, counts, cchunks, accumulate, gfeat, n_xt, B, xm);
-    } else {
-        const int TB = (tb == 64 || tb == 128 || tb == 256) ? tb : 64;
-        const int cchunks = (C / 4 + TB - 1) / TB;
-        int xm = 0;
-        const dim3 grid = grid_of(cchunks, &xm);
-        if (PHo <= 4 && PWo <= 4)
-            roi_align_bwd_gather_kernel<4><<<grid, TB, 0, st>>>(grad, K, C, H, W, Wp, PHo, PWo, Wy, Wx, rect, lists, counts, cchunks, accumulate, gfeat, n_xt, B, xm);
-        else
-            roi_align_bwd_gather_kernel<8><<<grid, TB, 0, st>>>(grad, K, C, H, W, Wp, PHo, PWo, Wy, Wx, rect, lists, counts, cchunks, accumulate, gfeat, n_xt, B, xm);
+        grid = dim3((unsigned)(8 * ((S + P - 1) / P)), 1u, 1u);
     }
+    if (PHo <= 4 && PWo <= 4)
+        roi_align_bwd_gather_kernel<4, 4><<<grid, 256, 0, st>>>(grad, K, C, H, W, Wp, PHo, PWo, Wy, Wx, rect, lists, counts, cchunks, accumulate, gfeat, n_xt, B, xm);
+    else
+        roi_align_bwd_gather_kernel<8, 4><<<grid, 256, 0, st>>>(grad, K, C, H, W, Wp, PHo, PWo, Wy, Wx, rect, lists, counts, cchunks, accumulate, gfeat, n_xt, B, xm);
     abr::prof_stop(st, rec);
     ABR_CHECK_LAUNCH("roi_align_backward_gather");
     return ABR_OK;

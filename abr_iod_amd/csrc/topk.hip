@@ -1,16 +1,13 @@
-// RPN proposal ranking: sigmoid + sorted top-k per image in ONE kernel.
+// RPN proposal ranking: sigmoid + sorted top-k per image.
 //
 // Reference: maskrcnn_benchmark/modeling/rpn/inference.py:87-96
 //     objectness = permute_and_flatten(objectness, N, A, 1, H, W).view(N, -1).sigmoid()
 //     objectness, topk_idx = objectness.topk(pre_nms_top_n, dim=1, sorted=True)
 // (ATen: permute copy, sigmoid, radix-select + segmented sort = ~8 kernels).  Here the objectness logits are read in place
 // from the fused NHWC head output (anchor j = row j/A, column j%A: already the flattened order):
-//   0. (chip-wide kernel) sigmoid keys once into a scratch + 12-bit histogram;   then one 1024-thread workgroup per image:
-//   1. radix select (12 + 12 + 8 bits, LDS histograms over the key scratch) of the k-th largest sigmoid value;
-//   2. the survivors (all values >= threshold, ties included) are packed as 64-bit (score bits << 32 | ~index) words into LDS;
-//   3. a bitonic sort of that LDS array (<= 16384 words = 128 KB of the CU's 160 KB) orders them by descending score,
-//      equal scores by ascending index;
-//   4. the first k are written out as fp32 scores + int64 indices.
+//   1. (chip-wide kernel) sigmoid keys once into a scratch + 12-bit histogram;
+//   2-5. partition, exact selection of the k-th key, chunk sorts and a merge by rank (below, before topk_partition_kernel);
+// the result orders by descending score, equal scores by ascending index, and the first k are written out as fp32 scores + int64 indices.
 // Scores are non-negative floats, so their bit patterns order like the values.
 #include <algorithm>
 #include <map>
@@ -84,81 +81,8 @@ __device__ __forceinline__ void find_bin_from_top(const int* h, int nbins, int* 
     }
 }
 
-// Phase 2, one 1024-thread workgroup per image: exact k-th largest key by two more histogram levels over the key scratch (12 + 12 + 8 bits; plain
-// coalesced dword reads, no expf), survivors packed into LDS, bitonic sort, emit.  Cleans the level-1 histogram for the next call.
-__global__ __launch_bounds__(TT) void topk_select_sort_kernel(const unsigned* __restrict__ keys_all, int* __restrict__ hist_all, int n, int k,
-                                                              float* __restrict__ scores, int64_t* __restrict__ idx) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* buf = reinterpret_cast<unsigned long long*>(smem);  // [CAP]
-    __shared__ int h[HB];
-    __shared__ int s_bin, s_krem, s_fill;
-    const unsigned* keys = keys_all + (size_t)blockIdx.x * n;
-    int* hist = hist_all + blockIdx.x * HB;
-    for (int i = threadIdx.x; i < HB; i += TT) { h[i] = hist[i]; hist[i] = 0; }
-    if (threadIdx.x == 0) { s_krem = k; s_fill = 0; s_bin = 0; }
-    __syncthreads();
-    unsigned thr = 0;
-    if (k < n) {
-        find_bin_from_top(h, HB, &s_bin, &s_krem);
-        __syncthreads();
-        const unsigned b1 = (unsigned)s_bin;
-        for (int i = threadIdx.x; i < HB; i += TT) h[i] = 0;
-        __syncthreads();
-        for (int j = threadIdx.x; j < n; j += TT) {
-            const unsigned key = keys[j];
-            if ((key >> 20) == b1) atomicAdd(&h[(key >> 8) & (HB - 1)], 1);
-        }
-        __syncthreads();
-        find_bin_from_top(h, HB, &s_bin, &s_krem);
-        __syncthreads();
-        const unsigned p24 = (b1 << 12) | (unsigned)s_bin;   // top 24 bits of the threshold
-        for (int i = threadIdx.x; i < 256; i += TT) h[i] = 0;
-        __syncthreads();
-        for (int j = threadIdx.x; j < n; j += TT) {
-            const unsigned key = keys[j];
-            if ((key >> 8) == p24) atomicAdd(&h[key & 255], 1);
-        }
-        __syncthreads();
-        find_bin_from_top(h, 256, &s_bin, &s_krem);
-        __syncthreads();
-        thr = (p24 << 8) | (unsigned)s_bin;
-    }
-    // pack every element with key >= thr (ties included; dropped only if the LDS capacity overflows)
-    for (int j = threadIdx.x; j < n; j += TT) {
-        const unsigned key = keys[j];
-        if (key >= thr) {
-            const int pos = atomicAdd(&s_fill, 1);
-            if (pos < CAP) buf[pos] = ((unsigned long long)key << 32) | (unsigned)(~(unsigned)j);
-        }
-    }
-    __syncthreads();
-    const int filled = min(s_fill, CAP);
-    int m = 1;
-    while (m < filled) m <<= 1;
-    for (int j = filled + threadIdx.x; j < m; j += TT) buf[j] = 0ull;  // padding sorts last
-    __syncthreads();
-    // bitonic sort, descending
-    for (int size = 2; size <= m; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < (m >> 1); t += TT) {
-                const int lo = 2 * t - (t & (stride - 1));  // index of the lower element of the pair
-                const int hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long a = buf[lo], b = buf[hi];
-                if ((a < b) == desc) { buf[lo] = b; buf[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    for (int j = threadIdx.x; j < k; j += TT) {
-        const unsigned long long v = j < filled ? buf[j] : 0ull;
-        if (scores) scores[(size_t)blockIdx.x * k + j] = __uint_as_float((unsigned)(v >> 32));
-        idx[(size_t)blockIdx.x * k + j] = (int64_t)(~(unsigned)(v & 0xFFFFFFFFu));
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------------
-// Round 4: phases 2-5 spread over the chip (the one-workgroup-per-image form below spent 130 of its 178 us in a 16384-word bitonic sort on ONE CU
+// Round 4: phases 2-5 spread over the chip (round 3's one-workgroup-per-image form spent 130 of its 178 us in a 16384-word bitonic sort on ONE CU
 // per image, and the step waits for ~60 % of this chain).
 //   2. partition (chip-wide, one workgroup per key slice): the level-1 bin b1 that holds the k-th key is read off the histogram by every workgroup;
 //      keys above the bin are survivors for certain, keys inside it are CANDIDATES; both are appended to per-image arrays as 64-bit
@@ -169,7 +93,7 @@ __global__ __launch_bounds__(TT) void topk_select_sort_kernel(const unsigned* __
 //   5. merge by rank (one workgroup per chunk): all sorted chunks of the image in LDS; an element's final position = its position in its own chunk
 //      + the number of larger elements in every other chunk (binary searches); words are unique (they carry the index), so positions are too;
 //      the first k positions are written out as fp32 scores + int64 indices.
-// Outputs are identical to the one-workgroup form's (descending score, equal scores by ascending index).
+// Outputs were identical to the one-workgroup form's (descending score, equal scores by ascending index).
 struct TopkCnt { int surv, cand, filled, pad; };
 constexpr int CH = 1024;      // words per sorted chunk
 constexpr int MAXCH = CAP / CH;
@@ -292,7 +216,7 @@ __global__ __launch_bounds__(TT) void topk_merge_emit_kernel(const unsigned long
     const int img = blockIdx.y, c = blockIdx.x;
     const int filled = cnt_all[img].filled;
     if (c * CH >= filled) {
-        // (filled < k cannot happen unless the capacity overflowed: then the tail reads as zeros, like the one-workgroup form)
+        // (filled < k cannot happen unless the capacity overflowed: then the tail reads as zeros)
         for (int j = max(filled, c * CH) + threadIdx.x; j < min(k, (c + 1) * CH); j += TT) {
             if (scores) scores[(size_t)img * k + j] = 0.f;
             idx[(size_t)img * k + j] = (int64_t)(~0u);
@@ -350,16 +274,14 @@ extern "C" int abr_sort_scores_desc(const float* scores, int n, int64_t* order, 
 }
 
 static int topk_run(const float* logits, int64_t img_stride, int N, int n, int A, int ld, int k, float* scores, int64_t* idx, int raw, void* stream) {
-    static const bool one_wg = getenv("ABR_TOPK_ONE_WG") && atoi(getenv("ABR_TOPK_ONE_WG")) != 0;   // round 3's one-workgroup-per-image phase 2 (A/B)
     const int G = 64;
     const int per = ((n + G - 1) / G + KT - 1) / KT * KT;
     const size_t lds_sort = (size_t)CAP * 8, lds_part = (size_t)per * 16;
     // the partition kernel keeps its slice's keys in LDS beside 16 KB of histogram: beyond 64 KB (n > ~196 k keys per image; the C4 geometries of
     // this path stay below 63 k) it cannot be launched -- say so instead of returning a launch error
-    ABR_REQUIRE(one_wg || lds_part + 16384 <= 65536, "topk_sigmoid: %d keys per image exceed the partition kernel's LDS (at most 196608; ABR_TOPK_ONE_WG=1 has no such limit)", n);
+    ABR_REQUIRE(lds_part + 16384 <= 65536, "topk_sigmoid: %d keys per image exceed the partition kernel's LDS (at most 196608)", n);
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(topk_merge_emit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort);
         attr = true;
     }
@@ -399,14 +321,10 @@ static int topk_run(const float* logits, int64_t img_stride, int N, int n, int A
     }
     const unsigned slices = (unsigned)((n + per - 1) / per);
     topk_keys_kernel<<<dim3(slices, (unsigned)N), KT, 0, st>>>(logits, img_stride, n, A, ld, per, keys, hist, raw);
-    if (one_wg) {
-        topk_select_sort_kernel<<<N, TT, lds_sort, st>>>(keys, hist, n, k, scores, idx);
-    } else {
-        topk_partition_kernel<<<dim3(slices, (unsigned)N), KT, lds_part, st>>>(keys, hist, n, k, per, surv, cand, cnt);
-        topk_select_kernel<<<N, TT, 0, st>>>(hist, n, k, surv, cand, cnt);
-        topk_chunk_sort_kernel<<<dim3(MAXCH, (unsigned)N), 256, 0, st>>>(surv, cnt);
-        topk_merge_emit_kernel<<<dim3(MAXCH, (unsigned)N), TT, lds_sort, st>>>(surv, cnt, k, scores, idx);
-    }
+    topk_partition_kernel<<<dim3(slices, (unsigned)N), KT, lds_part, st>>>(keys, hist, n, k, per, surv, cand, cnt);
+    topk_select_kernel<<<N, TT, 0, st>>>(hist, n, k, surv, cand, cnt);
+    topk_chunk_sort_kernel<<<dim3(MAXCH, (unsigned)N), 256, 0, st>>>(surv, cnt);
+    topk_merge_emit_kernel<<<dim3(MAXCH, (unsigned)N), TT, lds_sort, st>>>(surv, cnt, k, scores, idx);
     ABR_CHECK_LAUNCH("topk_sigmoid");
     return ABR_OK;
 }

@@ -206,11 +206,8 @@ def _arm_overlap(optimizer, head_inputs, features):
     """Gradient hooks that hand finished buckets of the flat gradient to the optimiser's GradReducer while backward is still running:
     layer4 + predictor once every RoI pass's pooled input has its gradient, the RPN once the C4 feature map has its own."""
     reducer = getattr(optimizer, "reducer", None)
-    final = getattr(optimizer, "bucket_final", None)    # FusedSGD: all-reduce of the bucket + (round 5) its early update
-    if reducer is None or final is None:
-        return
-    from ..solver.build import EARLY_SGD
-    if not (reducer.active or EARLY_SGD):
+    final = getattr(optimizer, "bucket_final", None)    # FusedSGD: all-reduce of the bucket
+    if reducer is None or final is None or not reducer.active:
         return
     heads = [t for t in head_inputs if torch.is_tensor(t) and t.requires_grad]
     left = [len(heads)]

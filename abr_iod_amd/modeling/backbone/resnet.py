@@ -338,21 +338,11 @@ class Bottleneck(nn.Module):
     def _dgrad(self, g, conv, scale, pad, **kw):
         return ops.conv_forward(g, conv.dgrad_weight(scale), 1, pad, math=self.math, w_version=conv.version(), **kw)
 
-    def prepare_derived(self):
-        """Rebuild, on the current stream, everything this block derives from its trainable weights: the flipped / BN-scaled dgrad
-        copies and, inside the library, what abr_conv_forward derives from the weight and from its dgrad copy (Winograd-domain weights of
-        the 3x3 conv, packed bf16x3 planes under bf16x6).  FusedSGD.step runs this on the weight-preparation stream right after the update."""
-        for conv, scale in self._conv_scales():
-            if not (conv.weight.requires_grad and conv.weight.is_cuda):
-                continue
-            wt = conv.dgrad_weight(scale)
-            ops.conv_prepare_weights(conv.weight, conv.stride, conv.padding, self.math, conv.version())
-            # the dgrad conv is stride 1 with pad k-1-p (a scatter for the stride-2 1x1 convs): same derived data either way
-            ops.conv_prepare_weights(wt, 1, conv.kernel_size - 1 - conv.padding, self.math, conv.version())
-
     def prep_entries(self):
-        """(conv, FrozenBN scale, stride, pad, math) of the trainable convs: FusedSGD prepares them all in one batched call instead of
-        prepare_derived()'s four launches per conv"""
+        """(conv, FrozenBN scale, stride, pad, math) of the trainable convs.  FusedSGD.step rebuilds, on the weight-preparation stream
+        right after the update and in one batched call, everything the block derives from them: the flipped / BN-scaled dgrad copies
+        and, inside the library, what abr_conv_forward derives from the weight and from its dgrad copy (Winograd-domain weights of the
+        3x3 conv, packed bf16x3 planes under bf16x6)"""
         return [(conv, scale, conv.stride, conv.padding, self.math) for conv, scale in self._conv_scales()
                 if conv.weight.requires_grad and conv.weight.is_cuda]
 
@@ -373,7 +363,7 @@ class Bottleneck(nn.Module):
         if self.dcn:
             return self._fwd_dcn(x, save, s)
         if (BLOCK_PLANS and ops.H3_TAGS and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
-                and (save or not (self.math == ops.MATH_BF16X6 and ops.FUSE_TAIL64 and self.conv2.weight.shape[0] == 64))):
+                and (save or not (self.math == ops.MATH_BF16X6 and self.conv2.weight.shape[0] == 64))):
             plans = self.__dict__.setdefault("_fwd_plans", {})
             keep_v = bool(save and ops.KEEP_WINO_V and self.conv2.weight.requires_grad)
             key = (x.shape, s, self.math, save, keep_v)

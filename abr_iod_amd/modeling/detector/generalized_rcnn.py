@@ -33,8 +33,6 @@ from .._flat import flatten_parameters
 # models to bf16x6 when a large share of the operands leaves its domain and to the fp32 MFMA kernels on inf / nan).  ABR_CONV_MATH=bf16x6 selects
 # rounds 2-4's default (exact three-term bf16 split, six products), ABR_CONV_MATH=f32 the fp32 MFMA kernels.
 DEFAULT_CONV_MATH = "f16x3"
-# source model's distillation proposals gathered from the selector's raw output by one kernel (GeneralizedRCNN._soften_fused)
-FUSED_SOFTEN = os.environ.get("ABR_FUSED_SOFTEN", "1") != "0"
 
 
 def _drop_derived_cache(base, nbytes):
@@ -221,7 +219,7 @@ class GeneralizedRCNN(nn.Module):
         pending = state["pending"]
         if isinstance(pending, dict):   # deferred: join the side stream, read the keep counts
             sel = self.rpn.box_selector_test
-            if FUSED_SOFTEN and pending["props"].is_cuda:
+            if pending["props"].is_cuda:   # the distillation proposals gathered from the selector's raw output by one kernel
                 return self._soften_fused(sel, pending, state, selected_indices)
             pending = sel.collect(pending)
         return self._soften_from_proposals(pending, state["features"], state["backbone_features"], state["anchors"],

@@ -16,7 +16,6 @@ MI355X-first differences (results identical):
   * IoU/Matcher/labels/encode are one kernel per image; both loss terms and their gradients are one kernel each.
 """
 import torch
-import os
 from torch import nn
 from torch.autograd import Function
 
@@ -52,7 +51,6 @@ def convert_to_roi_format(boxes):
     return torch.cat([ids, concat], dim=1)
 
 
-_DBG_SLEEP_ROI_TARGETS = int(os.environ.get("ABR_DBG_SLEEP_ROI_TARGETS", "0"))   # spin cycles in front of the RoI targets (probe only)
 
 
 class _JointPoolFn(Function):
@@ -155,9 +153,6 @@ class ResNet50Conv5ROIFeatureExtractor(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ predictor
-FUSE_POOL_RELU_BWD = os.environ.get("ABR_FUSE_POOL_RELU_BWD", "1") != "0"
-
-
 class _PredictorFn(Function):
     @staticmethod
     def forward(ctx, x, pred, *params):
@@ -169,7 +164,7 @@ class _PredictorFn(Function):
         ctx.need_dx = x.requires_grad
         # x is layer4's output, i.e. a ReLU's: its backward is fused into the pooling's (one pass over the [K,4,4,2048] tensor instead of
         # three), and the gradient handed to layer4 says so (_StageFn.backward skips its own mask; masking twice would be harmless)
-        ctx.relu_of = xh if (FUSE_POOL_RELU_BWD and x.requires_grad and getattr(x, "_abr_relu_output", False) and xh.is_contiguous()) else None
+        ctx.relu_of = xh if (x.requires_grad and getattr(x, "_abr_relu_output", False) and xh.is_contiguous()) else None
         return y
 
     @staticmethod
@@ -257,7 +252,7 @@ class FastRCNNPredictor(nn.Module):
             self._set_fused(self._fw2d, view, self._gw2d, grad_view)
 
     def prepare_derived(self):
-        """see Bottleneck.prepare_derived"""
+        """the fused predictor's dgrad copy, rebuilt by FusedSGD.step on the weight-preparation stream right after the update"""
         if self.fused_weight.is_cuda and self.cls_score.weight.requires_grad:
             self.fused_dgrad_weight()
 
@@ -347,8 +342,6 @@ class FastRCNNLossComputation(object):
         BATCH_SIZE_PER_IMAGE rows; rows past the number actually drawn (only when an image has fewer candidates than that) are
         padding with label -1, which the loss kernels skip.  Returns the dict of device tensors; `self._proposals` are BoxList VIEWS of it."""
         props, scores, keep, n_keep, sizes = lazy.raw()
-        if _DBG_SLEEP_ROI_TARGETS:
-            torch.cuda._sleep(_DBG_SLEEP_ROI_TARGETS)        # (criticality probe: tools/dbg/critical_probe.sh)
         R = self.fg_bg_sampler.batch_size_per_image
         t = ops.roi_head_targets(props, scores, keep, n_keep, [g.bbox for g in targets], [g.get_field("labels") for g in targets],
                                  self.proposal_matcher.high_threshold, self.proposal_matcher.low_threshold, self.box_coder.weights, R,

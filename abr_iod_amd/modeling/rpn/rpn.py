@@ -55,11 +55,6 @@ def generate_anchors(stride=16, sizes=(32, 64, 128, 256, 512), aspect_ratios=(0.
 
 
 PROPOSALS_SIDE_STREAM = os.environ.get("ABR_PROPOSAL_STREAM", "1") != "0"
-# training: hand the box head the selector's RAW device output (LazyProposals) instead of per-image BoxLists cut on the host
-FUSED_ROI_TARGETS = os.environ.get("ABR_FUSED_ROI_TARGETS", "1") != "0"
-
-
-_DBG_SLEEP_PROPOSALS = int(os.environ.get("ABR_DBG_SLEEP_PROPOSALS", "0"))   # spin cycles in front of the training selection (probe only)
 
 
 class LazyProposals(object):
@@ -229,20 +224,8 @@ class RPNHead(nn.Module):
         return [("weight", [self.cls_logits.weight, self.bbox_pred.weight], self.n_out_pad - self.n_out),
                 ("bias", [self.cls_logits.bias, self.bbox_pred.bias], self.n_out_pad - self.n_out)]
 
-    def prepare_derived(self):
-        """see Bottleneck.prepare_derived"""
-        if not self.fused_weight.is_cuda:
-            return
-        if self.fused_weight_grad is not None and (self.cls_logits.weight.requires_grad or self.bbox_pred.weight.requires_grad):
-            self.fused_dgrad_weight()
-            ops.conv_prepare_weights(self.fused_weight, 1, 0, self.math, self.fused_version())
-        if self.conv.weight.requires_grad:
-            wt = self.conv.dgrad_weight()
-            ops.conv_prepare_weights(self.conv.weight, 1, 1, self.math, self.conv.version())
-            ops.conv_prepare_weights(wt, 1, 1, self.math, self.conv.version())
-
     def prep_entries(self):
-        """the 3x3 head conv goes with FusedSGD's batched preparation; prepare_rest() does the fused 1x1 heads"""
+        """the 3x3 head conv goes with FusedSGD's batched preparation (see Bottleneck.prep_entries); prepare_rest() does the fused 1x1 heads"""
         return [(self.conv, None, 1, 1, self.math)] if (self.conv.weight.requires_grad and self.conv.weight.is_cuda) else []
 
     def prepare_rest(self):
@@ -364,8 +347,6 @@ class RPNPostProcessor(nn.Module):
         side = ops.side_stream((fused.device.index, tag))
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            if _DBG_SLEEP_PROPOSALS and self.training:
-                torch.cuda._sleep(_DBG_SLEEP_PROPOSALS)      # (criticality probe: tools/dbg/critical_probe.sh)
             pending = self.launch(anchors, fused, num_anchors)
         fused.record_stream(side)
         pending["stream"] = side
@@ -555,7 +536,8 @@ class RPNModule(nn.Module):
 
     def forward_finish(self, state):
         with torch.no_grad():
-            if FUSED_ROI_TARGETS and state["pending"]["props"].is_cuda and state["targets"] is not None:
+            # training: hand the box head the selector's RAW device output (LazyProposals) instead of per-image BoxLists cut on the host
+            if state["pending"]["props"].is_cuda and state["targets"] is not None:
                 boxes = LazyProposals(self.box_selector_train, state["pending"], state["targets"])
             else:
                 boxes = self.box_selector_train.collect(state["pending"], state["targets"])

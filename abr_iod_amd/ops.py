@@ -509,12 +509,9 @@ def take_marks():
     return out
 
 
-FUSE_TAIL64 = os.environ.get("ABR_FUSE_TAIL64", "1") != "0"
-
-
 def bottleneck_tail64_applies(o1, w2, w3, math):
     """the fused tail takes the 64-wide bottleneck of the frozen layer1 in the bf16x6 arithmetic (abr_conv_tail64_forward)"""
-    return (FUSE_TAIL64 and math == MATH_BF16X6 and tuple(w2.shape) == (64, 3, 3, 64) and tuple(w3.shape) == (256, 1, 1, 64)
+    return (math == MATH_BF16X6 and tuple(w2.shape) == (64, 3, 3, 64) and tuple(w3.shape) == (256, 1, 1, 64)
             and o1.shape[-1] == 64 and o1.numel() * 4 * 4 < 0x7FFFFFF0)
 
 

@@ -38,8 +38,8 @@ timeout 300 python bench.py --task 10-5 --batch-per-gpu 2 --mosaic-squares --ste
 # gradients per configuration and arithmetic) -- with -q alone the printed worst values are lost
 ( timeout 1500 python -m pytest tests/test_gpu_e2e_full_golden.py tests/test_gpu_e2e.py tests/test_gpu_e2e_golden.py tests/test_gpu_configs4_whole.py -q -s -p no:cacheprovider 2>&1 \
     | grep -E "^\[|worst|max-rel|l2-rel|passed|failed|^GPU |^oracle|proposal|present|distance" | grep -v amdgpu.ids ) > $O/${R}_fullsize_parity.log
-( echo "# tools/topk_probe.py: proposal ranking alone (multi-workgroup phases, then ABR_TOPK_ONE_WG=1 = round 3's one workgroup per image)"
-  timeout 120 python tools/topk_probe.py 2>&1 | grep -v amdgpu; ABR_TOPK_ONE_WG=1 timeout 120 python tools/topk_probe.py 2>&1 | grep -v amdgpu ) > $O/${R}_topk_probe.txt
+( echo "# tools/topk_probe.py: proposal ranking alone"
+  timeout 120 python tools/topk_probe.py 2>&1 | grep -v amdgpu ) > $O/${R}_topk_probe.txt
 fi
 if [ "$PART" = all ] || [ "$PART" = 2 ]; then
 # rocprofv3 kernel trace of the bench command (+ the PMC HBM-traffic passes)

@@ -129,7 +129,6 @@ enum ProfId { PROF_IGEMM_128x128 = 0, PROF_IGEMM_128x64, PROF_IGEMM_64x64, PROF_
 struct AmaxRef;
 // `amax` (optional, here and below): the kernel also writes max |value it stored| into that amax word (f16x3 consumers read it)
 int wino_input_transform(const float* x, int B, int H, int W, int C, float* V, hipStream_t st, const AmaxRef* amax = nullptr);
-int wino_weight_transform(const float* w, int N, int C, float* U, hipStream_t st);
 int wino_output_transform(const float* M, int B, int H, int W, int N, const float* scale, const float* bias, int relu, const float* mask,
                           float* out, hipStream_t st, const AmaxRef* amax = nullptr);
 int wino_outgrad_transform(const float* gy, int B, int H, int W, int N, float* Mg, hipStream_t st, const AmaxRef* amax = nullptr);
@@ -164,33 +163,48 @@ struct ConvRoute {
 // d.B == 0 (weight preparation, which knows no activation shape): the 2 GB bound on the Winograd tile tensors is not checked
 ConvRoute conv_route(const abr_conv_desc& d);
 
-// One job of a batched weight preparation (a table of these lives in device memory; workgroup b belongs to the job with first_block <= b).
+// One job of a weight preparation: one tensor's share of a launch.  Workgroup b of a launch belongs to the job with first_block <= b (c <= b
+// for the row-scale launches of the f16x3 kinds).
 struct PrepJob {
     const float* src;     // transpose: w [Cout][RS][Cin]; wino: w [N][3][3][C]; pack: matrix [rows][K]
     const float* scale;   // transpose: FrozenBN scale per Cout, or nullptr
     void* dst;            // transpose: wt [Cin][RS][Cout]; wino: U [36][N][C]; pack: planes
-    int a, b, c;          // transpose: Cout, RS, Cin; wino: N, C, -; pack: rows, K, -
-    int gx, gy;           // the job's grid (x, y) as the single-job kernel would have it (z = blocks / (gx * gy))
+    int a, b, c;          // transpose: Cout, RS, Cin; wino: N, C, -; pack: rows, K, first workgroup in the row-scale launch (f16x3)
+    int gx, gy;           // the job's own grid (x, y) (z = its blocks / (gx * gy))
     int first_block;
 };
+// Where a preparation kernel (template argument Src) takes its job from: a PrepTable of jobs in device memory, searched by workgroup index on the
+// field F; or the launch's only PrepJob, passed by value in the kernel arguments (its first_block and c are 0).
+struct PrepTable { const PrepJob* jobs; int njobs; };
+template <int PrepJob::*F = &PrepJob::first_block>
+__device__ __forceinline__ PrepJob prep_job(const PrepTable& t, int block) {
+    int lo = 0, hi = t.njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t.jobs[mid].*F <= block) lo = mid; else hi = mid - 1;
+    }
+    return t.jobs[lo];
+}
+template <int PrepJob::*F = &PrepJob::first_block>
+__device__ __forceinline__ PrepJob prep_job(const PrepJob& j, int) { return j; }
+// The jobs of one launch on the host side: n == 1: `one`, sent by value; n > 1: the table at `dev`.  prep_each calls f(the kernels' source)
+// unless there are none.
+struct PrepJobs { int n = 0; PrepJob one{}; const PrepJob* dev = nullptr; };
+template <class F>
+void prep_each(const PrepJobs& s, F&& f) {
+    if (s.n == 1) f(s.one);
+    else if (s.n > 1) f(PrepTable{s.dev, s.n});
+}
+// bytes of the f16x3 planes of a [rows][K] matrix: where the row scales behind them start
+__device__ __forceinline__ size_t h3_planes_bytes_dev(int rows, int K) { return (size_t)((rows + 31) / 32 * 32) * (size_t)K * 4; }
 // tile edge of a transpose job: 64 (16 B accesses) when both channel counts are multiples of 4 and both tensors are 16 B aligned, else 32
 __host__ __device__ __forceinline__ int prep_transpose_tile(int Cout, int Cin, const void* w, const void* wt) {
     return (((Cout | Cin) & 3) == 0 && ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(wt)) & 15) == 0) ? 64 : 32;
 }
-int prep_transpose_multi(const PrepJob* jobs_dev, int njobs, int blocks, hipStream_t st);   // conv_igemm.hip
-int prep_pack_multi(const PrepJob* jobs_dev, int njobs, int blocks, hipStream_t st);        // conv_igemm.hip
-int prep_pack_h3_multi(const PrepJob* jobs_dev, int njobs, int blocks, int scale_blocks, hipStream_t st);     // conv_igemm.hip (f16x3 planes: one workgroup per 32-row block)
-int prep_wino_u_multi(const PrepJob* jobs_dev, int njobs, int blocks, hipStream_t st);      // conv_winograd.hip (C % 4 == 0 jobs only)
-// f16x3: w [N][3][3][C] -> packed planes + row scales of the Winograd-domain [36 N][C] matrix, U never written (N % 32 == 0, C % 64 == 0)
-int prep_wino_h3_direct_multi(const PrepJob* jobs_dev, int njobs, int pack_blocks, int scale_blocks, unsigned* flags, hipStream_t st);   // conv_winograd.hip
-__device__ __forceinline__ int prep_find_job(const PrepJob* jobs, int njobs, int block) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].first_block <= block) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+// The Winograd preparation launches (conv_winograd.hip; launch errors are left for the caller's hipGetLastError).  fp32 w [N][3][3][C] -> U [36][N][C]
+// (C % 4 == 0); f16x3: w -> packed planes + row scales of the Winograd-domain [36 N][C] matrix, U never written (N % 32 == 0, C % 64 == 0).
+void prep_wino_u(const PrepJobs& jobs, int blocks, hipStream_t st);
+void prep_wino_h3_direct(const PrepJobs& jobs, int pack_blocks, int scale_blocks, unsigned* flags, hipStream_t st);
 void derived_cache_clear();
 void derived_cache_drop_range(const void* base, size_t bytes);
 size_t derived_cache_bytes();

@@ -85,7 +85,7 @@ struct ConvP {
     long a_bs, w_bs, o_bs;
     int math;  // ABR_MATH_*
     float* v_out;  // Winograd path: keep the transformed input here (abr_conv_desc::wino_v)
-    const void* w_planes;  // bf16x6: the weights as fragment-packed bf16x3 planes (x6_pack_kernel), or NULL = split w in-kernel
+    const void* w_planes;  // bf16x6: the weights as fragment-packed bf16x3 planes (x6_pack_multi_kernel), or NULL = split w in-kernel
     unsigned wp_bytes;     // bytes of one packed matrix (ceil(Cout/32)*32 * K * 6)
     long wp_bs;            // batched mode: bytes between two packed matrices
     int wp_nblocks;        // 32-row blocks in one packed matrix
@@ -531,7 +531,7 @@ constexpr int LDX = BKX + 8;   // LDS row pitch in bf16 elements (80 B)
 // ------------------------------------------------------------------------------------------------------------------------
 // bf16x6 with the WEIGHT operand fed straight from global memory into the MFMA registers (conv_igemm_x6w_kernel).
 // The weights of a conv change once per optimiser step (never, for the frozen source model), so their exact bf16x3 split is
-// made once per version by x6_pack_kernel and stored in MFMA-FRAGMENT order:
+// made once per version by x6_pack_multi_kernel and stored in MFMA-FRAGMENT order:
 //     chunk(nb, ks, pl) = 64 lanes x 16 B; lane l holds row nb*32 + (l & 31), k = ks*16 + (l >> 5)*8 .. +8 of plane pl
 //     byte address     = (((nb * K/16 + ks) * 3 + pl) * 64 + l) * 16
 // A wave's B fragment is then ONE coalesced 1 KB buffer load into the registers the MFMA reads: no LDS store, no fragment read and
@@ -1045,11 +1045,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 }
 
 // fp32 matrix [rows][K] (K % 16 == 0) -> fragment-packed bf16x3 planes (layout above), rows padded with zeros to a multiple of 32.
-// One workgroup = one 32-row block x 64 k: the fp32 block comes in as whole 256 B row segments (coalesced), goes through LDS, and
-// leaves as 4 k-steps x 3 planes x 1 KB chunks.  Every weight element is range-checked here (abr_x6_range_flags), once per version.
-__global__ __launch_bounds__(256) void x6_pack_kernel(const float* __restrict__ w, int rows, int K, uint4* __restrict__ planes, unsigned* flags) {
+// One workgroup = one 32-row block x 64 k of one job (a = rows, b = K, gx = K / 64 workgroups per block): the fp32 block comes in as whole
+// 256 B row segments (coalesced), goes through LDS, and leaves as 4 k-steps x 3 planes x 1 KB chunks.  Every weight element is range-checked
+// here (abr_x6_range_flags), once per version.
+template <class Src>
+__global__ __launch_bounds__(256) void x6_pack_multi_kernel(Src jobs, unsigned* flags) {
     __shared__ float t[32][68];
-    const int nb = blockIdx.y, k0 = blockIdx.x * 64, tid = threadIdx.x;
+    const abr::PrepJob jb = abr::prep_job(jobs, blockIdx.x);
+    const float* __restrict__ w = jb.src;
+    uint4* __restrict__ planes = reinterpret_cast<uint4*>(jb.dst);
+    const int rows = jb.a, K = jb.b;
+    const int lb = blockIdx.x - jb.first_block;
+    const int nb = lb / jb.gx, k0 = (lb % jb.gx) * 64, tid = threadIdx.x;
     unsigned bmin = 0xFFFFFFFFu;
     float nonfin = 0.f;
 #pragma unroll
@@ -1084,12 +1091,6 @@ __global__ __launch_bounds__(256) void x6_pack_kernel(const float* __restrict__ 
 
 static int64_t x6_packed_bytes(int64_t rows, int64_t K) { return (rows + 31) / 32 * 32 * K * 6; }
 
-static int x6_pack(const float* w, int64_t rows, int K, void* planes, hipStream_t st) {
-    dim3 grid((unsigned)((K + 63) / 64), (unsigned)((rows + 31) / 32));
-    x6_pack_kernel<<<grid, 256, 0, st>>>(w, (int)rows, K, reinterpret_cast<uint4*>(planes), abr::x6_flags_ptr());
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------
 // f16x3 weight planes: fp32 matrix [rows][K] (K % 16 == 0) -> per-row scale s_n (the power of two with rowmax / s_n in [2^14, 2^15)), two
 // fragment-packed fp16 planes g0 = fp16(w / s_n), g1 = fp16(w / s_n - g0) in the order the MFMA consumes them -- chunk (nb, ks, pl) = 64 lanes x
@@ -1098,7 +1099,6 @@ static int x6_pack(const float* w, int64_t rows, int K, void* planes, hipStream_
 // pass over its K columns finds the row maxima, a second one (L2 hits) splits and stores.  A non-finite weight raises ABR_X6_FLAG_NONFINITE.
 // ------------------------------------------------------------------------------------------------------------------------
 static int64_t h3_planes_bytes(int64_t rows, int64_t K) { return (rows + 31) / 32 * 32 * K * 4; }
-__device__ __forceinline__ size_t h3_planes_bytes_dev(int rows, int K) { return (size_t)((rows + 31) / 32 * 32) * (size_t)K * 4; }
 static int64_t h3_packed_bytes(int64_t rows, int64_t K) { return h3_planes_bytes(rows, K) + (rows + 31) / 32 * 32 * 4; }
 
 // Two launches (round 5b: one workgroup per 32-row block walking all of K twice took 16-20 us per weight, 110 us for a model's table, on the
@@ -1145,42 +1145,20 @@ __device__ __forceinline__ void h3_pack_chunk(const float* __restrict__ w, int r
     planes[ch * 64 + lane] = make_uint4(h0[0], h0[1], h0[2], h0[3]);
     planes[(ch + 1) * 64 + lane] = make_uint4(h1[0], h1[1], h1[2], h1[3]);
 }
-__global__ __launch_bounds__(256) void h3_rowscale_kernel(const float* __restrict__ w, int rows, int K, uint4* __restrict__ planes, unsigned* flags) {
-    const int rows32 = (rows + 31) / 32 * 32;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row < rows32) h3_rowscale_row(w, rows, K, row, reinterpret_cast<float*>(reinterpret_cast<char*>(planes) + h3_planes_bytes_dev(rows, K)), flags);
-}
-__global__ __launch_bounds__(256) void h3_pack_kernel(const float* __restrict__ w, int rows, int K, uint4* __restrict__ planes) {
-    h3_pack_chunk(w, rows, K, blockIdx.y, blockIdx.x * 64, planes, reinterpret_cast<const float*>(reinterpret_cast<const char*>(planes) + h3_planes_bytes_dev(rows, K)));
-}
-// the same over a TABLE of matrices (abr_conv_prepare_batch): jobs[j].c = first workgroup of job j in the row-scale launch, .first_block in the pack launch
-__device__ __forceinline__ int prep_find_job_c(const abr::PrepJob* jobs, int njobs, int block) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].c <= block) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-__global__ __launch_bounds__(256) void h3_rowscale_multi_kernel(const abr::PrepJob* __restrict__ jobs, int njobs, unsigned* flags) {
-    const int j = prep_find_job_c(jobs, njobs, blockIdx.x);
-    const abr::PrepJob jb = jobs[j];
+// one job: a = rows, b = K, c = its first workgroup in the row-scale launch (4 rows per workgroup), first_block / gx = K / 64 in the pack launch
+template <class Src>
+__global__ __launch_bounds__(256) void h3_rowscale_multi_kernel(Src jobs, unsigned* flags) {
+    const abr::PrepJob jb = abr::prep_job<&abr::PrepJob::c>(jobs, blockIdx.x);
     const int rows32 = (jb.a + 31) / 32 * 32;
     const int row = (blockIdx.x - jb.c) * 4 + (threadIdx.x >> 6);
-    if (row < rows32) h3_rowscale_row(jb.src, jb.a, jb.b, row, reinterpret_cast<float*>(reinterpret_cast<char*>(jb.dst) + h3_planes_bytes_dev(jb.a, jb.b)), flags);
+    if (row < rows32) h3_rowscale_row(jb.src, jb.a, jb.b, row, reinterpret_cast<float*>(reinterpret_cast<char*>(jb.dst) + abr::h3_planes_bytes_dev(jb.a, jb.b)), flags);
 }
-__global__ __launch_bounds__(256) void h3_pack_multi_kernel(const abr::PrepJob* __restrict__ jobs, int njobs) {
-    const int j = abr::prep_find_job(jobs, njobs, blockIdx.x);
-    const abr::PrepJob jb = jobs[j];
+template <class Src>
+__global__ __launch_bounds__(256) void h3_pack_multi_kernel(Src jobs) {
+    const abr::PrepJob jb = abr::prep_job(jobs, blockIdx.x);
     const int lb = blockIdx.x - jb.first_block;
     uint4* planes = reinterpret_cast<uint4*>(jb.dst);
-    h3_pack_chunk(jb.src, jb.a, jb.b, lb / jb.gx, (lb % jb.gx) * 64, planes, reinterpret_cast<const float*>(reinterpret_cast<const char*>(planes) + h3_planes_bytes_dev(jb.a, jb.b)));
-}
-static int h3_pack(const float* w, int64_t rows, int K, void* planes, hipStream_t st) {
-    const unsigned rb = (unsigned)((rows + 31) / 32);
-    h3_rowscale_kernel<<<rb * 8u, 256, 0, st>>>(w, (int)rows, K, reinterpret_cast<uint4*>(planes), abr::x6_flags_ptr());
-    h3_pack_kernel<<<dim3((unsigned)((K + 63) / 64), rb), 256, 0, st>>>(w, (int)rows, K, reinterpret_cast<uint4*>(planes));
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    h3_pack_chunk(jb.src, jb.a, jb.b, lb / jb.gx, (lb % jb.gx) * 64, planes, reinterpret_cast<const float*>(reinterpret_cast<const char*>(planes) + abr::h3_planes_bytes_dev(jb.a, jb.b)));
 }
 
 static int num_cus() {
@@ -1292,37 +1270,14 @@ int launch(const ConvP& p, const float* x, const float* w, float* out, hipStream
     return 0;
 }
 
-// (Cout, R*S, Cin) -> (Cin, R*S flipped, Cout), scaled by scale[cout]; 32x32 LDS transpose per (rs) plane.
-__global__ __launch_bounds__(256) void dgrad_weights_kernel(const float* __restrict__ w, const float* __restrict__ scale,
-                                                             int Cout, int RS, int Cin, float* __restrict__ wt) {
-    __shared__ float t[32][33];
-    const int rs = blockIdx.z;
-    const int co0 = blockIdx.y * 32, ci0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    for (int i = ty; i < 32; i += 8) {
-        const int co = co0 + i, ci = ci0 + tx;
-        float v = 0.f;
-        if (co < Cout && ci < Cin) v = w[((size_t)co * RS + rs) * Cin + ci] * (scale ? scale[co] : 1.f);
-        t[i][tx] = v;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int ci = ci0 + i, co = co0 + tx;
-        if (ci < Cin && co < Cout) {
-            const size_t o = ((size_t)ci * RS + (RS - 1 - rs)) * Cout + co;
-            wt[o] = t[tx][i];
-        }
-    }
-}
-
-// dgrad_weights_kernel / x6_pack_kernel over a TABLE of tensors (abr_conv_prepare_batch): workgroup -> (job, the job's own block indices)
+// The dgrad copy: (Cout, R*S, Cin) -> (Cin, R*S flipped, Cout), scaled by scale[cout]; one LDS tile per workgroup and (rs) plane.
 // 64 x 64 tiles moved as 16 B per lane when both channel counts are multiples of 4 and both tensors 16 B aligned (every conv of the step but the
-// 76-wide RPN head: 260 MB per step at 2.8 TB/s with 32 x 32 tiles of 4 B accesses); abr::prep_transpose_tile is the rule, shared with the host
-// side that sizes the job's grid.
-__global__ __launch_bounds__(256) void dgrad_weights_multi_kernel(const abr::PrepJob* __restrict__ jobs, int njobs) {
+// 76-wide RPN head: 260 MB per step at 2.8 TB/s with 32 x 32 tiles of 4 B accesses), else 32 x 32; abr::prep_transpose_tile is the rule, shared
+// with the host side that sizes the job's grid.
+template <class Src>
+__global__ __launch_bounds__(256) void dgrad_weights_multi_kernel(Src jobs) {
     __shared__ float t[64][65];
-    const int j = abr::prep_find_job(jobs, njobs, blockIdx.x);
-    const abr::PrepJob jb = jobs[j];
+    const abr::PrepJob jb = abr::prep_job(jobs, blockIdx.x);
     const float* __restrict__ w = jb.src;
     const float* __restrict__ scale = jb.scale;
     float* __restrict__ wt = reinterpret_cast<float*>(jb.dst);
@@ -1366,47 +1321,6 @@ __global__ __launch_bounds__(256) void dgrad_weights_multi_kernel(const abr::Pre
         const int ci = ci0 + i, co = co0 + tx;
         if (ci < Cin && co < Cout) wt[((size_t)ci * RS + (RS - 1 - rs)) * Cout + co] = t[tx][i];
     }
-}
-
-__global__ __launch_bounds__(256) void x6_pack_multi_kernel(const abr::PrepJob* __restrict__ jobs, int njobs, unsigned* flags) {
-    __shared__ float t[32][68];
-    const int j = abr::prep_find_job(jobs, njobs, blockIdx.x);
-    const abr::PrepJob jb = jobs[j];
-    const float* __restrict__ w = jb.src;
-    uint4* __restrict__ planes = reinterpret_cast<uint4*>(jb.dst);
-    const int rows = jb.a, K = jb.b;
-    const int lb = blockIdx.x - jb.first_block;
-    const int nb = lb / jb.gx, k0 = (lb % jb.gx) * 64, tid = threadIdx.x;
-    unsigned bmin = 0xFFFFFFFFu;
-    float nonfin = 0.f;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const int r = (tid >> 4) + 16 * h, c = (tid & 15) * 4, row = nb * 32 + r;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < rows && k0 + c < K) v = *reinterpret_cast<const float4*>(w + (size_t)row * K + k0 + c);
-        *reinterpret_cast<float4*>(&t[r][c]) = v;
-        const unsigned b0 = (__float_as_uint(v.x) << 1) - 1u, b1 = (__float_as_uint(v.y) << 1) - 1u, b2 = (__float_as_uint(v.z) << 1) - 1u,
-                       b3 = (__float_as_uint(v.w) << 1) - 1u;
-        bmin = min(min(bmin, min(b0, b1)), min(b2, b3));
-        nonfin = fmaf(v.x, 0.f, nonfin); nonfin = fmaf(v.y, 0.f, nonfin); nonfin = fmaf(v.z, 0.f, nonfin); nonfin = fmaf(v.w, 0.f, nonfin);
-    }
-    if (flags) abr::x6_report(bmin, nonfin, flags);
-    __syncthreads();
-    const int ksl = tid >> 6, lane = tid & 63, ks = k0 / 16 + ksl;
-    if (ks * 16 >= K) return;
-    const float* src = &t[lane & 31][ksl * 16 + (lane >> 5) * 8];
-    __bf16 h[3][8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-        const float v = src[e];
-        const __bf16 h0 = (__bf16)v;
-        const float r1 = v - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        h[0][e] = h0; h[1][e] = h1; h[2][e] = (__bf16)(r1 - (float)h1);
-    }
-    const size_t c = ((size_t)nb * (K / 16) + ks) * 3;
-#pragma unroll
-    for (int pl = 0; pl < 3; pl++) planes[(c + pl) * 64 + lane] = *reinterpret_cast<const uint4*>(h[pl]);
 }
 
 // part / tickets (round 5): every (column chunk, row chunk) workgroup parks its 64 column sums; the LAST row chunk of a column chunk to arrive adds
@@ -1584,24 +1498,148 @@ ConvRoute conv_route(const abr_conv_desc& d) {
 
 static bool wino_split_kind(int kind) { return kind == abr::DERIVED_WINO_U_X6_PLANES || kind == abr::DERIVED_WINO_U_H3_PLANES; }
 
-// Writes the derived weights of route r for the tensor at w into buf on st (0 = ok).  The packed planes of U go through the fp32 U in `u`
-// (rows x K floats; nullptr = this stream's scratch, consumed by the pack launch right behind the transform).
-static int derive_weights(const abr::ConvRoute& r, const float* w, void* buf, float* u, hipStream_t st) {
-    if (r.kind == abr::DERIVED_WINO_U) return abr::wino_weight_transform(w, (int)(r.rows / 36), r.K, static_cast<float*>(buf), st);
-    const float* src = w;
-    if (wino_split_kind(r.kind)) {
-        if (!u) u = abr::wino_ws(st, (size_t)r.rows * r.K);
-        if (!u || abr::wino_weight_transform(w, (int)(r.rows / 36), r.K, u, st)) return 1;
-        src = u;
+// Job tables of the launches with several jobs: a RING of pinned host staging + device slots per stream.  A call takes the next njobs slots; a region is
+// reused only after the upload that last used it has completed -- thousands of jobs (tens of optimiser steps) later, so the host never waits for
+// the stream (a single staging buffer made every call wait for the previous call's upload, which sits behind the whole backward pass).
+namespace {
+constexpr size_t kPrepRing = 8192;
+struct PrepTables {
+    abr::PrepJob* host = nullptr;
+    abr::PrepJob* dev = nullptr;
+    size_t head = 0;                                   // next free slot
+    std::vector<std::pair<size_t, hipEvent_t>> inflight;   // (end slot of a past call's region, its upload event), oldest first
+    size_t inflight_begin = 0;                         // first slot still covered by `inflight`
+    float* u_scratch = nullptr;   // abr_conv_prepare_batch's fp32 Winograd-domain weights on their way to being packed
+    size_t u_floats = 0;
+};
+std::map<hipStream_t, PrepTables> g_prep_tables;
+std::mutex g_prep_mu;
+
+// slots [*first, *first + n) of the ring, free of any upload still in flight
+bool prep_ring_take(PrepTables& T, size_t n, size_t* first) {
+    if (n > kPrepRing) return false;
+    if (!T.host) {
+        if (hipHostMalloc(&T.host, kPrepRing * sizeof(abr::PrepJob)) != hipSuccess || hipMalloc(&T.dev, kPrepRing * sizeof(abr::PrepJob)) != hipSuccess) return false;
     }
-    const bool h3 = r.kind == abr::DERIVED_H3_PLANES || r.kind == abr::DERIVED_WINO_U_H3_PLANES;
-    return h3 ? h3_pack(src, r.rows, r.K, buf, st) : x6_pack(src, r.rows, r.K, buf, st);
+    if (T.head + n > kPrepRing) {   // wrap: everything recorded so far must be done before slot 0 is written again
+        for (auto& pr : T.inflight) { (void)hipEventSynchronize(pr.second); (void)hipEventDestroy(pr.second); }
+        T.inflight.clear();
+        T.head = 0;
+    }
+    *first = T.head;
+    T.head += n;
+    return true;
 }
+
+// ---- weight preparation ---------------------------------------------------------------------------------------------------------------
+// Every weight-derived tensor (dgrad copies, packed planes, Winograd-domain weights) is made by the preparation kernels (*_multi_kernel, here and
+// in conv_winograd.hip) from abr::PrepJob lists, one per kind.  A PrepPlan collects the jobs of one tensor or of many; prep_launch issues them.
+enum PrepKind { PREP_TRANSPOSE, PREP_WINO_U, PREP_X6, PREP_H3, PREP_WINO_H3, PREP_KINDS };   // (launch order)
+struct PrepPlan {
+    std::vector<abr::PrepJob> jobs[PREP_KINDS];
+    int blocks[PREP_KINDS] = {};         // workgroups of each kind's launch
+    int scale_blocks[PREP_KINDS] = {};   // ... and of the row-scale launch in front of it (PREP_H3, PREP_WINO_H3)
+    // fp32 U on its way to packed planes lives in the scratch prep_launch is given (u_floats floats): its U job writes, its pack job reads `off`
+    struct ViaU { size_t u_job, pack_job; int pack_kind; size_t off; };
+    std::vector<ViaU> via_u;
+    size_t u_floats = 0;
+
+    abr::PrepJob& add(int k, const float* src, void* dst, int a, int b, int gx, int gy, int nblocks) {
+        abr::PrepJob j{};
+        j.src = src; j.dst = dst; j.a = a; j.b = b; j.gx = gx; j.gy = gy; j.first_block = blocks[k];
+        blocks[k] += nblocks;
+        jobs[k].push_back(j);
+        return jobs[k].back();
+    }
+    // the dgrad copy wt [Cin][RS flipped][Cout] of w [Cout][RS][Cin], scaled by scale[cout] (nullptr: 1)
+    void transpose(const float* w, const float* scale, float* wt, int Cout, int RS, int Cin) {
+        const int tile = abr::prep_transpose_tile(Cout, Cin, w, wt);
+        const int gx = (Cin + tile - 1) / tile, gy = (Cout + tile - 1) / tile;
+        abr::PrepJob& j = add(PREP_TRANSPOSE, w, wt, Cout, RS, gx, gy, gx * gy * RS);
+        j.scale = scale; j.c = Cin;
+    }
+    // the packed planes of matrix m [rows][K]: f16x3 (h3) or bf16x3
+    void pack(bool h3, const float* m, int64_t rows, int K, void* dst) {
+        const int gx = (K + 63) / 64, gy = (int)((rows + 31) / 32);
+        abr::PrepJob& j = add(h3 ? PREP_H3 : PREP_X6, m, dst, (int)rows, K, gx, gy, gx * gy);
+        if (h3) { j.c = scale_blocks[PREP_H3]; scale_blocks[PREP_H3] += gy * 8; }
+    }
+    // what route r derives from w [Cout][R][S][Cin], into dst: the packed planes of w; for a Winograd conv U itself (fp32), else U's packed planes --
+    // f16x3 straight from w when Cin % 64 == 0, otherwise through U in the scratch
+    void derived(const abr::ConvRoute& r, const float* w, void* dst) {
+        if (r.kind == abr::DERIVED_NONE) return;
+        const bool h3 = r.kind == abr::DERIVED_H3_PLANES || r.kind == abr::DERIVED_WINO_U_H3_PLANES;
+        if (r.kind == abr::DERIVED_H3_PLANES || r.kind == abr::DERIVED_X6_PLANES) return pack(h3, w, r.rows, r.K, dst);
+        const int N = (int)(r.rows / 36), C = r.K;
+        if (h3 && C % 64 == 0) {   // conv_winograd.hip: wino_h3_scales / wino_h3_pack
+            abr::PrepJob& j = add(PREP_WINO_H3, w, dst, N, C, C / 64, N / 32, (C / 64) * (N / 32));
+            j.c = scale_blocks[PREP_WINO_H3];
+            scale_blocks[PREP_WINO_H3] += N / 4;
+            return;
+        }
+        const int gx = (int)(((int64_t)N * (C / 4) + 255) / 256);
+        const bool via = r.kind != abr::DERIVED_WINO_U;
+        add(PREP_WINO_U, w, via ? nullptr : dst, N, C, gx, 1, gx);
+        if (!via) return;
+        const int pk = h3 ? PREP_H3 : PREP_X6;
+        via_u.push_back({jobs[PREP_WINO_U].size() - 1, jobs[pk].size(), pk, u_floats});
+        pack(h3, nullptr, r.rows, r.K, dst);
+        u_floats += (size_t)r.rows * r.K;
+    }
+};
+
+// Issues plan p on st, kind by kind in launch order: a kind with one job passes it to its kernels by value, the kinds with several share one
+// upload into the ring T (needed then).  u: the scratch of p.u_floats floats.  nullptr = issued; else what failed.  Launch errors are left for
+// the caller's hipGetLastError.
+const char* prep_launch(PrepPlan& p, float* u, hipStream_t st, PrepTables* T = nullptr) {
+    if (p.u_floats && !u) return "no memory for the Winograd-domain scratch";
+    for (const PrepPlan::ViaU& v : p.via_u) {
+        p.jobs[PREP_WINO_U][v.u_job].dst = u + v.off;
+        p.jobs[v.pack_kind][v.pack_job].src = u + v.off;
+    }
+    abr::PrepJobs src[PREP_KINDS];
+    size_t njobs = 0;   // in the table
+    for (int k = 0; k < PREP_KINDS; k++) {
+        src[k].n = (int)p.jobs[k].size();
+        if (src[k].n == 1) src[k].one = p.jobs[k][0];
+        else njobs += p.jobs[k].size();
+    }
+    if (njobs) {
+        size_t first = 0;
+        if (!T || !prep_ring_take(*T, njobs, &first)) return "no memory for the job tables";
+        for (int k = 0, at = 0; k < PREP_KINDS; k++)
+            if (src[k].n > 1) {
+                std::copy(p.jobs[k].begin(), p.jobs[k].end(), T->host + first + at);
+                src[k].dev = T->dev + first + at;
+                at += src[k].n;
+            }
+        if (hipMemcpyAsync(T->dev + first, T->host + first, njobs * sizeof(abr::PrepJob), hipMemcpyHostToDevice, st) != hipSuccess) return "table upload failed";
+        hipEvent_t up = nullptr;
+        if (hipEventCreateWithFlags(&up, hipEventDisableTiming) == hipSuccess) {
+            (void)hipEventRecord(up, st);
+            T->inflight.emplace_back(first + njobs, up);
+        }
+    }
+    abr::prep_each(src[PREP_TRANSPOSE], [&](auto s) { dgrad_weights_multi_kernel<<<(unsigned)p.blocks[PREP_TRANSPOSE], 256, 0, st>>>(s); });
+    abr::prep_wino_u(src[PREP_WINO_U], p.blocks[PREP_WINO_U], st);
+    abr::prep_each(src[PREP_X6], [&](auto s) { x6_pack_multi_kernel<<<(unsigned)p.blocks[PREP_X6], 256, 0, st>>>(s, abr::x6_flags_ptr()); });
+    abr::prep_each(src[PREP_H3], [&](auto s) {
+        h3_rowscale_multi_kernel<<<(unsigned)p.scale_blocks[PREP_H3], 256, 0, st>>>(s, abr::x6_flags_ptr());
+        h3_pack_multi_kernel<<<(unsigned)p.blocks[PREP_H3], 256, 0, st>>>(s);
+    });
+    abr::prep_wino_h3_direct(src[PREP_WINO_H3], p.blocks[PREP_WINO_H3], p.scale_blocks[PREP_WINO_H3], abr::x6_flags_ptr(), st);
+    return nullptr;
+}
+}  // namespace
 
 // The derived weights route r needs, from the library's per-(w, w_version) cache, filled here on a miss; nullptr = no version, or no memory.
 static const void* cached_weights(const abr::ConvRoute& r, const float* w, int64_t version, hipStream_t st) {
     if (!version) return nullptr;
-    return abr::derived_cached(w, r.kind, r.bytes, version, st, [&](void* buf) { return derive_weights(r, w, buf, nullptr, st); });
+    return abr::derived_cached(w, r.kind, r.bytes, version, st, [&](void* buf) {
+        PrepPlan p;
+        p.derived(r, w, buf);
+        return prep_launch(p, p.u_floats ? abr::wino_ws(st, p.u_floats) : nullptr, st) || hipGetLastError() != hipSuccess;
+    });
 }
 
 // ... or, without a cache entry, derived into this stream's scratch behind the `own` floats the caller keeps there for itself (*ws = the scratch;
@@ -1613,7 +1651,9 @@ static const void* conv_weights(const abr::ConvRoute& r, const float* w, int64_t
     if (ws) *ws = s;
     if (cached || !s) return cached;
     float* buf = s + own;
-    return derive_weights(r, w, buf, buf + r.bytes / 4, st) ? nullptr : buf;
+    PrepPlan p;
+    p.derived(r, w, buf);
+    return prep_launch(p, buf + r.bytes / 4, st) || hipGetLastError() != hipSuccess ? nullptr : buf;
 }
 
 // stride-1 pad-1 3x3 conv as Winograd F(4x4,3x3): weight + input transforms, 36 batched GEMMs, output transform with the epilogue.  The
@@ -1811,66 +1851,13 @@ extern "C" int abr_conv_prepare_weights(const float* w, int Cout, int R, int S, 
     return ABR_OK;
 }
 
-namespace abr {
-int prep_transpose_multi(const PrepJob* jobs_dev, int njobs, int blocks, hipStream_t st) {
-    if (njobs <= 0 || blocks <= 0) return 0;
-    dgrad_weights_multi_kernel<<<(unsigned)blocks, 256, 0, st>>>(jobs_dev, njobs);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-int prep_pack_h3_multi(const PrepJob* jobs_dev, int njobs, int blocks, int scale_blocks, hipStream_t st) {
-    if (njobs <= 0 || blocks <= 0) return 0;
-    h3_rowscale_multi_kernel<<<(unsigned)scale_blocks, 256, 0, st>>>(jobs_dev, njobs, abr::x6_flags_ptr());
-    h3_pack_multi_kernel<<<(unsigned)blocks, 256, 0, st>>>(jobs_dev, njobs);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-int prep_pack_multi(const PrepJob* jobs_dev, int njobs, int blocks, hipStream_t st) {
-    if (njobs <= 0 || blocks <= 0) return 0;
-    x6_pack_multi_kernel<<<(unsigned)blocks, 256, 0, st>>>(jobs_dev, njobs, abr::x6_flags_ptr());
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-}  // namespace abr
-
-// Job tables of abr_conv_prepare_batch: a RING of pinned host staging + device slots per stream.  A call takes the next njobs slots; a region is
-// reused only after the upload that last used it has completed -- thousands of jobs (tens of optimiser steps) later, so the host never waits for
-// the stream (a single staging buffer made every call wait for the previous call's upload, which sits behind the whole backward pass).
-namespace {
-constexpr size_t kPrepRing = 8192;
-struct PrepTables {
-    abr::PrepJob* host = nullptr;
-    abr::PrepJob* dev = nullptr;
-    size_t head = 0;                                   // next free slot
-    std::vector<std::pair<size_t, hipEvent_t>> inflight;   // (end slot of a past call's region, its upload event), oldest first
-    size_t inflight_begin = 0;                         // first slot still covered by `inflight`
-    float* u_scratch = nullptr;   // fp32 Winograd-domain weights on their way to being packed
-    size_t u_floats = 0;
-};
-std::map<hipStream_t, PrepTables> g_prep_tables;
-std::mutex g_prep_mu;
-
-// slots [*first, *first + n) of the ring, free of any upload still in flight
-bool prep_ring_take(PrepTables& T, size_t n, size_t* first) {
-    if (n > kPrepRing) return false;
-    if (!T.host) {
-        if (hipHostMalloc(&T.host, kPrepRing * sizeof(abr::PrepJob)) != hipSuccess || hipMalloc(&T.dev, kPrepRing * sizeof(abr::PrepJob)) != hipSuccess) return false;
-    }
-    if (T.head + n > kPrepRing) {   // wrap: everything recorded so far must be done before slot 0 is written again
-        for (auto& pr : T.inflight) { (void)hipEventSynchronize(pr.second); (void)hipEventDestroy(pr.second); }
-        T.inflight.clear();
-        T.head = 0;
-    }
-    *first = T.head;
-    T.head += n;
-    return true;
-}
-}  // namespace
-
 extern "C" int abr_conv_prepare_batch(const abr_prep_item* items, int n, void* stream) {
     ABR_REQUIRE(n >= 0 && (n == 0 || items), "conv_prepare_batch: bad args");
     if (n == 0) return ABR_OK;
     hipStream_t st = abr::as_stream(stream);
     std::lock_guard<std::mutex> lock(g_prep_mu);
     PrepTables& T = g_prep_tables[st];
-    std::vector<abr::PrepJob> tj, uj, pj, hj, wj;    // transposes, Winograd weight transforms, bf16x3 packings, f16x3 packings, f16x3 Winograd weights straight to planes
+    PrepPlan plan;
     std::vector<void*> tokens;
     std::vector<hipStream_t> waited;              // reader streams this call's stream is already ordered behind (derived_acquire)
     // every early return between the acquires below and derived_commit releases the tokens (entries left pending would never be evictable and
@@ -1879,125 +1866,42 @@ extern "C" int abr_conv_prepare_batch(const abr_prep_item* items, int n, void* s
         std::vector<void*>& t; bool committed = false;
         ~TokenGuard() { if (!committed && !t.empty()) abr::derived_abandon(t.data(), (int)t.size()); }
     } token_guard{tokens};
-    std::vector<size_t> u_off;                    // per uj entry: offset (floats) of its U inside the scratch
-    size_t u_total = 0;
-    int tb = 0, ub = 0, pb = 0, hb = 0, hsb = 0, wb = 0, wsb = 0;  // workgroups of the launches (hsb: the f16x3 row-scale launch; wb / wsb: the direct Winograd pack / scale launches)
-    std::vector<int> h_scale_first;               // per hj entry: its first workgroup in the row-scale launch (stored in PrepJob::c once the sources are patched)
-    auto add_pack_h3 = [&](const float* src, int64_t rows, int K, void* dst) {
-        abr::PrepJob j{};
-        j.src = src; j.dst = dst; j.a = (int)rows; j.b = K; j.gx = (K + 63) / 64; j.gy = (int)((rows + 31) / 32); j.first_block = hb;
-        hb += j.gx * j.gy;
-        h_scale_first.push_back(hsb);
-        hsb += j.gy * 8;
-        hj.push_back(j);
-    };
-    auto add_pack = [&](const float* src, int64_t rows, int K, void* dst) {
-        abr::PrepJob j{};
-        j.src = src; j.dst = dst; j.a = (int)rows; j.b = K; j.gx = (K + 63) / 64; j.gy = (int)((rows + 31) / 32); j.first_block = pb;
-        pb += j.gx * j.gy;
-        pj.push_back(j);
-    };
-    // what abr_conv_prepare_weights derives from tensor `w` ([Cout][R][S][Cin]) of a conv with this geometry: returns 1 when it has to go the per-tensor way
-    auto derive = [&](const float* w, int Cout, int R, int S, int Cin, int stride, int pad, int math, int64_t ver) -> int {
+    // what abr_conv_prepare_weights derives from tensor `w` ([Cout][R][S][Cin]) of a conv with this geometry, planned into its cache entry unless
+    // that holds the version already; false = no memory for the entry
+    auto derive = [&](const float* w, int Cout, int R, int S, int Cin, int stride, int pad, int math, int64_t ver) {
         const abr::ConvRoute r = prep_route(Cout, R, S, Cin, stride, pad, math);
-        if (r.kind == abr::DERIVED_NONE) return 0;   // nothing to derive
-        if (r.kind == abr::DERIVED_WINO_U) return 1;
+        if (r.kind == abr::DERIVED_NONE) return true;
         void* tok = nullptr;
         void* dst = abr::derived_acquire(w, r.kind, r.bytes, ver, st, &tok, &waited);
-        if (!dst) return 1;
-        if (!tok) return 0;   // already there
-        tokens.push_back(tok);
-        const bool h3 = r.kind == abr::DERIVED_H3_PLANES || r.kind == abr::DERIVED_WINO_U_H3_PLANES;
-        if (!wino_split_kind(r.kind)) {
-            if (h3) add_pack_h3(w, r.rows, r.K, dst); else add_pack(w, r.rows, r.K, dst);
-            return 0;
+        if (!dst) return false;
+        if (tok) {
+            tokens.push_back(tok);
+            plan.derived(r, w, dst);
         }
-        if (h3 && Cin % 64 == 0) {   // w -> planes, U never written (conv_winograd.hip: wino_h3_scales / wino_h3_pack)
-            abr::PrepJob j{};
-            j.src = w; j.dst = dst; j.a = Cout; j.b = Cin; j.gx = Cin / 64; j.gy = Cout / 32; j.first_block = wb; j.c = wsb;
-            wb += j.gx * j.gy;
-            wsb += Cout / 4;
-            wj.push_back(j);
-            return 0;
-        }
-        abr::PrepJob j{};
-        j.src = w; j.a = Cout; j.b = Cin; j.gx = (int)(((int64_t)Cout * (Cin / 4) + 255) / 256); j.gy = 1; j.first_block = ub;
-        ub += j.gx;
-        uj.push_back(j);
-        u_off.push_back(u_total);
-        // the packing job reads the fp32 U from the scratch: its src is patched in once the scratch address is known (c = 1: src is a scratch offset)
-        if (h3) { add_pack_h3(reinterpret_cast<const float*>(u_total), r.rows, r.K, dst); hj.back().c = 1; }
-        else { add_pack(reinterpret_cast<const float*>(u_total), r.rows, r.K, dst); pj.back().c = 1; }
-        u_total += (size_t)r.rows * r.K;
-        return 0;
+        return true;
     };
-    std::vector<int> single_fwd, single_bwd;
     for (int i = 0; i < n; i++) {
         const abr_prep_item& it = items[i];
         ABR_REQUIRE(it.w && it.w_version != 0 && it.Cout > 0 && it.R > 0 && it.S > 0 && it.Cin > 0, "conv_prepare_batch: bad item");
-        if (derive(it.w, it.Cout, it.R, it.S, it.Cin, it.stride, it.pad, it.math, it.w_version)) single_fwd.push_back(i);
+        ABR_REQUIRE(derive(it.w, it.Cout, it.R, it.S, it.Cin, it.stride, it.pad, it.math, it.w_version), "conv_prepare_batch: no memory for the derived weights");
         if (it.wt) {
-            abr::PrepJob j{};
-            j.src = it.w; j.scale = it.scale; j.dst = it.wt; j.a = it.Cout; j.b = it.R * it.S; j.c = it.Cin;
-            const int tile = abr::prep_transpose_tile(it.Cout, it.Cin, it.w, it.wt);
-            j.gx = (it.Cin + tile - 1) / tile; j.gy = (it.Cout + tile - 1) / tile; j.first_block = tb;
-            tb += j.gx * j.gy * it.R * it.S;
-            tj.push_back(j);
+            plan.transpose(it.w, it.scale, it.wt, it.Cout, it.R * it.S, it.Cin);
             // the dgrad conv: [Cin][R][S][Cout] weights, stride 1, pad R-1-pad
-            if (derive(it.wt, it.Cin, it.R, it.S, it.Cout, 1, it.R - 1 - it.pad, it.math, it.w_version)) single_bwd.push_back(i);
+            ABR_REQUIRE(derive(it.wt, it.Cin, it.R, it.S, it.Cout, 1, it.R - 1 - it.pad, it.math, it.w_version),
+                        "conv_prepare_batch: no memory for the derived weights");
         }
     }
-    const size_t njobs = tj.size() + uj.size() + pj.size() + hj.size() + wj.size();
-    if (njobs) {
-        if (u_total && T.u_floats < u_total) {
-            if (T.u_scratch) { (void)hipStreamSynchronize(st); (void)hipFree(T.u_scratch); T.u_scratch = nullptr; T.u_floats = 0; }
-            ABR_REQUIRE(hipMalloc(&T.u_scratch, u_total * sizeof(float)) == hipSuccess, "conv_prepare_batch: no memory for the Winograd-domain scratch");
-            T.u_floats = u_total;
-        }
-        for (size_t k = 0; k < uj.size(); k++) uj[k].dst = T.u_scratch + u_off[k];
-        for (auto& j : pj)
-            if (j.c == 1) { j.src = T.u_scratch + reinterpret_cast<size_t>(j.src); j.c = 0; }
-        for (size_t k = 0; k < hj.size(); k++) {
-            if (hj[k].c == 1) hj[k].src = T.u_scratch + reinterpret_cast<size_t>(hj[k].src);
-            hj[k].c = h_scale_first[k];
-        }
-        size_t first = 0;
-        ABR_REQUIRE(prep_ring_take(T, njobs, &first), "conv_prepare_batch: no memory for the job tables");
-        abr::PrepJob* h = T.host + first;
-        abr::PrepJob* d = T.dev + first;
-        std::copy(tj.begin(), tj.end(), h);
-        std::copy(uj.begin(), uj.end(), h + tj.size());
-        std::copy(pj.begin(), pj.end(), h + tj.size() + uj.size());
-        std::copy(hj.begin(), hj.end(), h + tj.size() + uj.size() + pj.size());
-        std::copy(wj.begin(), wj.end(), h + tj.size() + uj.size() + pj.size() + hj.size());
-        ABR_REQUIRE(hipMemcpyAsync(d, h, njobs * sizeof(abr::PrepJob), hipMemcpyHostToDevice, st) == hipSuccess, "conv_prepare_batch: table upload failed");
-        hipEvent_t up = nullptr;
-        if (hipEventCreateWithFlags(&up, hipEventDisableTiming) == hipSuccess) {
-            (void)hipEventRecord(up, st);
-            T.inflight.emplace_back(first + njobs, up);
-        }
-        int bad = abr::prep_transpose_multi(d, (int)tj.size(), tb, st);
-        bad |= abr::prep_wino_u_multi(d + tj.size(), (int)uj.size(), ub, st);
-        bad |= abr::prep_pack_multi(d + tj.size() + uj.size(), (int)pj.size(), pb, st);
-        bad |= abr::prep_pack_h3_multi(d + tj.size() + uj.size() + pj.size(), (int)hj.size(), hb, hsb, st);
-        bad |= abr::prep_wino_h3_direct_multi(d + tj.size() + uj.size() + pj.size() + hj.size(), (int)wj.size(), wb, wsb,
-                                              abr::x6_flags_ptr(), st);
-        ABR_REQUIRE(!bad, "conv_prepare_batch: launch failed");
-        abr::derived_commit(tokens.data(), (int)tokens.size(), st);
-        token_guard.committed = true;
-        ABR_CHECK_LAUNCH("conv_prepare_batch");
+    if (T.u_floats < plan.u_floats) {
+        if (T.u_scratch) { (void)hipStreamSynchronize(st); (void)hipFree(T.u_scratch); T.u_scratch = nullptr; T.u_floats = 0; }
+        ABR_REQUIRE(hipMalloc(&T.u_scratch, plan.u_floats * sizeof(float)) == hipSuccess, "conv_prepare_batch: no memory for the Winograd-domain scratch");
+        T.u_floats = plan.u_floats;
     }
-    // shapes the batched kernels do not take: the per-tensor calls (after the transposes above, which every dgrad copy went through)
-    for (int i : single_fwd) {
-        const abr_prep_item& it = items[i];
-        const int rc = abr_conv_prepare_weights(it.w, it.Cout, it.R, it.S, it.Cin, it.stride, it.pad, it.math, it.w_version, stream);
-        if (rc != ABR_OK) return rc;
-    }
-    for (int i : single_bwd) {
-        const abr_prep_item& it = items[i];
-        const int rc = abr_conv_prepare_weights(it.wt, it.Cin, it.R, it.S, it.Cout, 1, it.R - 1 - it.pad, it.math, it.w_version, stream);
-        if (rc != ABR_OK) return rc;
-    }
+    const char* err = prep_launch(plan, T.u_scratch, st, &T);
+    ABR_REQUIRE(!err, "conv_prepare_batch: %s", err);
+    ABR_REQUIRE(hipGetLastError() == hipSuccess, "conv_prepare_batch: launch failed");
+    abr::derived_commit(tokens.data(), (int)tokens.size(), st);
+    token_guard.committed = true;
+    ABR_CHECK_LAUNCH("conv_prepare_batch");
     return ABR_OK;
 }
 
@@ -2032,15 +1936,19 @@ extern "C" int64_t abr_conv_packed_bytes(int64_t rows, int64_t K) { return rows 
 extern "C" int abr_conv_pack_weights(const float* w, int64_t rows, int K, void* planes, void* stream) {
     ABR_REQUIRE(w && planes && rows > 0 && K > 0 && K % 16 == 0, "conv_pack_weights: needs pointers, rows > 0 and K a positive multiple of 16");
     ABR_REQUIRE(x6_packed_bytes(rows, K) < (int64_t)0xFFFFFFF0, "conv_pack_weights: packed matrix must stay below 4 GB (32-bit buffer offsets)");
-    ABR_REQUIRE(x6_pack(w, rows, K, planes, abr::as_stream(stream)) == 0, "conv_pack_weights: launch failed");
+    PrepPlan p;
+    p.pack(false, w, rows, K, planes);
+    ABR_REQUIRE(!prep_launch(p, nullptr, abr::as_stream(stream)) && hipGetLastError() == hipSuccess, "conv_pack_weights: launch failed");
     return ABR_OK;
 }
 
 extern "C" int abr_conv_dgrad_weights(const float* w, const float* scale, int Cout, int R, int S, int Cin, float* wt,
                                       void* stream) {
     ABR_REQUIRE(w && wt && Cout > 0 && R > 0 && S > 0 && Cin > 0, "conv_dgrad_weights: bad args");
-    dim3 grid((Cin + 31) / 32, (Cout + 31) / 32, R * S);
-    dgrad_weights_kernel<<<grid, 256, 0, abr::as_stream(stream)>>>(w, scale, Cout, R * S, Cin, wt);
+    PrepPlan p;
+    p.transpose(w, scale, wt, Cout, R * S, Cin);
+    const char* err = prep_launch(p, nullptr, abr::as_stream(stream));
+    ABR_REQUIRE(!err, "conv_dgrad_weights: %s", err);
     ABR_CHECK_LAUNCH("conv_dgrad_weights");
     return ABR_OK;
 }

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict
 }
 
 // U = G g G^T, one row I of it (6 values), with EVERY rounding spelled out (contraction off, explicit fma): the same U has to come out of every
-// kernel that forms it -- the fp32 transforms (wino_weight_*_kernel) and the kernels that go from w straight to packed f16x3 planes
+// kernel that forms it -- the fp32 transform (wino_weight_multi_kernel) and the kernels that go from w straight to packed f16x3 planes
 // (wino_h3_*_multi_kernel) -- and left to itself the compiler fuses (1/24) a -+ (1/12) b + (1/6) c and the sums of products differently from one
 // kernel to the next (seen in round 6: planes differing in rows 24..35 between two kernels built from one expression).  The expressions are the
 // ones rounds 2-5's build evaluated (read off its code), so that every result of those rounds is reproduced bit for bit:
@@ -204,36 +204,11 @@ __device__ __forceinline__ void for_rows6(F&& f) {
     f(std::integral_constant<int, 3>{}); f(std::integral_constant<int, 4>{}); f(std::integral_constant<int, 5>{});
 }
 
-// w [N][3][3][C] (OHWI) -> U [36][N][C]; V input channels per thread
-template <int V>
-__global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restrict__ w, int N, int C, float* __restrict__ U) {
-    typedef vf<V> fv;
-    const int Cv = C / V;
-    const int64_t total = (int64_t)N * Cv;
-    const int64_t ps = (int64_t)N * C;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int c = V * (int)(idx % Cv);
-        const int64_t n = idx / Cv;
-        fv g[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int q = 0; q < 3; q++) g[r][q] = vld<V>(w + ((n * 3 + r) * 3 + q) * C + c);
-        for_rows6([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            fv u[6];
-            wino_u_row<i>(g, u);
-            float* o = U + ((int64_t)(6 * i) * N + n) * C + c;
-            vst(o, u[0]); vst(o + ps, u[1]); vst(o + 2 * ps, u[2]); vst(o + 3 * ps, u[3]); vst(o + 4 * ps, u[4]); vst(o + 5 * ps, u[5]);
-        });
-    }
-}
-
-// the same for a table of weight tensors (abr_conv_prepare_batch): workgroup -> (job, 256 (n, c4) items of it)
-__global__ __launch_bounds__(256) void wino_weight_multi_kernel(const abr::PrepJob* __restrict__ jobs, int njobs) {
+// w [N][3][3][C] (OHWI) -> U [36][N][C], C % 4 == 0: workgroup -> (job, 256 (n, c4) items of it)
+template <class Src>
+__global__ __launch_bounds__(256) void wino_weight_multi_kernel(Src jobs) {
     typedef vf<4> fv;
-    const int j = abr::prep_find_job(jobs, njobs, blockIdx.x);
-    const abr::PrepJob jb = jobs[j];
+    const abr::PrepJob jb = abr::prep_job(jobs, blockIdx.x);
     const float* w = jb.src;
     float* U = reinterpret_cast<float*>(jb.dst);
     const int N = jb.a, C = jb.b, Cv = C / 4;
@@ -257,37 +232,27 @@ __global__ __launch_bounds__(256) void wino_weight_multi_kernel(const abr::PrepJ
 }
 
 // ---- f16x3: Winograd-domain weights straight into the packed planes (round 6) ---------------------------------------------------------------
-// abr_conv_prepare_batch used to go  w -> U (fp32, 4x the weights' size, written) -> row amax (U read) -> pack (U read again, planes written):
+// The f16x3 planes of U used to go  w -> U (fp32, 4x the weights' size, written) -> row amax (U read) -> pack (U read again, planes written):
 // 3.4 GB of HBM traffic per optimiser step for the step's 20.6 M Winograd-domain weights and their dgrad copies, on a stream of its own but NOT
 // hidden -- with the preparation knocked out the step is 0.86 ms shorter (MEASUREMENTS.md).  The two kernels below never materialise U: pass A
 // computes every U row's amax from w (one wave per output channel), pass B recomputes U from a w tile staged in LDS and writes the two fp16 planes
 // in MFMA-fragment order directly.  w (1/4 of U) is read twice, the planes are written once.  Same G g G^T arithmetic (wino_u_row), same row scales,
-// same split as wino_weight_multi_kernel + h3_rowscale_multi_kernel + h3_pack_multi_kernel: bit-identical planes
-// (tests/test_gpu_prep_batch.py compares against the self-contained path).  jobs[j]: src = w [N][3][3][C], dst = planes of the [36 N][C] matrix with
-// its 36 N row scales behind them, a = N (% 32 == 0), b = C (% 64 == 0), c = first workgroup in the scale launch (N / 4 workgroups),
-// first_block / gx = C / 64 / gy = N / 32 in the pack launch.
-__device__ __forceinline__ int prep_find_job_by_c(const abr::PrepJob* jobs, int njobs, int block) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].c <= block) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-__device__ __forceinline__ size_t h3_planes_bytes_of(int rows, int K) { return (size_t)((rows + 31) / 32 * 32) * (size_t)K * 4; }
+// same split as wino_weight_multi_kernel + h3_rowscale_multi_kernel + h3_pack_multi_kernel, which still make the planes when C % 64 != 0:
+// bit-identical planes.  A job: src = w [N][3][3][C], dst = planes of the [36 N][C] matrix with its 36 N row scales behind them, a = N (% 32 == 0),
+// b = C (% 64 == 0), c = first workgroup in the scale launch (N / 4 workgroups), first_block / gx = C / 64 / gy = N / 32 in the pack launch.
 
 // pass A: the scale of every U row.  One WAVE per output channel n: its lanes walk the input channels (4 per lane, 256 per trip), keep the 36
 // running maxima of |U| in registers, reduce them across the wave once and lanes 0..35 write the rows' scales (h3_scales of the amax bits) behind the
 // planes -- no atomics, no zeroed scratch.  .c = the job's first workgroup in this launch (4 output channels per workgroup).
-__global__ __launch_bounds__(256, 3) void wino_h3_scales_multi_kernel(const abr::PrepJob* __restrict__ jobs, int njobs, unsigned* flags) {
+template <class Src>
+__global__ __launch_bounds__(256, 3) void wino_h3_scales_multi_kernel(Src jobs, unsigned* flags) {
     typedef vf<4> fv;
-    const int j = prep_find_job_by_c(jobs, njobs, blockIdx.x);
-    const abr::PrepJob jb = jobs[j];
+    const abr::PrepJob jb = abr::prep_job<&abr::PrepJob::c>(jobs, blockIdx.x);
     const float* w = jb.src;
     const int N = jb.a, C = jb.b;
     const int lane = threadIdx.x & 63;
     const int64_t n = (int64_t)(blockIdx.x - jb.c) * 4 + (threadIdx.x >> 6);    // N % 32 == 0: always inside
-    float* scales = reinterpret_cast<float*>(reinterpret_cast<char*>(jb.dst) + h3_planes_bytes_of(36 * N, C));
+    float* scales = reinterpret_cast<float*>(reinterpret_cast<char*>(jb.dst) + abr::h3_planes_bytes_dev(36 * N, C));
     unsigned mx[36];
 #pragma unroll
     for (int k = 0; k < 36; k++) mx[k] = 0u;
@@ -332,11 +297,11 @@ __global__ __launch_bounds__(256, 3) void wino_h3_scales_multi_kernel(const abr:
 constexpr int kWhPitch = 9 * 64 + 4;                                  // floats per row of the staged w tile (+4: conflict-free ds_read_b128 over 32 rows)
 constexpr size_t kWhLds = sizeof(float) * 32 * kWhPitch;              // 74 240 B: two workgroups per CU
 
-__global__ __launch_bounds__(256) void wino_h3_pack_multi_kernel(const abr::PrepJob* __restrict__ jobs, int njobs) {
+template <class Src>
+__global__ __launch_bounds__(256) void wino_h3_pack_multi_kernel(Src jobs) {
     typedef vf<4> fv;
     extern __shared__ __attribute__((aligned(16))) float wt_[];
-    const int j = abr::prep_find_job(jobs, njobs, blockIdx.x);
-    const abr::PrepJob jb = jobs[j];
+    const abr::PrepJob jb = abr::prep_job(jobs, blockIdx.x);
     const float* w = jb.src;
     const int N = jb.a, C = jb.b;
     const int lb = blockIdx.x - jb.first_block;
@@ -365,7 +330,7 @@ __global__ __launch_bounds__(256) void wino_h3_pack_multi_kernel(const abr::Prep
             gB[r][q] = {{b.x, b.y, b.z, b.w}};
         }
     uint4* planes = reinterpret_cast<uint4*>(jb.dst);
-    const float* scales = reinterpret_cast<const float*>(reinterpret_cast<const char*>(jb.dst) + h3_planes_bytes_of(36 * N, C));   // pass A's
+    const float* scales = reinterpret_cast<const float*>(reinterpret_cast<const char*>(jb.dst) + abr::h3_planes_bytes_dev(36 * N, C));   // pass A's
     const int ks = kc * 4 + wave, KS = C / 16;
     auto emit = [&](int xi, const fv& uA, const fv& uB, float sc) {
         const float inv = 1.f / sc;   // (a power of two: exact)
@@ -583,27 +548,21 @@ int wino_input_transform(const float* x, int B, int H, int W, int C, float* V, h
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-int wino_weight_transform(const float* w, int N, int C, float* U, hipStream_t st) {
-    if (C % 4 == 0) wino_weight_kernel<4><<<grid_for((int64_t)N * (C / 4)), 256, 0, st>>>(w, N, C, U);
-    else wino_weight_kernel<2><<<grid_for((int64_t)N * (C / 2)), 256, 0, st>>>(w, N, C, U);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-
-int prep_wino_h3_direct_multi(const PrepJob* jobs_dev, int njobs, int pack_blocks, int scale_blocks, unsigned* flags, hipStream_t st) {
-    if (njobs <= 0 || pack_blocks <= 0) return 0;
+void prep_wino_h3_direct(const PrepJobs& jobs, int pack_blocks, int scale_blocks, unsigned* flags, hipStream_t st) {
+    if (!jobs.n) return;
     static std::once_flag attr_once;   // (several host threads may prepare weights: one attribute call, seen by all)
     std::call_once(attr_once, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino_h3_pack_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWhLds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino_h3_pack_multi_kernel<PrepTable>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWhLds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino_h3_pack_multi_kernel<PrepJob>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWhLds);
     });
-    wino_h3_scales_multi_kernel<<<(unsigned)scale_blocks, 256, 0, st>>>(jobs_dev, njobs, flags);
-    wino_h3_pack_multi_kernel<<<(unsigned)pack_blocks, 256, kWhLds, st>>>(jobs_dev, njobs);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    prep_each(jobs, [&](auto src) {
+        wino_h3_scales_multi_kernel<<<(unsigned)scale_blocks, 256, 0, st>>>(src, flags);
+        wino_h3_pack_multi_kernel<<<(unsigned)pack_blocks, 256, kWhLds, st>>>(src);
+    });
 }
 
-int prep_wino_u_multi(const PrepJob* jobs_dev, int njobs, int blocks, hipStream_t st) {
-    if (njobs <= 0 || blocks <= 0) return 0;
-    wino_weight_multi_kernel<<<(unsigned)blocks, 256, 0, st>>>(jobs_dev, njobs);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+void prep_wino_u(const PrepJobs& jobs, int blocks, hipStream_t st) {
+    prep_each(jobs, [&](auto src) { wino_weight_multi_kernel<<<(unsigned)blocks, 256, 0, st>>>(src); });
 }
 
 int wino_output_transform(const float* Mm, int B, int H, int W, int N, const float* scale, const float* bias, int relu, const float* mask,

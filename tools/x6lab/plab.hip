@@ -2,7 +2,7 @@
 //
 // Today (conv_igemm_x6w_kernel<128,128,1,4>): a workgroup fetches its 128 x 32 fp32 A tile, splits it into three bf16 planes in registers
 // (~1.8 VALU per MFMA) and parks them in LDS (12 ds_write_b64 per thread and k-tile); every n-tile column repeats that for the same rows.
-// Here the producer of A has written the exact split ONCE, in MFMA-fragment order (the layout x6_pack_kernel gives the weights):
+// Here the producer of A has written the exact split ONCE, in MFMA-fragment order (the layout x6_pack_multi_kernel gives the weights):
 //     chunk(mb, ks, pl) = 64 lanes x 16 B, lane l = row mb*32 + (l & 31), k = ks*16 + (l >> 5)*8 .. +8 of plane pl
 //     byte address      = (((mb * K/16 + ks) * 3 + pl) * 64 + l) * 16
 // and the consumer brings the 24 chunks of a k-tile into LDS by LDS-DMA (buffer_load_dwordx4 ... lds: 1 KB per wave-instruction, no VGPR

@@ -1,8 +1,8 @@
 """Flat parameter / gradient storage.
 
-The reference keeps 52 separate trainable tensors, gives each its own SGD param group (solver/build.py:7-21) and lets
-DistributedDataParallel bucket their gradients.  On MI355X the whole trainable set (32.96 M fp32 = 131.9 MB) is ONE
-contiguous buffer, its gradient ONE buffer of the same shape:
+The reference keeps every trainable tensor separate (R-50-C4 at the default FREEZE_CONV_BODY_AT 2: 52 of them, R-101-C4: 103), gives
+each its own SGD param group (solver/build.py:7-21) and lets DistributedDataParallel bucket their gradients.  On MI355X the whole trainable set
+(R-50-C4: 32.97 M fp32 = 131.9 MB, R-101-C4: 51.91 M = 207.6 MB) is ONE contiguous buffer, its gradient ONE buffer of the same shape:
   * wgrad kernels accumulate straight into views of the gradient buffer (no per-tensor autograd accumulation),
   * the data-parallel exchange is a single RCCL all-reduce over that buffer (or a few large chunks),
   * the optimiser is one fused multi-tensor kernel with per-segment (lr, weight-decay).

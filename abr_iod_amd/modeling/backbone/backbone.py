@@ -1,4 +1,4 @@
-"""build_backbone (mirror of maskrcnn_benchmark/modeling/backbone/backbone.py): R-50-C4 = nn.Sequential(body=ResNet)."""
+"""build_backbone (mirror of maskrcnn_benchmark/modeling/backbone/backbone.py): R-50-C4 / R-101-C4 = nn.Sequential(body=ResNet)."""
 from collections import OrderedDict
 
 from torch import nn
@@ -15,7 +15,7 @@ class _Body(nn.Sequential):
 
 
 def build_backbone(cfg):
-    assert cfg.MODEL.BACKBONE.CONV_BODY == "R-50-C4", "every configs/voc YAML uses R-50-C4; FPN / FBNet are out of scope"
+    resnet.stage_specs(cfg.MODEL.BACKBONE.CONV_BODY)   # NotImplementedError for the bodies this build does not run
     body = resnet.ResNet(cfg)
     model = _Body(OrderedDict([("body", body)]))
     model.out_channels = cfg.MODEL.RESNETS.BACKBONE_OUT_CHANNELS

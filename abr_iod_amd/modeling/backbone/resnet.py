@@ -1,7 +1,8 @@
-"""ResNet-50 C4 body and C5 head on the HIP conv engine.
+"""ResNet C4 bodies (R-50-C4, R-101-C4) and the C5 head on the HIP conv engine.
 
-Mirror of maskrcnn_benchmark/modeling/backbone/resnet.py for the one variant every configs/voc YAML uses
-(CONV_BODY "R-50-C4", BottleneckWithFixedBatchNorm, StemWithFixedBatchNorm, STRIDE_IN_1X1=True, groups=1), with the deformable conv2 of
+Mirror of maskrcnn_benchmark/modeling/backbone/resnet.py for the C4 bodies of the reference's backbone registry (backbone.py:12-15)
+(CONV_BODY "R-50-C4", the configs/voc default, and "R-101-C4": layer3 has 23 blocks instead of 6; BottleneckWithFixedBatchNorm,
+StemWithFixedBatchNorm, STRIDE_IN_1X1=True, groups=1), with the deformable conv2 of
 STAGE_WITH_DCN / WITH_MODULATED_DCN / DEFORMABLE_GROUPS in layer1..layer3 (resnet.py:105-125, :289-312; layers/misc.py:114-190):
     ResNet (:81-155)       stem + layer1..layer3, FREEZE_CONV_BODY_AT semantics of _freeze_backbone (:134-143)
     ResNetHead (:158-207)  layer4, used by ResNet50Conv5ROIFeatureExtractor
@@ -10,7 +11,7 @@ Module / parameter / buffer NAMES are the reference's (state_dict keys match; co
 instead of OIHW, converted at the checkpoint boundary).
 
 Execution model: every conv is ONE launch of the implicit-GEMM MFMA kernel with FrozenBN scale/bias, the residual
-add and the ReLU fused in its epilogue.  A whole stage (3-6 bottlenecks) is a single autograd node whose backward is
+add and the ReLU fused in its epilogue.  A whole stage (3-23 bottlenecks) is a single autograd node whose backward is
 hand-scheduled: dgrad is the same kernel on a flipped/transposed weight copy with the ReLU mask of the producer
 fused in the epilogue, wgrad accumulates atomically into the flat gradient buffer.  Activations are NHWC.
 """
@@ -29,6 +30,20 @@ from ...layers._layout import as_nhwc, from_nhwc
 StageSpec = namedtuple("StageSpec", ["index", "block_count", "return_features"])
 ResNet50StagesTo4 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, False), (2, 4, False), (3, 6, True)))
 ResNet50StagesTo5 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, False), (2, 4, False), (3, 6, False), (4, 3, True)))
+ResNet101StagesTo4 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, False), (2, 4, False), (3, 23, True)))
+
+# CONV_BODY -> the body's stages: the C4 entries of the reference's _STAGE_SPECS (resnet.py:443-453).  The C5 bodies would feed C5 into the
+# detector's layer4 head, and the FPN bodies' forward returns a tuple FPN cannot take (resnet.py:145-155): neither makes a working detector there.
+STAGE_SPECS = {"R-50-C4": ResNet50StagesTo4, "R-101-C4": ResNet101StagesTo4}
+
+
+def stage_specs(conv_body):
+    """the StageSpecs of MODEL.BACKBONE.CONV_BODY; NotImplementedError for every body this build does not run"""
+    specs = STAGE_SPECS.get(conv_body)
+    if specs is None:
+        raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r}: this build runs the C4 bodies {} only (no C5, FPN or FBNet body)"
+                                  .format(conv_body, ", ".join(sorted(STAGE_SPECS))))
+    return specs
 
 # Weight versions: data derived from a weight tensor (the flipped dgrad copies; inside the library, under abr_conv_desc::w_version, the
 # Winograd-domain weights and the fragment-packed bf16x3 planes the bf16x6 weights-direct kernel reads) is rebuilt lazily when its version is stale.  _PARAM_VERSION moves with EVERY change (optimiser steps, loads, in-place
@@ -648,7 +663,7 @@ class _StemFn(Function):
 class ResNet(nn.Module):
     def __init__(self, cfg):
         super().__init__()
-        assert cfg.MODEL.BACKBONE.CONV_BODY == "R-50-C4", "only the R-50-C4 body is on the hot path (every configs/voc YAML)"
+        specs = stage_specs(cfg.MODEL.BACKBONE.CONV_BODY)
         assert cfg.MODEL.RESNETS.STRIDE_IN_1X1 and cfg.MODEL.RESNETS.NUM_GROUPS == 1
         self.stem = StemWithFixedBatchNorm(cfg)
         width = cfg.MODEL.RESNETS.NUM_GROUPS * cfg.MODEL.RESNETS.WIDTH_PER_GROUP
@@ -656,7 +671,7 @@ class ResNet(nn.Module):
         out2 = cfg.MODEL.RESNETS.RES2_OUT_CHANNELS
         self.stages, self.return_features = [], {}
         with_dcn = tuple(cfg.MODEL.RESNETS.STAGE_WITH_DCN)
-        for spec in ResNet50StagesTo4:
+        for spec in specs:
             name = "layer" + str(spec.index)
             f = 2 ** (spec.index - 1)
             # every block of a stage with STAGE_WITH_DCN[index - 1] gets a deformable conv2 (the layer4 head never does: roi_box_feature_extractors.py:27-36)

@@ -1,7 +1,7 @@
 """make_optimizer / make_lr_scheduler (mirror of maskrcnn_benchmark/solver/build.py:7-30).
 
 The reference builds one torch.optim.SGD param group PER TENSOR (weights: lr=BASE_LR, wd=WEIGHT_DECAY; any name containing
-"bias": lr*BIAS_LR_FACTOR, wd=WEIGHT_DECAY_BIAS) -> 52 x 3 tiny launches per step.  FusedSGD keeps exactly those per-tensor
+"bias": lr*BIAS_LR_FACTOR, wd=WEIGHT_DECAY_BIAS) -> 3 tiny launches per trainable tensor per step (52 tensors for R-50-C4, 103 for R-101-C4).  FusedSGD keeps exactly those per-tensor
 hyper-parameters but applies the whole update as ONE kernel over the model's flat parameter buffer, and owns the
 data-parallel gradient exchange (a few large RCCL all-reduces of the flat gradient buffer over xGMI, the first ones issued during
 the backward pass: solver/grad_reducer.py)."""

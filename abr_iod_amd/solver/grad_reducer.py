@@ -4,9 +4,10 @@ tools/train_incremental.py:231-235), laid out for xGMI: a handful of LARGE sum a
 The flat buffer is cut into three buckets by the order their gradients become final during the backward pass:
     roi_heads  (layer4 + predictor, 15.1 M floats)  -> final once both RoI passes' pooled inputs have their gradient
     rpn        (3x3 conv + fused heads, 9.5 M)      -> final once the C4 feature map has its gradient
-    backbone   (layer2 + layer3, 8.3 M)             -> final at the end of backward
+    backbone   (layer2 + layer3: 8.3 M for R-50-C4, 27.2 M for R-101-C4; more when FREEZE_CONV_BODY_AT < 2)
+                                                    -> final at the end of backward
 `reduce_bucket_async(name)` is called from gradient hooks the trainer arms on those tensors (engine/trainer.py::_arm_overlap), so
-the first two exchanges (75 % of the bytes) run on RCCL's stream underneath the rest of the backward pass; `finish()` issues whatever
+the first two exchanges (75 % of the bytes for R-50-C4, 48 % for R-101-C4) run on RCCL's stream underneath the rest of the backward pass; `finish()` issues whatever
 is left and makes the current stream wait for all of them.
 
 Every rank must issue the SAME sequence of collectives whatever its local state (which hooks fired, whether overlap is enabled,

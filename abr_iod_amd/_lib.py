@@ -161,6 +161,14 @@ _SIGS = {
     "abr_comm_info": (_i, [_vp, _vp]),
     "abr_comm_destroy": (_i, [_vp]),
     "abr_allreduce_flat": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "abr_mask_compact_pos": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "abr_mask_gather_rows": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "abr_mask_targets": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_mask_d2s_bias_relu": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_mask_d2s_bias_relu_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_mask_loss": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _f, _vp, _vp]),
+    "abr_mask_select_sigmoid": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "abr_mask_paste": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
 }
 
 # every symbol include/abr_iod_hip.h declares (tests/test_abi.py checks the library exports them all)

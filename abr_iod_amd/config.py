@@ -158,6 +158,23 @@ _C.MODEL.ROI_BOX_HEAD.NAME_OLD_CLASSES = []
 _C.MODEL.ROI_BOX_HEAD.NAME_NEW_CLASSES = []
 _C.MODEL.ROI_BOX_HEAD.NAME_EXCLUDED_CLASSES = []
 
+# mask head (defaults.py:258-274).  Honoured: the C4 head -- ResNet50Conv5ROIFeatureExtractor shared with the box head, MaskRCNNC4Predictor,
+# CONV_LAYERS[-1], RESOLUTION, POSTPROCESS_MASKS(_THRESHOLD); every other value raises (modeling/roi_heads/mask_head/mask_head.py)
+_C.MODEL.ROI_MASK_HEAD = CN()
+_C.MODEL.ROI_MASK_HEAD.FEATURE_EXTRACTOR = "ResNet50Conv5ROIFeatureExtractor"
+_C.MODEL.ROI_MASK_HEAD.PREDICTOR = "MaskRCNNC4Predictor"
+_C.MODEL.ROI_MASK_HEAD.POOLER_RESOLUTION = 14
+_C.MODEL.ROI_MASK_HEAD.POOLER_SAMPLING_RATIO = 0
+_C.MODEL.ROI_MASK_HEAD.POOLER_SCALES = (1.0 / 16,)
+_C.MODEL.ROI_MASK_HEAD.MLP_HEAD_DIM = 1024
+_C.MODEL.ROI_MASK_HEAD.CONV_LAYERS = (256, 256, 256, 256)
+_C.MODEL.ROI_MASK_HEAD.RESOLUTION = 14
+_C.MODEL.ROI_MASK_HEAD.SHARE_BOX_FEATURE_EXTRACTOR = True
+_C.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS = False
+_C.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS_THRESHOLD = 0.5
+_C.MODEL.ROI_MASK_HEAD.DILATION = 1
+_C.MODEL.ROI_MASK_HEAD.USE_GN = False
+
 _C.SOLVER = CN()
 _C.SOLVER.MAX_ITER = 40000
 _C.SOLVER.BASE_LR = 0.001

@@ -89,9 +89,26 @@ def build_models(cfg_source, cfg_target, seed=0, need_source=True):
     return model_source, model_target
 
 
-def synthetic_batch(batch, height=600, width=1000, seed=42, label_range=(16, 21), device="cuda", max_boxes=5):
+def _box_masks(boxes, height, width, shape, dtype):
+    """[n,H,W] instance masks from xyxy boxes: the ellipse inscribed in each box, or the box itself (no random numbers are drawn)"""
+    ys = torch.arange(height, dtype=torch.float32).view(1, -1, 1)
+    xs = torch.arange(width, dtype=torch.float32).view(1, 1, -1)
+    x1, y1, x2, y2 = (boxes[:, i].view(-1, 1, 1) for i in range(4))
+    if shape == "ellipse":
+        cx, cy, rx, ry = (x1 + x2) / 2, (y1 + y2) / 2, ((x2 - x1) / 2).clamp(min=0.5), ((y2 - y1) / 2).clamp(min=0.5)
+        inside = ((xs - cx) / rx) ** 2 + ((ys - cy) / ry) ** 2 <= 1.0
+    elif shape == "rect":
+        inside = (xs >= x1) & (xs <= x2) & (ys >= y1) & (ys <= y2)
+    else:
+        raise ValueError("masks must be None, 'ellipse' or 'rect', got {!r}".format(shape))
+    return inside.to(dtype)
+
+
+def synthetic_batch(batch, height=600, width=1000, seed=42, label_range=(16, 21), device="cuda", max_boxes=5, masks=None, mask_dtype=torch.uint8):
     """images: uint8-valued U[0,255] BGR minus PIXEL_MEAN (transforms.py:161-165 + defaults.py:56-60);
-    targets: 1..max_boxes GT boxes per image, w,h log-uniform in [32,480], labels over the task's NEW class ids."""
+    targets: 1..max_boxes GT boxes per image, w,h log-uniform in [32,480], labels over the task's NEW class ids.
+    masks="ellipse" / "rect" (opt-in, MODEL.MASK_ON): a "masks" field (SegmentationMask, mode "mask", mask_dtype uint8 or float32) with one
+    instance inside each GT box; images, boxes and labels are the same with and without it."""
     g = torch.Generator().manual_seed(seed)
     mean = torch.tensor([102.9801, 115.9465, 122.7717]).view(1, 3, 1, 1)
     images = torch.randint(0, 256, (batch, 3, height, width), generator=g).float() - mean
@@ -106,5 +123,8 @@ def synthetic_batch(batch, height=600, width=1000, seed=42, label_range=(16, 21)
         labels = torch.randint(label_range[0], label_range[1], (n,), generator=g)
         t = BoxList(boxes.to(device), (width, height), mode="xyxy")
         t.add_field("labels", labels.to(device))
+        if masks is not None:
+            from ..structures.segmentation_mask import SegmentationMask
+            t.add_field("masks", SegmentationMask(_box_masks(boxes, height, width, masks, mask_dtype).to(device), (width, height), mode="mask"))
         targets.append(t)
     return images.to(device), targets

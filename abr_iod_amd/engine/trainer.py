@@ -326,7 +326,9 @@ def train_step(model_source, model_target, images, targets, optimizer, scheduler
                         ev.record()
                         tstate.prefetched["target_prefix"] = (ev, pf)
 
-    joint = need_source and JOINT_ROI_PASS and deferred is None and hasattr(model_target, "forward_joint")
+    # (an even pooler -- the Mask R-CNN C4 setting, POOLER_RESOLUTION 14 -- cannot take the joint pass: the two passes of :89-95 run instead)
+    joint_ok = getattr(getattr(model_target, "roi_heads", None), "joint_supported", True)
+    joint = need_source and JOINT_ROI_PASS and deferred is None and hasattr(model_target, "forward_joint") and joint_ok
     if joint:   # :89-95 as one pass: the distillation RoIs share the detection pass's trip through layer4
         (loss_dict_target, feature_target, _, _, rpn_output_target, target_proposals, det_pooled, target_soften_results), \
             (target_result, _, roi_align_features_target) = model_target.forward_joint(images, targets, soften_proposal,
@@ -366,7 +368,7 @@ def train_step(model_source, model_target, images, targets, optimizer, scheduler
             # wait for and the device has the proposal selection's wait to fill
             enqueue_prefetch()
         ready = getattr(soften_proposal[0], "_roi_ready", None) if (EARLY_SECOND_PASS and src is not None and soften_proposal) else None
-        joint_ov = JOINT_ROI_PASS and need_source and bool(soften_proposal) and hasattr(model_target.roi_heads, "forward_joint")
+        joint_ov = JOINT_ROI_PASS and need_source and bool(soften_proposal) and hasattr(model_target.roi_heads, "forward_joint") and joint_ok
         if joint_ov:
             # ABR_JOINT_ROI in the overlapped step: the 64 distillation RoIs per image ride along with the 512 detection RoIs through ONE
             # layer4 / predictor pass (rows of the same GEMMs) instead of a second pass of M = 4096-row launches at ~half the big pass's rate

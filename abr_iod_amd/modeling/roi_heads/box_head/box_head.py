@@ -124,6 +124,11 @@ class ResNet50Conv5ROIFeatureExtractor(nn.Module):
         return x, roi_align_features
 
 
+    @property
+    def joint_supported(self):
+        """forward_joint pools the detection RoIs on the even bins only: that equals layer4's stride-2 1x1 convs for an ODD pooled side"""
+        return self.resolution % 2 == 1 and list(self.head.layer4)[0].stride == 2
+
     def pool_soft_early(self, x, soft_proposals):
         """the distillation RoIs' pooling, ahead of the detection RoIs' (see _JointPoolFn.forward): -> (RoI table, pooled [Ks,7,7,C] NHWC)"""
         soft_rois = soft_proposals if torch.is_tensor(soft_proposals) else convert_to_roi_format(soft_proposals)
@@ -138,7 +143,9 @@ class ResNet50Conv5ROIFeatureExtractor(nn.Module):
         rows of every GEMM): the detection RoIs are pooled on the even bins only, the distillation RoIs on all 7x7 bins (ARD reads
         them) and then sub-sampled the way layer4's stride-2 1x1 convs would.  -> (head features [Kd+Ks,2048,4,4], detection
         pooled [Kd,1024,4,4], distillation pooled [Ks,1024,7,7])"""
-        assert self.resolution % 2 == 1 and list(self.head.layer4)[0].stride == 2
+        if not self.joint_supported:
+            raise NotImplementedError("the joint detection + distillation head pass needs an odd MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION (got {}) and a "
+                                      "stride-2 layer4: run the two passes (ROIBoxHead.forward, then calculate_soften_label)".format(self.resolution))
         det_rois = det_proposals if torch.is_tensor(det_proposals) else convert_to_roi_format(det_proposals)
         soft_rois, soft_ready = soft_early if soft_early is not None else (
             soft_proposals if torch.is_tensor(soft_proposals) else convert_to_roi_format(soft_proposals), None)
@@ -428,6 +435,8 @@ class ROIBoxHead(nn.Module):
         self.loss_evaluator = make_roi_box_loss_evaluator(cfg)
         self.post_processor = make_roi_box_post_processor(cfg)
         self.need_roi_features_in_training = False
+        self.keep_joint_head_features = False     # set by CombinedROIHeads when a mask head follows (forward_joint then keeps the soft rows' features)
+        self.last_joint_soft_x = None
 
     def forward(self, features, proposals, targets=None):
         """training: -> (x, proposals, (class_logits, box_regression[K,K_all,4]), loss dict, roi_align_features)
@@ -477,7 +486,11 @@ class ROIBoxHead(nn.Module):
         kd = sum(len(p) for p in proposals)
         det, soft = fused[:kd], fused[kd:]
         loss_classifier, loss_box_reg = self.loss_evaluator(K, None, fused=det)
-        first = (x[:kd], proposals, (det[:, :K], det[:, K:K + R4].reshape(-1, K, 4)),
+        x_det = x[:kd]
+        if self.keep_joint_head_features:    # (a mask head behind this one reads both parts; CombinedROIHeads takes and clears the attribute)
+            self.last_joint_soft_x = x[kd:]
+            ops.amax_carry_bound(x_det, x)   # the detection rows are a subset of the joint output's values: its amax word bounds them (f16x3 scales)
+        first = (x_det, proposals, (det[:, :K], det[:, K:K + R4].reshape(-1, K, 4)),
                  dict(loss_classifier=loss_classifier, loss_box_reg=loss_box_reg), raf_det)
         return first, (soft[:, :K], soft[:, K:K + R4].reshape(-1, K, 4), raf_soft)
 

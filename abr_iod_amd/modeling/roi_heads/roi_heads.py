@@ -1,40 +1,70 @@
-"""CombinedROIHeads (mirror of maskrcnn_benchmark/modeling/roi_heads/roi_heads.py:9-77) with the box head only:
-MASK_ON / KEYPOINT_ON are False in every configs/voc YAML (defaults.py:25,27)."""
+"""CombinedROIHeads (mirror of maskrcnn_benchmark/modeling/roi_heads/roi_heads.py:9-77): the box head and, under MODEL.MASK_ON, the C4 mask
+head behind it (mask_head/mask_head.py).  KEYPOINT_ON is False in every configs/voc YAML (defaults.py:27) and not built."""
 import torch
 
 from .box_head.box_head import build_roi_box_head
+from .mask_head.mask_head import build_roi_mask_head, check_mask_head_cfg
 
 
 class CombinedROIHeads(torch.nn.ModuleDict):
     def __init__(self, cfg, heads):
         super().__init__(heads)
         self.cfg = cfg.clone()
+        if "mask" in self:
+            self.box.keep_joint_head_features = True
+
+    @property
+    def joint_supported(self):
+        """whether forward_joint can run (an even pooler, e.g. the Mask R-CNN C4 setting 14 -> 7x7, takes the two passes: engine/trainer.py)"""
+        return self.box.feature_extractor.joint_supported
+
+    def _mask_train(self, x, detections, targets):
+        t = getattr(self.box.loss_evaluator, "_fused_targets", None)     # the fused sampler's RoI table and labels, already single device tensors
+        return self.mask(x, detections, targets, fused=t)
 
     def forward(self, features, proposals, targets=None):
         """training -> (x, detections, soften_results, losses, roi_align_features); eval -> (x, detections, results_background, [])
         (roi_heads.py:23-63)"""
         losses = {}
+        mask_on = "mask" in self
         if not self.training:
             x, detections, results_background = self.box(features, proposals, targets)
+            if mask_on:     # roi_heads.py:33-45: the mask head runs the shared extractor on the DETECTIONS
+                x, detections, _ = self.mask(features, detections, targets)
             return x, detections, results_background, []
         x, detections, soft_res, loss_box, roi_align_features = self.box(features, proposals, targets)
         losses.update(loss_box)
+        if mask_on:         # training: the box head's layer4 rows of the positives, no second ROIAlign / layer4 pass
+            _, detections, loss_mask = self._mask_train(x, detections, targets)
+            losses.update(loss_mask)
         return x, detections, soft_res, losses, roi_align_features
 
     def forward_joint(self, features, proposals, targets, soften_proposals):
         """training forward + calculate_soften_label(features, soften_proposals) sharing one head pass"""
         (x, detections, soft_res, loss_box, raf), (s_score, s_bbox, s_raf) = self.box.forward_joint(features, proposals, targets, soften_proposals)
-        return (x, detections, soft_res, dict(loss_box), raf), (s_score, s_bbox, None, s_raf)
+        losses, mask_logits = dict(loss_box), None
+        if "mask" in self:
+            _, detections, loss_mask = self._mask_train(x, detections, targets)       # x: the detection rows of the joint head pass
+            losses.update(loss_mask)
+            mask_logits = self.mask.calculate_soften_label(self.box.last_joint_soft_x)
+            self.box.last_joint_soft_x = None
+        return (x, detections, soft_res, losses, raf), (s_score, s_bbox, mask_logits, s_raf)
 
     def calculate_soften_label(self, features, proposals, targets=None):
-        """-> (soften_score, soften_bbox, mask_logits=None, roi_align_features)  (roi_heads.py:65-72)"""
-        soften_score, soften_bbox, _, roi_align_features = self.box.calculate_soften_label(features, proposals, targets)
-        return soften_score, soften_bbox, None, roi_align_features
+        """-> (soften_score, soften_bbox, mask_logits (None without a mask head), roi_align_features)  (roi_heads.py:65-72)"""
+        soften_score, soften_bbox, x, roi_align_features = self.box.calculate_soften_label(features, proposals, targets)
+        mask_logits = self.mask.calculate_soften_label(x) if "mask" in self else None
+        return soften_score, soften_bbox, mask_logits, roi_align_features
 
 
 def build_roi_heads(cfg, in_channels):
-    if cfg.MODEL.RETINANET_ON or cfg.MODEL.MASK_ON or cfg.MODEL.KEYPOINT_ON:
-        raise NotImplementedError("only the box head is on the hot path (SURVEY.md §2 rows 6b/7b)")
+    if cfg.MODEL.RETINANET_ON or cfg.MODEL.KEYPOINT_ON:
+        raise NotImplementedError("only the box and mask heads are on the hot path (SURVEY.md §2 rows 6b/7b)")
+    if cfg.MODEL.MASK_ON:
+        check_mask_head_cfg(cfg)
     if cfg.MODEL.RPN_ONLY:
         return []
-    return CombinedROIHeads(cfg, [("box", build_roi_box_head(cfg, in_channels))])
+    heads = [("box", build_roi_box_head(cfg, in_channels))]
+    if cfg.MODEL.MASK_ON:
+        heads.append(("mask", build_roi_mask_head(cfg, in_channels, heads[0][1].feature_extractor)))
+    return CombinedROIHeads(cfg, heads)

@@ -1351,3 +1351,105 @@ def rpn_distill(obj_s, reg_s, obj_t, reg_t, thr, use_bbox, want_grad=False):
                                     reg_t.stride(2), N * H * W, A, float(thr), int(bool(use_bbox)), L.ptr(loss), 1.0, L.ptr(d_o), L.ptr(d_r),
                                     A, 4 * A, L.stream()), "rpn_distill")
     return loss, d_o, d_r
+
+
+# ----------------------------------------------------------------------------------------------- mask head (csrc/mask.hip)
+def mask_compact_pos(labels, p_max):
+    """rows with labels > 0 in ascending order, nothing read back: -> (pos_rows [p_max] int64, -1 padded; pos_labels [p_max]; inv [K] =
+    position of each row in pos_rows or -1; n_pos int32 [1])"""
+    L.require_cuda(labels)
+    labels = labels.to(torch.int64).contiguous()
+    K, dev = labels.numel(), labels.device
+    pos_rows = torch.empty((p_max,), dtype=torch.int64, device=dev)
+    pos_labels = torch.empty((p_max,), dtype=torch.int64, device=dev)
+    inv = torch.empty((K,), dtype=torch.int64, device=dev)
+    n_pos = torch.empty((1,), dtype=torch.int32, device=dev)
+    L.check(L.lib().abr_mask_compact_pos(L.ptr(labels), K, int(p_max), L.ptr(pos_rows), L.ptr(pos_labels), L.ptr(inv), L.ptr(n_pos), L.stream()),
+            "mask_compact_pos")
+    return pos_rows, pos_labels, inv, n_pos
+
+
+def mask_gather_rows(x, rows):
+    """x [n, ...] contiguous fp32 -> [len(rows), ...]: row rows[p] of x, zeros where rows[p] < 0"""
+    L.require_cuda(x, rows)
+    x = L.f32c(x)
+    n_out = rows.numel()
+    row = x.numel() // max(x.shape[0], 1) if x.shape[0] else int(torch.Size(x.shape[1:]).numel())
+    out = torch.empty((n_out,) + tuple(x.shape[1:]), dtype=_f32, device=x.device)
+    L.check(L.lib().abr_mask_gather_rows(L.ptr(x), L.ptr(rows), x.shape[0], n_out, row, L.ptr(out), L.stream()), "mask_gather_rows")
+    return out
+
+
+def mask_targets(masks, gt_boxes, rois, pos_rows, M):
+    """masks: per-image [n,H,W] device tensors (all uint8 or all float32), gt_boxes: per-image [n,4]; rois [K,5]; pos_rows [P] -> [P,M,M]"""
+    L.require_cuda(rois, pos_rows, *masks)
+    dev = rois.device
+    u8 = masks[0].dtype == torch.uint8
+    for m, g in zip(masks, gt_boxes):
+        if m.dtype != (torch.uint8 if u8 else _f32) or m.dim() != 3:
+            raise RuntimeError("mask_targets: instance masks must be [n,H,W] tensors, all uint8 or all float32")
+        if m.shape[0] != g.shape[0]:
+            raise RuntimeError("mask_targets: {} masks for {} ground-truth boxes".format(m.shape[0], g.shape[0]))
+    ms = [m.contiguous() for m in masks]
+    gs = [L.f32c(g) for g in gt_boxes]
+    rois = L.f32c(rois)
+    P = pos_rows.numel()
+    out = torch.empty((P, M, M), dtype=_f32, device=dev)
+    dims = _small_table([v for m in ms for v in m.shape], torch.int32, dev)
+    mtab, gtab = _pointer_table(ms, dev), _pointer_table(gs, dev)     # (held in locals until the launch is enqueued: _evict_oldest)
+    L.check(L.lib().abr_mask_targets(L.ptr(mtab), L.ptr(dims), int(u8), L.ptr(gtab), L.ptr(rois), L.ptr(pos_rows), P, rois.shape[0], len(ms), int(M),
+                                     L.ptr(out), L.stream()), "mask_targets")
+    return out
+
+
+def mask_d2s_bias_relu(y, bias):
+    """y [P,h,w,4*Cm] (the deconvolution's GEMM, columns (dy*2+dx)*Cm + co) -> relu(depth_to_space(y) + bias) [P,2h,2w,Cm]"""
+    y, bias = L.f32c(y), L.f32c(bias)
+    P, h, w, c4 = y.shape
+    Cm = c4 // 4
+    out = torch.empty((P, 2 * h, 2 * w, Cm), dtype=_f32, device=y.device)
+    L.check(L.lib().abr_mask_d2s_bias_relu(L.ptr(y), L.ptr(bias), P, h, w, Cm, L.ptr(out), L.stream()), "mask_d2s_bias_relu")
+    return out
+
+
+def mask_d2s_bias_relu_backward(g, out):
+    """g, out [P,2h,2w,Cm] -> the GEMM output's gradient [P,h,w,4*Cm] (ReLU mask of `out` applied)"""
+    g, out = L.f32c(g), L.f32c(out)
+    P, h2, w2, Cm = out.shape
+    gy = torch.empty((P, h2 // 2, w2 // 2, 4 * Cm), dtype=_f32, device=g.device)
+    L.check(L.lib().abr_mask_d2s_bias_relu_backward(L.ptr(g), L.ptr(out), P, h2 // 2, w2 // 2, Cm, L.ptr(gy), L.stream()), "mask_d2s_bias_relu_backward")
+    return gy
+
+
+def mask_loss(logits, num_classes, labels, targets, n_pos=None, gscale=1.0, want_grad=False):
+    """logits [P,M,M,ldk] NHWC (ldk >= num_classes, % 4 == 0), labels [P] int64 (<= 0: row skipped), targets [P,M,M]; n_pos: device int32
+    count of the mean's rows (None: P) -> (loss [1], grad like logits or None)"""
+    L.require_cuda(logits, labels, targets)
+    logits, targets = L.f32c(logits), L.f32c(targets)
+    P, M1, M2, ldk = logits.shape
+    loss = _empty((1,), logits)
+    grad = torch.empty_like(logits) if want_grad else None
+    L.check(L.lib().abr_mask_loss(L.ptr(logits), ldk, int(num_classes), L.ptr(labels), L.ptr(targets), P, M1 * M2, L.ptr(n_pos), L.ptr(loss),
+                                  float(gscale), L.ptr(grad), L.stream()), "mask_loss")
+    return loss, grad
+
+
+def mask_select_sigmoid(logits, num_classes, labels):
+    """logits [D,M,M,ldk] NHWC, labels [D] -> [D,1,M,M] = sigmoid of channel labels[d]"""
+    L.require_cuda(logits, labels)
+    logits = L.f32c(logits)
+    D, M1, M2, ldk = logits.shape
+    out = torch.empty((D, 1, M1, M2), dtype=_f32, device=logits.device)
+    L.check(L.lib().abr_mask_select_sigmoid(L.ptr(logits), ldk, int(num_classes), L.ptr(labels.to(torch.int64).contiguous()), D, M1 * M2, L.ptr(out),
+                                            L.stream()), "mask_select_sigmoid")
+    return out
+
+
+def mask_paste(prob, boxes, im_h, im_w, thresh=0.5):
+    """prob [D,1,M,M], boxes [D,4] xyxy -> uint8 [D,1,im_h,im_w] (Masker, padding 1)"""
+    L.require_cuda(prob, boxes)
+    prob, boxes = L.f32c(prob), L.f32c(boxes)
+    D, M = prob.shape[0], prob.shape[-1]
+    out = torch.empty((D, 1, im_h, im_w), dtype=torch.uint8, device=prob.device)
+    L.check(L.lib().abr_mask_paste(L.ptr(prob), L.ptr(boxes), D, M, int(im_h), int(im_w), float(thresh), L.ptr(out), L.stream()), "mask_paste")
+    return out

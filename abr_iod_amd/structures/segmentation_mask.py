@@ -1,0 +1,98 @@
+"""SegmentationMask over binary instance masks (mirror of maskrcnn_benchmark/structures/segmentation_mask.py:33-179, 445-545 for
+mode="mask"): ONE tensor [n,H,W] (uint8 or float32) on any device, with the reference's crop / resize / transpose / indexing, so that BoxList
+indexing, flipping and resizing carry a "masks" field as they do there.  This is the data path's API; the training step never calls it per
+RoI -- its targets come from ops.mask_targets.  mode="poly" needs pycocotools' rasteriser and is out of scope."""
+import torch
+
+FLIP_LEFT_RIGHT = 0
+FLIP_TOP_BOTTOM = 1
+
+
+class SegmentationMask(object):
+    def __init__(self, instances, size, mode="mask"):
+        """instances: [n,H,W] tensor, [H,W] tensor, list of [H,W] tensors or a SegmentationMask; size = (width, height)"""
+        if mode == "poly":
+            raise NotImplementedError("SegmentationMask mode 'poly': polygon masks need pycocotools' rasteriser, which this build does not carry; "
+                                      "rasterise on the host and pass mode='mask'")
+        if mode != "mask":
+            raise NotImplementedError("Unknown mode: %s" % str(mode))
+        assert isinstance(size, (list, tuple)) and len(size) == 2
+        size = tuple(int(s.item()) if isinstance(s, torch.Tensor) else s for s in size)
+        if isinstance(instances, SegmentationMask):
+            masks = instances.masks
+        elif isinstance(instances, (list, tuple)):
+            masks = torch.stack(list(instances), dim=0) if len(instances) else torch.zeros((0, int(size[1]), int(size[0])), dtype=torch.uint8)
+        else:
+            masks = instances
+        if masks.dim() == 2:
+            masks = masks.unsqueeze(0)
+        assert masks.dim() == 3
+        assert masks.shape[1] == size[1], "%s != %s" % (masks.shape[1], size[1])
+        assert masks.shape[2] == size[0], "%s != %s" % (masks.shape[2], size[0])
+        if masks.dtype not in (torch.uint8, torch.float32):
+            raise TypeError("SegmentationMask holds uint8 or float32 masks, got {}".format(masks.dtype))
+        self.masks = masks
+        self.size = size
+        self.mode = mode
+
+    @property
+    def instances(self):   # (the reference wraps a BinaryMaskList with the same methods)
+        return self
+
+    def transpose(self, method):
+        if method not in (FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM):
+            raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
+        return SegmentationMask(self.masks.flip(1 if method == FLIP_TOP_BOTTOM else 2), self.size, self.mode)
+
+    def crop(self, box):
+        """box xyxy; corners through Python's round (half to even), clamped as segmentation_mask.py:99-106"""
+        assert isinstance(box, (list, tuple, torch.Tensor)), str(type(box))
+        current_width, current_height = self.size
+        xmin, ymin, xmax, ymax = [round(float(b)) for b in box]
+        assert xmin <= xmax and ymin <= ymax, str(box)
+        xmin = min(max(xmin, 0), current_width - 1)
+        ymin = min(max(ymin, 0), current_height - 1)
+        xmax = min(max(xmax, 0), current_width)
+        ymax = min(max(ymax, 0), current_height)
+        xmax = max(xmax, xmin + 1)
+        ymax = max(ymax, ymin + 1)
+        return SegmentationMask(self.masks[:, ymin:ymax, xmin:xmax], (xmax - xmin, ymax - ymin), self.mode)
+
+    def resize(self, size, *args, **kwargs):
+        try:
+            iter(size)
+        except TypeError:
+            assert isinstance(size, (int, float))
+            size = size, size
+        width, height = map(int, size)
+        assert width > 0 and height > 0
+        if len(self.masks) > 0:
+            resized = torch.nn.functional.interpolate(self.masks.unsqueeze(0).float(), size=(height, width), mode="bilinear",
+                                                      align_corners=False)[0].type_as(self.masks)
+        else:
+            resized = torch.zeros(0, height, width).type_as(self.masks)
+        return SegmentationMask(resized, (width, height), self.mode)
+
+    def convert(self, mode):
+        if mode == self.mode:
+            return self
+        return SegmentationMask(self.masks, self.size, mode)    # raises for "poly"
+
+    def to(self, device):
+        return SegmentationMask(self.masks.to(device), self.size, self.mode)
+
+    def get_mask_tensor(self):
+        return self.masks.squeeze(0)     # ([H,W] when there is one instance, segmentation_mask.py:512-517)
+
+    def __len__(self):
+        return len(self.masks)
+
+    def __getitem__(self, item):
+        return SegmentationMask(self.masks[item], self.size, self.mode)
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self[i]
+
+    def __repr__(self):
+        return "SegmentationMask(num_instances={}, image_width={}, image_height={}, mode={})".format(len(self), self.size[0], self.size[1], self.mode)

@@ -26,6 +26,11 @@ def reference_state_dict(model):
             out[name.replace("cell_anchors", "cell_anchors.0")] = b.detach().clone()
             continue
         out[name] = b.detach().clone()
+    if "mask" in getattr(model, "roi_heads", {}):
+        # the reference registers the SHARED feature extractor under the mask head too (roi_heads.py:18-21): its state_dict repeats every key
+        box, mask = "roi_heads.box.feature_extractor.", "roi_heads.mask.feature_extractor."
+        for k in [k for k in out if k.startswith(box)]:
+            out[mask + k[len(box):]] = out[k]
     return out
 
 
@@ -42,7 +47,7 @@ def load_reference_state_dict(model, sd, strict=True):
             v = sd[name].to(p.device)
             m = convs.get(id(p))
             if m is not None:
-                if v.shape[0] == p.shape[0]:
+                if v.shape[0] == p.shape[0] or getattr(m, "whole_only", False):
                     m.load_oihw(v)
                 else:
                     p[: v.shape[0]].copy_(v.permute(0, 2, 3, 1))

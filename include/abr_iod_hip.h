@@ -595,6 +595,40 @@ int abr_comm_destroy(void* comm);
  * ONE RCCL group enqueued on `stream`; returns without synchronising.  Every rank must pass the same ranges in the same order. */
 int abr_allreduce_flat(void* comm, float* flat, const int64_t* ranges_host, int n_ranges, void* stream);
 
+/* =====================================================================================================
+ * 9. Mask head (MODEL.MASK_ON, MaskRCNNC4Predictor; maskrcnn_benchmark/modeling/roi_heads/mask_head/).  The two contractions (the 2x2
+ *    stride-2 deconvolution as a GEMM with 4 * C_mid output columns, the 1x1 logits conv) run through abr_conv_forward / abr_conv_wgrad;
+ *    these are the memory-bound kernels around them (csrc/mask.hip).  NHWC activations, fp32.
+ * ===================================================================================================== */
+/* rows with labels[i] > 0, in ascending order: pos_rows / pos_labels [P_max] (-1 past the count), inv [K] (position of row i in pos_rows,
+ * or -1), n_pos [1] = min(count, P_max).  No host read-back: every consumer below takes the fixed-size, -1 padded lists. */
+int abr_mask_compact_pos(const int64_t* labels, int K, int P_max, int64_t* pos_rows, int64_t* pos_labels, int64_t* inv, int32_t* n_pos,
+                         void* stream);
+/* out[p, :] = x[rows[p], :] for p < n_out (zeros where rows[p] < 0); x [n_src, row_floats], row_floats % 4 == 0.  With rows = inv of
+ * abr_mask_compact_pos this is also the gather's backward: every row of the head output's gradient is written once, no atomics. */
+int abr_mask_gather_rows(const float* x, const int64_t* rows, int n_src, int n_out, int64_t row_floats, float* out, void* stream);
+/* project_masks_on_boxes (mask_head/loss.py:11-42) for the rows pos_rows [P_max] of the RoI table rois [K,5] (batch index, x1, y1, x2, y2):
+ * the matched instance (first maximum IoU over the image's GT boxes gt_ptrs[img] [n,4]) of mask_ptrs[img] ([n,H,W] uint8 or fp32;
+ * mask_dims [N,3] = n, H, W) is cropped to the box (corners rounded half to even, clamped as BinaryMaskList.crop) and resized to
+ * M x M (bilinear, align_corners=False; uint8 masks truncate) -> out [P_max, M, M] fp32, zeros for padding rows. */
+int abr_mask_targets(const void* const* mask_ptrs, const int32_t* mask_dims, int is_u8, const float* const* gt_ptrs, const float* rois,
+                     const int64_t* pos_rows, int P_max, int K, int N, int M, float* out, void* stream);
+/* y [P,h,w,4*Cm] (columns (dy*2+dx)*Cm + co: the deconvolution's GEMM) -> out [P,2h,2w,Cm] = relu(y + bias[co]) */
+int abr_mask_d2s_bias_relu(const float* y, const float* bias, int P, int h, int w, int Cm, float* out, void* stream);
+/* gy [P,h,w,4*Cm] = out > 0 ? g : 0 in the GEMM's column order (g, out [P,2h,2w,Cm]); the bias gradient is abr_bias_grad of gy seen as
+ * [P*h*w*4, Cm] */
+int abr_mask_d2s_bias_relu_backward(const float* g, const float* out, int P, int h, int w, int Cm, float* gy, void* stream);
+/* mask_head/loss.py:102-128: mean over (rows with 0 < labels[p] < Kc) x MM of BCE-with-logits(logits[p, :, labels[p]], targets[p, :]);
+ * logits [P,MM,ldk] (ldk % 4 == 0 >= Kc), targets [P,MM].  n_pos (device, optional): the mean's row count (NULL: P); 0 gives loss 0 and
+ * zero gradients.  grad (optional) [P,MM,ldk] is written whole.  The sum is a fixed tree: two runs agree bit for bit. */
+int abr_mask_loss(const float* logits, int ldk, int Kc, const int64_t* labels, const float* targets, int P, int MM, const int32_t* n_pos,
+                  float* loss_out, float gscale, float* grad, void* stream);
+/* mask_head/inference.py:38-45: out [D,MM] = sigmoid(logits[d, :, labels[d]]) */
+int abr_mask_select_sigmoid(const float* logits, int ldk, int Kc, const int64_t* labels, int D, int MM, float* out, void* stream);
+/* Masker / paste_mask_in_image (inference.py:91-159, padding 1) for all detections of one image: prob [D,M,M], boxes [D,4] xyxy ->
+ * out uint8 [D,im_h,im_w] (1 where the resized mask exceeds thresh >= 0) */
+int abr_mask_paste(const float* prob, const float* boxes, int D, int M, int im_h, int im_w, float thresh, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

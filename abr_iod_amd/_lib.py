@@ -169,6 +169,9 @@ _SIGS = {
     "abr_mask_loss": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _f, _vp, _vp]),
     "abr_mask_select_sigmoid": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "abr_mask_paste": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "abr_mask_pack_bits": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_mask_resize_pack_bits": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "abr_mask_pair_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp]),
 }
 
 # every symbol include/abr_iod_hip.h declares (tests/test_abi.py checks the library exports them all)

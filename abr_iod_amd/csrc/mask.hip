@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mask_bilinear.h"
 
 namespace {
 
@@ -76,26 +77,6 @@ __device__ __forceinline__ float mask_box_iou(const float4 g, const float4 b) {
     const float w = fmaxf(rx - lx + 1, 0.f), h = fmaxf(ry - ly + 1, 0.f);
     const float inter = w * h;
     return inter / (area1 + area2 - inter);
-}
-
-// torch's bilinear source index, align_corners=False: (index of the first tap, of the second tap, weight of the second tap).  The operation
-// order is the one the reference's CPU run shows (tests/golden/mask_head.npz is reproduced bit for bit by it and by no other): the source
-// coordinate is ONE fused multiply-add, the four tap weights are multiplied first and the taps accumulated in a chain of fused multiply-adds
-// -- so a uint8 target pixel whose four taps are all 1 can still truncate to 0 where the rounded weights sum to 1 - 2^-24, as it does there.
-#pragma clang fp contract(off)
-__device__ __forceinline__ void bilinear_tap(const float scale, const int dst, const int in_size, int& i0, int& i1, float& l1) {
-    float s = __fmaf_rn(scale, (float)dst + 0.5f, -0.5f);
-    if (s < 0.f) s = 0.f;
-    i0 = min((int)floorf(s), in_size - 1);
-    l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-}
-
-#pragma clang fp contract(off)
-__device__ __forceinline__ float bilinear_mix(const float v00, const float v01, const float v10, const float v11, const float lx, const float ly) {
-    const float wx0 = 1.f - lx, wy0 = 1.f - ly;
-    const float w00 = wy0 * wx0, w01 = wy0 * lx, w10 = ly * wx0, w11 = ly * lx;
-    return __fmaf_rn(w11, v11, __fmaf_rn(w10, v10, __fmaf_rn(w01, v01, w00 * v00)));
 }
 
 __device__ __forceinline__ int round_to_int(const float v) {   // Python round() of a float: half to even

@@ -72,9 +72,29 @@ class EvalRangeGuard(object):
         return out
 
 
-def compute_on_dataset(model, data_loader, device, timer=None, guard=None):
+def _pack_masks(output, img_ids, dataset):
+    """each image's pasted masks [n,1,H,W] -> PackedMasks at the image's ORIGINAL size, resized and packed on the device (the reference
+    wraps output[0] alone in a SegmentationMask, inference.py:70-79, and resizes on the host inside the metric).  An output whose "mask"
+    field is not a pasted uint8 tensor is left as it is: the metric names what is wrong with it."""
+    from .. import ops
+    from ..structures.segmentation_mask import PackedMasks
+    packed = []
+    for img_id, o in zip(img_ids, output):
+        m = o.get_field("mask") if o.has_field("mask") else None
+        if isinstance(m, torch.Tensor) and m.dtype == torch.uint8 and m.dim() == 4:
+            info = dataset.get_img_info(img_id)
+            width, height = int(info["width"]), int(info["height"])
+            new = o.copy_with_fields([f for f in o.fields() if f != "mask"])
+            new.add_field("mask", PackedMasks(ops.mask_resize_pack_bits(m[:, 0], height, width), (width, height)))
+            o = new
+        packed.append(o)
+    return packed
+
+
+def compute_on_dataset(model, data_loader, device, timer=None, guard=None, pack_masks=False):
     """-> ({image id: BoxList on cpu}, {image id: background BoxList})  (inference.py:43-109).
-    Batches are (images, targets, img_ids) or the reference's 4-tuple (images, targets, proposals, img_ids)."""
+    Batches are (images, targets, img_ids) or the reference's 4-tuple (images, targets, proposals, img_ids).
+    pack_masks: a "mask" field of pasted masks crosses to the host as PackedMasks at the dataset's original image size."""
     model.eval()
     results, results_background = {}, {}
     if guard is None:
@@ -89,6 +109,8 @@ def compute_on_dataset(model, data_loader, device, timer=None, guard=None):
             if timer is not None:
                 torch.cuda.synchronize()
                 timer["total"] = timer.get("total", 0.0) + time.perf_counter() - t0
+        if pack_masks:
+            output = _pack_masks(output, img_ids, data_loader.dataset)
         output = [o.to("cpu") for o in output]
         results.update({i: o for i, o in zip(img_ids, output)})
         # the reference keeps ONE background list per batch, keyed by the batch's first image id (inference.py:107)
@@ -119,7 +141,8 @@ def _accumulate_predictions_from_multiple_gpus(predictions_per_gpu):
 def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=False, device="cuda", expected_results=(),
               expected_results_sigma_tol=4, output_folder=None, external_proposal=False, alphabetical_order=True,
               summary_writer=None, save_predictions=False):
-    """inference.py:163-213.  Returns the metric dict on rank 0 ({"ap", "map"} for VOC), None elsewhere."""
+    """inference.py:163-213.  Returns the metric dict on rank 0 ({"ap", "map"} for VOC; {"mask", "box"} when iou_types holds "segm"),
+    None elsewhere."""
     if external_proposal:
         raise NotImplementedError("external (edge-box) proposals are outside the RPN path this package implements")
     logger = logging.getLogger("maskrcnn_benchmark_target_model.inference")
@@ -128,7 +151,7 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     logger.info("Start evaluation on {} dataset({} images).".format(dataset_name, len(dataset)))
     timer = {}
     t0 = time.perf_counter()
-    predictions, _background = compute_on_dataset(model, data_loader, torch.device(device), timer)
+    predictions, _background = compute_on_dataset(model, data_loader, torch.device(device), timer, pack_masks="segm" in iou_types)
     synchronize()
     total = time.perf_counter() - t0
     world = get_world_size()

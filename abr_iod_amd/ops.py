@@ -1453,3 +1453,60 @@ def mask_paste(prob, boxes, im_h, im_w, thresh=0.5):
     out = torch.empty((D, 1, im_h, im_w), dtype=torch.uint8, device=prob.device)
     L.check(L.lib().abr_mask_paste(L.ptr(prob), L.ptr(boxes), D, M, int(im_h), int(im_w), float(thresh), L.ptr(out), L.stream()), "mask_paste")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- mask evaluation (csrc/mask_eval.hip)
+def mask_words_per_row(width):
+    return (int(width) + 63) // 64
+
+
+def mask_pack_bits(masks):
+    """masks [n,H,W] uint8 or float32 -> int64 [n,H,ceil(W/64)]: bit x % 64 of word x // 64 is set iff masks[i,y,x] == 1"""
+    L.require_cuda(masks)
+    if masks.dim() != 3 or masks.dtype not in (torch.uint8, _f32):
+        raise RuntimeError("mask_pack_bits: expected [n,H,W] uint8 or float32 masks, got {} {}".format(tuple(masks.shape), masks.dtype))
+    masks = masks.contiguous()
+    n, H, W = masks.shape
+    bits = torch.empty((n, H, mask_words_per_row(W)), dtype=torch.int64, device=masks.device)
+    L.check(L.lib().abr_mask_pack_bits(L.ptr(masks), int(masks.dtype == torch.uint8), n, H, W, L.ptr(bits), L.stream()), "mask_pack_bits")
+    return bits
+
+
+def mask_resize_pack_bits(masks, height, width):
+    """uint8 masks [n,Hs,Ws] -> the packed bits [n,height,ceil(width/64)] of their bilinear resize (align_corners=False, truncated to
+    uint8, == 1): what BinaryMaskList.resize((width, height)) followed by mask_pack_bits gives, without the resized image"""
+    L.require_cuda(masks)
+    if masks.dim() != 3 or masks.dtype != torch.uint8:
+        raise RuntimeError("mask_resize_pack_bits: expected [n,H,W] uint8 masks, got {} {}".format(tuple(masks.shape), masks.dtype))
+    masks = masks.contiguous()
+    n, Hs, Ws = masks.shape
+    bits = torch.empty((n, int(height), mask_words_per_row(width)), dtype=torch.int64, device=masks.device)
+    L.check(L.lib().abr_mask_resize_pack_bits(L.ptr(masks), n, Hs, Ws, int(height), int(width), L.ptr(bits), L.stream()), "mask_resize_pack_bits")
+    return bits
+
+
+def mask_pair_counts(pred_bits, gt_bits, width, pred_labels=None, gt_labels=None):
+    """pred_bits [P,H,Wq], gt_bits [T,H,Wq] (mask_pack_bits of masks `width` wide) -> (inter [P,T], area_p [P], area_t [T]) int32 pixel
+    counts; with both label vectors, pairs of different labels are 0 and are not read"""
+    L.require_cuda(pred_bits, gt_bits)
+    if pred_bits.dtype != torch.int64 or gt_bits.dtype != torch.int64 or pred_bits.dim() != 3 or pred_bits.shape[1:] != gt_bits.shape[1:]:
+        raise RuntimeError("mask_pair_counts: expected int64 [P,H,Wq] and [T,H,Wq] of one image size")
+    if (pred_labels is None) != (gt_labels is None):
+        raise RuntimeError("mask_pair_counts: labels must be given for both sides or neither")
+    pred_bits, gt_bits = pred_bits.contiguous(), gt_bits.contiguous()
+    P, H, Wq = pred_bits.shape
+    T, dev = gt_bits.shape[0], pred_bits.device
+    if P == 0 or T == 0:
+        z = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)    # noqa: E731
+        return z(P, T), z(P), z(T)
+    if pred_labels is not None:
+        pred_labels = pred_labels.to(device=dev, dtype=torch.int64).contiguous()
+        gt_labels = gt_labels.to(device=dev, dtype=torch.int64).contiguous()
+        if pred_labels.numel() != P or gt_labels.numel() != T:
+            raise RuntimeError("mask_pair_counts: {} / {} labels for {} / {} masks".format(pred_labels.numel(), gt_labels.numel(), P, T))
+    inter = torch.empty((P, T), dtype=torch.int32, device=dev)
+    area_p = torch.empty((P,), dtype=torch.int32, device=dev)
+    area_t = torch.empty((T,), dtype=torch.int32, device=dev)
+    L.check(L.lib().abr_mask_pair_counts(L.ptr(pred_bits), L.ptr(gt_bits), L.ptr(pred_labels), L.ptr(gt_labels), P, T, H, int(width), H * Wq,
+                                         L.ptr(inter), L.ptr(area_p), L.ptr(area_t), L.stream()), "mask_pair_counts")
+    return inter, area_p, area_t

@@ -96,3 +96,52 @@ class SegmentationMask(object):
 
     def __repr__(self):
         return "SegmentationMask(num_instances={}, image_width={}, image_height={}, mode={})".format(len(self), self.size[0], self.size[1], self.mode)
+
+
+class PackedMasks(object):
+    """Binary instance masks as bits: `bits` int64 [n,H,ceil(W/64)], bit x % 64 of word x // 64 of row y set iff the pixel is 1
+    (ops.mask_pack_bits), and size = (width, height).  What the test loop keeps per image when mask AP is asked for (engine/inference.py):
+    one eighth of the uint8 masks' bytes, already at the original image size and ready for ops.mask_pair_counts.  A BoxList carries it as a
+    non-tensor field like SegmentationMask."""
+
+    def __init__(self, bits, size):
+        size = tuple(int(s) for s in size)
+        assert bits.dim() == 3 and bits.dtype == torch.int64, "PackedMasks holds int64 [n,H,Wq] words"
+        assert bits.shape[1] == size[1] and bits.shape[2] == (size[0] + 63) // 64, "{} does not pack masks of size {}".format(tuple(bits.shape), size)
+        self.bits = bits
+        self.size = size
+        self.mode = "packed"
+
+    @property
+    def instances(self):
+        return self
+
+    def to(self, device):
+        return PackedMasks(self.bits.to(device), self.size)
+
+    def resize(self, size, *args, **kwargs):
+        try:
+            size = tuple(int(s) for s in size)
+        except TypeError:
+            size = (int(size), int(size))
+        if size != self.size:
+            raise ValueError("PackedMasks of size {} cannot be resized to {}: bits are packed at their final size (resize the "
+                             "SegmentationMask first, or pack with ops.mask_resize_pack_bits)".format(self.size, size))
+        return self
+
+    def unpack(self):
+        """-> uint8 [n,H,W] (tests and debugging)"""
+        n, H, Wq = self.bits.shape
+        shifts = torch.arange(64, dtype=torch.int64, device=self.bits.device)
+        px = (self.bits.unsqueeze(-1) >> shifts) & 1
+        return px.reshape(n, H, Wq * 64)[:, :, : self.size[0]].to(torch.uint8)
+
+    def __len__(self):
+        return self.bits.shape[0]
+
+    def __getitem__(self, item):
+        bits = self.bits[item]
+        return PackedMasks(bits.unsqueeze(0) if bits.dim() == 2 else bits, self.size)
+
+    def __repr__(self):
+        return "PackedMasks(num_instances={}, image_width={}, image_height={})".format(len(self), self.size[0], self.size[1])

@@ -629,6 +629,24 @@ int abr_mask_select_sigmoid(const float* logits, int ldk, int Kc, const int64_t*
  * out uint8 [D,im_h,im_w] (1 where the resized mask exceeds thresh >= 0) */
 int abr_mask_paste(const float* prob, const float* boxes, int D, int M, int im_h, int im_w, float thresh, uint8_t* out, void* stream);
 
+/* =====================================================================================================
+ * 10. Instance-mask evaluation (VOC box and mask AP; maskrcnn_benchmark/data/datasets/evaluation/voc/voc_eval_inst.py:89-105): the pixel
+ *     counts behind masklist_iou as integer popcounts over bit-packed masks (csrc/mask_eval.hip).  Packed form of masks [n,H,W]:
+ *     [n, H, Wq] 64-bit words, Wq = ceil(W / 64); bit x % 64 of word x / 64 of row y is set iff mask[i,y,x] == 1 (a 255 is not "set",
+ *     as in the reference's test); the tail bits of a row's last word are zero.
+ * ===================================================================================================== */
+/* masks [n,H,W] uint8 (is_u8) or fp32 -> bits [n,H,Wq] */
+int abr_mask_pack_bits(const void* masks, int is_u8, int n, int H, int W, uint64_t* bits, void* stream);
+/* The bits of BinaryMaskList.resize((Wd,Hd)) (structures/segmentation_mask.py:113-135) of uint8 masks [n,Hs,Ws]: bilinear with
+ * align_corners=False in fp32, truncated to uint8, compared with 1 -- bit for bit what torch computes on the CPU; the resized image is
+ * never stored.  Equal sizes are abr_mask_pack_bits. */
+int abr_mask_resize_pack_bits(const uint8_t* masks, int n, int Hs, int Ws, int Hd, int Wd, uint64_t* bits, void* stream);
+/* pred_bits [P,words], gt_bits [T,words] (words = H * Wq) -> inter [P,T] = popcount(pred & gt), area_p [P], area_t [T], all int32, one
+ * launch.  With pred_labels [P] and gt_labels [T] (both or neither) a pair whose labels differ gets inter = 0 and is not read.  P == 0 or
+ * T == 0: success, nothing launched or written. */
+int abr_mask_pair_counts(const uint64_t* pred_bits, const uint64_t* gt_bits, const int64_t* pred_labels, const int64_t* gt_labels, int P, int T,
+                         int H, int W, int64_t words, int32_t* inter, int32_t* area_p, int32_t* area_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

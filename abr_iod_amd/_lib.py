@@ -125,6 +125,7 @@ _SIGS = {
     "abr_conv_tail64_forward": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp]),
     "abr_conv_wgrad": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp]),
     "abr_conv_wino_v_floats": (_i64, [C.POINTER(ConvDesc)]),
+    "abr_conv_route_info": (_i, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
     "abr_conv_packed_bytes": (_i64, [_i64, _i64]),
     "abr_conv_pack_weights": (_i, [_vp, _i64, _i, _vp, _vp]),
     "abr_conv_dgrad_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -1700,6 +1700,13 @@ static bool wino_conv(const ConvP& p, const abr::ConvRoute& r, const float* x, c
 
 extern "C" int64_t abr_conv_wino_v_floats(const abr_conv_desc* d) { return d ? abr::conv_route(*d).v_floats : 0; }
 
+extern "C" int abr_conv_route_info(const abr_conv_desc* d, int32_t out[4]) {
+    ABR_REQUIRE(d && out, "conv_route_info: null pointer");
+    const abr::ConvRoute r = abr::conv_route(*d);
+    out[0] = r.math; out[1] = r.fwd_wino ? 1 : 0; out[2] = r.wgrad_wino ? 1 : 0; out[3] = r.wgrad_math;
+    return ABR_OK;
+}
+
 extern "C" int abr_conv_forward(const abr_conv_desc* d, const float* x, const float* w, float* out, void* stream) {
     ABR_REQUIRE(d && x && w && out, "conv_forward: null pointer");
     ABR_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->R > 0 && d->S > 0 && d->stride > 0,

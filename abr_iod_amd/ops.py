@@ -427,6 +427,16 @@ def conv_desc(x_shape, w_shape, stride, pad, scale=None, bias=None, residual=Non
     return d
 
 
+def conv_route_info(x_shape, w_shape, stride, pad, scale=None, bias=None, residual=None, mask=None, relu=False,
+                    out_hw=None, out_stride=(1, 1), math=MATH_F32):
+    """What the library decided for conv_desc(the same arguments) (abr_conv_route_info; host only, no device call): (the arithmetic the forward
+    pass runs in, forward takes Winograd, weight gradient takes Winograd, the weight gradient's arithmetic)."""
+    d = conv_desc(tuple(x_shape), tuple(w_shape), stride, pad, scale, bias, residual, mask, relu, out_hw, out_stride, math)
+    out = (C.c_int32 * 4)()
+    L.check(L.lib().abr_conv_route_info(C.byref(d), out), "conv_route_info")
+    return int(out[0]), bool(out[1]), bool(out[2]), int(out[3])
+
+
 KEEP_WINO_V = os.environ.get("ABR_WINOGRAD_KEEP_V", "1") != "0"
 
 

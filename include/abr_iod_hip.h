@@ -378,6 +378,10 @@ int64_t abr_conv_cache_bytes(void);
  * Winograd F(4x4,3x3) path for this descriptor (wide stride-1 pad-1 3x3, no residual / scatter; fp32 math, or bf16x6 / f16x3 with
  * Cout % 32 == 0), else 0 */
 int64_t abr_conv_wino_v_floats(const abr_conv_desc* d_host);
+/* What the library decided for this descriptor (host only, no device call): out = { the arithmetic the forward pass runs in (ABR_MATH_*: fp32 for
+ * a split arithmetic with Cin % 32 != 0 and for bf16 with Cin % 64 != 0), 1 if abr_conv_forward takes Winograd F(4x4,3x3), 1 if abr_conv_wgrad
+ * does, the arithmetic of the weight gradient }.  The forward entries follow d_host's residual pointer and scatter geometry. */
+int abr_conv_route_info(const abr_conv_desc* d_host, int32_t out[4]);
 /* Fragment-packed bf16x3 planes of an fp32 matrix w [rows][K] (K % 16 == 0; a conv weight: rows = Cout, K = R*S*Cin) for
  * abr_conv_desc::w_planes.  Exact three-way split x = p0 + p1 + p2 (p0 = bf16(x), p1 = bf16(x - p0), p2 = bf16(x - p0 - p1), RNE), stored in
  * the order the bf16 MFMA consumes it: chunk (nb, ks, pl) = 64 lanes x 16 B at byte (((nb * K/16 + ks) * 3 + pl) * 64 + lane) * 16, lane l

@@ -69,3 +69,54 @@ def test_winograd_v_size_follows_the_forward_route():
         assert v_floats(x_shape, w_shape, ops.MATH_BF16) == 0, x_shape
     for math in (ops.MATH_BF16X6, ops.MATH_F16X3):
         assert v_floats((2, 21, 10, 128), (136, 3, 3, 128), math) == 0, math
+
+
+def test_conv_route_table():
+    """abr_conv_route_info (host only) returns what abr::conv_route decided; this pins the table in conv_route's own comments."""
+    from abr_iod_amd import ops
+    F32, BF16, X6, H3, F16 = ops.MATH_F32, ops.MATH_BF16, ops.MATH_BF16X6, ops.MATH_F16X3, ops.MATH_F16
+    import torch
+    res = torch.zeros(4)      # (the route looks at the pointer only)
+
+    def route(x_shape, w_shape, stride=1, pad=1, **kw):
+        return ops.conv_route_info(x_shape, w_shape, stride, pad, **kw)
+
+    wide = ((2, 21, 10, 256), (256, 3, 3, 256))
+    # wide stride-1 pad-1 3x3: Winograd forward and weight gradient in every full-precision arithmetic ...
+    for m in (F32, X6, H3):
+        assert route(*wide, math=m) == (m, True, True, m), m
+    # ... bf16 and f16 never (a transform of rounded operands is another function than the mode's definition)
+    for m in (BF16, F16):
+        assert route(*wide, math=m) == (m, False, False, m), m
+    # not wide, not stride 1, not pad 1, not 3x3: direct
+    for x_shape, w_shape, st, pad in [((2, 21, 10, 64), (256, 3, 3, 64), 1, 1), ((2, 21, 10, 256), (64, 3, 3, 256), 1, 1),
+                                      ((2, 21, 10, 256), (256, 3, 3, 256), 2, 1), ((2, 21, 10, 256), (256, 3, 3, 256), 1, 0),
+                                      ((2, 21, 10, 256), (256, 1, 1, 256), 1, 0)]:
+        for m in (F32, X6, H3):
+            assert route(x_shape, w_shape, st, pad, math=m)[1:3] == (False, False), (x_shape, w_shape, st, pad, m)
+    # a residual epilogue: forward direct, weight gradient still Winograd
+    for m in (F32, X6, H3):
+        assert route(*wide, residual=res, math=m) == (m, False, True, m), m
+    # Cout % 32 != 0 under the split arithmetics (U's 36 matrices are packed as one whose 32-row blocks must not straddle two): forward direct;
+    # fp32 Winograd takes any Cout % 4 == 0
+    for cout in (132, 136, 200):
+        for m in (X6, H3):
+            assert route((2, 21, 10, 128), (cout, 3, 3, 128), math=m) == (m, False, True, m), (cout, m)
+        assert route((2, 21, 10, 128), (cout, 3, 3, 128), math=F32) == (F32, True, True, F32), cout
+    # Cout % 4 != 0: forward direct in every arithmetic
+    for m in (F32, X6, H3):
+        assert route((2, 21, 10, 128), (129, 3, 3, 128), math=m)[1] is False, m
+    # Cin % 32 != 0: forward direct (and in fp32 under a split arithmetic); the weight gradient asks for Cin % 4 == 0 only and keeps its arithmetic
+    assert route((2, 21, 10, 132), (128, 3, 3, 132), math=F32) == (F32, False, True, F32)
+    for m in (X6, H3):
+        assert route((2, 21, 10, 132), (128, 3, 3, 132), math=m) == (F32, False, True, m), m
+    # Cin = 4 (the stem) under a split arithmetic or f16: fp32
+    for m in (X6, H3, F16):
+        assert route((2, 64, 64, 4), (64, 7, 7, 4), 2, 3, math=m)[0] == F32, m
+    # bf16 covers the Cin % 64 == 0 layers: elsewhere forward and weight gradient run in fp32 (and may then take Winograd)
+    assert route((2, 21, 10, 128), (128, 3, 3, 128), math=BF16) == (BF16, False, False, BF16)
+    assert route((2, 21, 10, 160), (160, 3, 3, 160), math=BF16) == (F32, True, True, F32)
+    assert route((2, 21, 10, 96), (64, 1, 1, 96), 1, 0, math=BF16) == (F32, False, False, F32)
+    # a scattered output (the input gradient of a strided conv): direct
+    for m in (F32, X6, H3):
+        assert route(*wide, out_hw=(42, 20), out_stride=(2, 2), math=m)[1] is False, m

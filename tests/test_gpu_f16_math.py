@@ -12,7 +12,8 @@ FrozenBN -> + identity (1x1 (stride) -> FrozenBN when the width changes) -> ReLU
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
+
+from conv_ref import conv64 as _conv64, q16 as _q, wgrad64 as _wgrad64
 
 pytestmark = pytest.mark.gpu
 
@@ -22,33 +23,6 @@ EPS = 2.0 ** -24
 def _gen(seed):
     g = torch.Generator(device="cuda").manual_seed(seed)
     return (lambda *s: torch.randn(*s, device="cuda", generator=g)), (lambda *s: torch.rand(*s, device="cuda", generator=g))
-
-
-def _q(t, per_row=False):
-    """s q16(t / s) in float64 on the CPU; per_row: one scale per output row of a [Cout, R, S, Cin] weight"""
-    t64 = t.detach().double().cpu()
-    a = t64.abs().flatten(1).amax(1).view(-1, *([1] * (t64.dim() - 1))) if per_row else t64.abs().max()
-    _, e = torch.frexp(a)                                   # a = m 2^e, m in [0.5, 1)
-    s = torch.where(a > 0, torch.exp2((e - 15).double()), torch.ones_like(a, dtype=torch.float64))
-    return (t64 / s).to(torch.float16).double() * s
-
-
-def _conv64(x, w, stride, pad):
-    """NHWC x, OHWI w (float64) -> NHWC"""
-    return F.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), stride=stride, padding=pad).permute(0, 2, 3, 1)
-
-
-def _wgrad64(x, gy, R, stride, pad):
-    """dW[n, r, s, c] = sum_{b, ho, wo} gy[b, ho, wo, n] x[b, ho * stride - pad + r, wo * stride - pad + s, c] (NHWC, float64)"""
-    Ho, Wo = gy.shape[1], gy.shape[2]
-    xp = F.pad(x, (0, 0, pad, pad, pad, pad))
-    out = torch.zeros(gy.shape[3], R, R, x.shape[3], dtype=torch.float64)
-    g2 = gy.reshape(-1, gy.shape[3])
-    for r in range(R):
-        for s in range(R):
-            xs = xp[:, r:r + stride * (Ho - 1) + 1:stride, s:s + stride * (Wo - 1) + 1:stride, :].reshape(-1, x.shape[3])
-            out[:, r, s, :] = g2.t() @ xs
-    return out
 
 
 def _err(y, y64, scale):

@@ -173,6 +173,10 @@ _SIGS = {
     "abr_mask_pack_bits": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "abr_mask_resize_pack_bits": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "abr_mask_pair_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp]),
+    "abr_rle_decode_workspace_bytes": (_i64, [_i, _i64]),
+    "abr_rle_decode": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "abr_rle_encode_workspace_bytes": (_i64, [_i, _i, _i]),
+    "abr_rle_encode": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
 }
 
 # every symbol include/abr_iod_hip.h declares (tests/test_abi.py checks the library exports them all)

@@ -1,5 +1,6 @@
 import logging
 
+from .coco_results import prepare_for_coco_segmentation  # noqa: F401
 from .voc_eval import do_voc_evaluation
 from .voc_eval_inst import do_voc_evaluation_inst
 

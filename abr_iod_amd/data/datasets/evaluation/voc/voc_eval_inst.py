@@ -54,10 +54,15 @@ def image_mask_counts(prediction, gt_boxlist, size, device=None):
         held = field.bits if hasattr(field, "bits") else (field.masks if hasattr(field, "masks") else field)
         device = held.device if held.is_cuda else torch.device("cuda")
     pred_bits = _prediction_bits(field, size, device)
-    gt_masks = gt_boxlist.get_field("masks").instances.masks
-    assert tuple(gt_masks.shape[1:]) == (int(size[1]), int(size[0])), "ground-truth masks {} are not at the image's size {}".format(
-        tuple(gt_masks.shape), size)
-    gt_bits = ops.mask_pack_bits(gt_masks.to(device))
+    gt = gt_boxlist.get_field("masks").instances
+    if hasattr(gt, "bits"):      # PackedMasks (decoded from run-length annotations straight into bits)
+        assert tuple(gt.size) == (int(size[0]), int(size[1])), "ground-truth masks {} are not at the image's size {}".format(gt, size)
+        gt_bits = gt.bits.to(device)
+    else:
+        gt_masks = gt.masks
+        assert tuple(gt_masks.shape[1:]) == (int(size[1]), int(size[0])), "ground-truth masks {} are not at the image's size {}".format(
+            tuple(gt_masks.shape), size)
+        gt_bits = ops.mask_pack_bits(gt_masks.to(device))
     inter, area_p, area_t = ops.mask_pair_counts(pred_bits, gt_bits, size[0], prediction.get_field("labels"), gt_boxlist.get_field("labels"))
     return {"inter": inter.cpu().numpy().astype(np.int64), "area_p": area_p.cpu().numpy().astype(np.int64),
             "area_t": area_t.cpu().numpy().astype(np.int64)}

@@ -1520,3 +1520,126 @@ def mask_pair_counts(pred_bits, gt_bits, width, pred_labels=None, gt_labels=None
     L.check(L.lib().abr_mask_pair_counts(L.ptr(pred_bits), L.ptr(gt_bits), L.ptr(pred_labels), L.ptr(gt_labels), P, T, H, int(width), H * Wq,
                                          L.ptr(inter), L.ptr(area_p), L.ptr(area_t), L.stream()), "mask_pair_counts")
     return inter, area_p, area_t
+
+
+# ----------------------------------------------------------------------------------------------- COCO run-length masks (csrc/rle.hip)
+_RLE_ERRORS = {-1: "the last value of the counts string is cut short", -2: "a character of the counts string is outside [48, 111]",
+               -3: "a value of the counts string is longer than 7 characters or outside int32", -4: "a negative run length"}
+
+
+def _rle_payload(rles, h, w):
+    """checks each dict's "size" and -> (compressed?, [bytes or int32 array per instance])"""
+    import numpy as np
+    from .structures.rle import RLEError, counts_to_string
+    items = []
+    for i, r in enumerate(rles):
+        if not isinstance(r, dict) or "counts" not in r or "size" not in r:
+            raise RLEError("RLE instance {}: expected a dict with 'size' and 'counts', got {!r}".format(i, type(r).__name__))
+        if tuple(int(v) for v in r["size"]) != (h, w):
+            raise RLEError("RLE instance {}: its size {} is not the expected (h, w) = {}".format(i, list(r["size"]), (h, w)))
+        c = r["counts"]
+        items.append(c.encode("ascii") if isinstance(c, str) else (bytes(c) if isinstance(c, (bytes, bytearray)) else [int(v) for v in c]))
+    compressed = any(isinstance(c, bytes) for c in items)
+    if compressed:        # (a list among strings: one form per call, so it is written as a string here)
+        items = [c if isinstance(c, bytes) else counts_to_string(c).encode("ascii") for c in items]
+        return True, [np.frombuffer(c, np.uint8) for c in items]
+    for i, c in enumerate(items):
+        if any(v < 0 or v > 0x7fffffff for v in c):
+            raise RLEError("RLE instance {}: a negative run length".format(i) if min(c) < 0 else "RLE instance {}: a run length outside int32".format(i))
+    return False, [np.asarray(c, np.int32).reshape(-1) for c in items]
+
+
+def rle_decode(rles, size, device="cuda", packed=False, out=None):
+    """list of COCO RLE dicts of one image -> its instance masks on `device`: uint8 [n,h,w] of 0 / 1, or with packed=True the int64
+    [n,h,ceil(w/64)] words of mask_pack_bits (the bytes are never written).  size = (h, w) as in the dicts' "size".  counts may be str, bytes
+    or a list of ints.  One upload (offsets + counts), one launch chain, one [n]-element read-back of the sums that tells a malformed
+    annotation: structures.rle.RLEError names the instance.  `out`: a contiguous tensor of the result's shape and dtype to decode into.
+    device "cpu": the host codec (structures/rle.py)."""
+    import numpy as np
+    from .structures.rle import RLEError
+    h, w = int(size[0]), int(size[1])
+    device = torch.device(device)
+    n = len(rles)
+    shape = (n, h, mask_words_per_row(w)) if packed else (n, h, w)
+    dtype = torch.int64 if packed else torch.uint8
+    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device.type != device.type):
+        raise RuntimeError("rle_decode: `out` must be a contiguous {} tensor of shape {} on {}".format(dtype, shape, device))
+    if device.type == "cpu":
+        from .structures import rle as host
+        m = torch.from_numpy(host.decode(list(rles), (h, w)))
+        if packed:
+            px = torch.zeros((n, h, shape[2] * 64), dtype=torch.int64)
+            px[:, :, :w] = m
+            m = (px.reshape(n, h, shape[2], 64) << torch.arange(64, dtype=torch.int64)).sum(-1)
+        return m if out is None else out.copy_(m)
+    if h <= 0 or w <= 0 or h * w >= 2 ** 31:
+        raise RuntimeError("rle_decode: bad size {}".format((h, w)))
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    if n == 0:
+        return out
+    compressed, items = _rle_payload(rles, h, w)
+    lens = np.array([len(c) for c in items], np.int64)
+    offsets = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    n_items = int(offsets[-1])
+    item = 1 if compressed else 4
+    host = np.zeros(8 * (n + 1) + (n_items * item + 7) // 8 * 8, np.uint8)          # offsets, then the items: ONE upload
+    host[: 8 * (n + 1)] = offsets.view(np.uint8)
+    if n_items:
+        host[8 * (n + 1): 8 * (n + 1) + n_items * item] = np.concatenate(items).view(np.uint8)
+    with torch.cuda.device(device):
+        buf = torch.from_numpy(host).to(device)
+        payload = buf[8 * (n + 1):]
+        ws_bytes = L.lib().abr_rle_decode_workspace_bytes(n, n_items)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+        totals = torch.empty((n,), dtype=torch.int64, device=device)
+        L.check(L.lib().abr_rle_decode(L.ptr(payload) if compressed else None, None if compressed else L.ptr(payload), L.ptr(buf), n, n_items, h, w,
+                                       None if packed else L.ptr(out), L.ptr(out) if packed else None, L.ptr(totals), L.ptr(ws), ws_bytes, L.stream()),
+                "rle_decode")
+        got = totals.cpu().tolist()
+    for i, t in enumerate(got):
+        if t != h * w:
+            raise RLEError("RLE instance {}: {}".format(i, _RLE_ERRORS.get(t, "its counts sum to {}, not to h * w = {}".format(t, h * w))))
+    return out
+
+
+def rle_encode(masks, width=None):
+    """uint8 [n,h,w] device masks (a pixel is set iff it == 1), a PackedMasks, or int64 packed words [n,h,ceil(width/64)] with `width` ->
+    list of {"size": [h, w], "counts": str}, encoded on the device.  Capacity protocol (abr_rle_encode): the call gets room for
+    max(1024, h * w / 16) characters per instance; the per-instance offsets are read back (one small copy), and only when their last entry
+    says the room was too small -- masks close to noise -- the call is repeated with exactly that many bytes; then the characters are
+    downloaded, exactly as many as were written."""
+    if hasattr(masks, "bits") and hasattr(masks, "size"):
+        masks, width = masks.bits, masks.size[0]
+    L.require_cuda(masks)
+    if masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.int64) or (masks.dtype == torch.int64 and width is None):
+        raise RuntimeError("rle_encode: expected uint8 [n,h,w] masks, a PackedMasks, or int64 words with `width`; got {} {}".format(
+            tuple(masks.shape), masks.dtype))
+    masks = masks.contiguous()
+    is_bits = masks.dtype == torch.int64
+    n, h = int(masks.shape[0]), int(masks.shape[1])
+    w = int(width) if is_bits else int(masks.shape[2])
+    if is_bits and masks.shape[2] != mask_words_per_row(w):
+        raise RuntimeError("rle_encode: words of shape {} do not pack masks {} wide".format(tuple(masks.shape), w))
+    if n == 0:
+        return []
+    dev = masks.device
+    head = 8 * (n + 1) + (4 * n + 7) // 8 * 8
+    with torch.cuda.device(dev):
+        ws_bytes = L.lib().abr_rle_encode_workspace_bytes(n, h, w)
+        if ws_bytes < 0:
+            raise RuntimeError("rle_encode: bad size {}".format((h, w)))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        capacity = n * max(1024, h * w // 16)
+        while True:
+            buf = torch.empty((head + capacity,), dtype=torch.uint8, device=dev)     # offsets [n+1] int64 | nruns [n] int32 | characters
+            L.check(L.lib().abr_rle_encode(None if is_bits else L.ptr(masks), L.ptr(masks) if is_bits else None, n, h, w, L.ptr(buf[head:]), capacity,
+                                           L.ptr(buf), L.ptr(buf[8 * (n + 1):]), L.ptr(ws), ws_bytes, L.stream()), "rle_encode")
+            offsets = buf[: 8 * (n + 1)].cpu().numpy().view("int64")
+            total = int(offsets[-1])
+            if total <= capacity:
+                break
+            capacity = total
+        chars = buf[head: head + total].cpu().numpy().tobytes()
+    return [{"size": [h, w], "counts": chars[int(offsets[i]): int(offsets[i + 1])].decode("ascii")} for i in range(n)]

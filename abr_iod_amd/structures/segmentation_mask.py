@@ -1,16 +1,27 @@
 """SegmentationMask over binary instance masks (mirror of maskrcnn_benchmark/structures/segmentation_mask.py:33-179, 445-545 for
 mode="mask"): ONE tensor [n,H,W] (uint8 or float32) on any device, with the reference's crop / resize / transpose / indexing, so that BoxList
 indexing, flipping and resizing carry a "masks" field as they do there.  This is the data path's API; the training step never calls it per
-RoI -- its targets come from ops.mask_targets.  mode="poly" needs pycocotools' rasteriser and is out of scope."""
+RoI -- its targets come from ops.mask_targets.  mode="poly" needs pycocotools' rasteriser and is out of scope.  COCO run-length annotations (a list of RLE dicts, what the reference hands to
+pycocotools' mask_utils.decode, segmentation_mask.py:57-63) are decoded by ops.rle_decode: on the device when one is given, else by the host codec
+(structures/rle.py)."""
 import torch
 
 FLIP_LEFT_RIGHT = 0
 FLIP_TOP_BOTTOM = 1
 
 
+def _decode_rles(rles, size, device, packed):
+    from .. import ops
+    for i, inst in enumerate(rles):     # the reference's check, segmentation_mask.py:59-61
+        assert isinstance(inst, dict) and "size" in inst and "counts" in inst, "RLE instance %d: expected a dict with 'size' and 'counts'" % i
+        assert (size[1], size[0]) == tuple(inst["size"]), "RLE instance %d: %s != %s" % (i, (size[1], size[0]), tuple(inst["size"]))
+    return ops.rle_decode(list(rles), (size[1], size[0]), device if device is not None else "cpu", packed=packed)
+
+
 class SegmentationMask(object):
-    def __init__(self, instances, size, mode="mask"):
-        """instances: [n,H,W] tensor, [H,W] tensor, list of [H,W] tensors or a SegmentationMask; size = (width, height)"""
+    def __init__(self, instances, size, mode="mask", device=None):
+        """instances: [n,H,W] tensor, [H,W] tensor, list of [H,W] tensors, list of COCO RLE dicts or a SegmentationMask; size = (width, height);
+        device: where RLE dicts are decoded (None: the CPU); tensors stay where they are"""
         if mode == "poly":
             raise NotImplementedError("SegmentationMask mode 'poly': polygon masks need pycocotools' rasteriser, which this build does not carry; "
                                       "rasterise on the host and pass mode='mask'")
@@ -20,8 +31,11 @@ class SegmentationMask(object):
         size = tuple(int(s.item()) if isinstance(s, torch.Tensor) else s for s in size)
         if isinstance(instances, SegmentationMask):
             masks = instances.masks
+        elif isinstance(instances, (list, tuple)) and len(instances) and isinstance(instances[0], dict):
+            masks = _decode_rles(instances, size, device, packed=False)
         elif isinstance(instances, (list, tuple)):
-            masks = torch.stack(list(instances), dim=0) if len(instances) else torch.zeros((0, int(size[1]), int(size[0])), dtype=torch.uint8)
+            masks = torch.stack(list(instances), dim=0) if len(instances) else torch.zeros((0, int(size[1]), int(size[0])), dtype=torch.uint8,
+                                                                                           device=device if device is not None else "cpu")
         else:
             masks = instances
         if masks.dim() == 2:
@@ -111,6 +125,17 @@ class PackedMasks(object):
         self.bits = bits
         self.size = size
         self.mode = "packed"
+
+    @classmethod
+    def from_rle(cls, rles, size, device=None):
+        """list of COCO RLE dicts, size = (width, height) -> PackedMasks on `device` (None: the CPU): the words are written by the decoder,
+        the masks never exist as bytes (ground truth for mask AP)"""
+        size = tuple(int(s) for s in size)
+        if len(rles) == 0:
+            bits = torch.zeros((0, size[1], (size[0] + 63) // 64), dtype=torch.int64, device=device if device is not None else "cpu")
+        else:
+            bits = _decode_rles(rles, size, device, packed=True)
+        return cls(bits, size)
 
     @property
     def instances(self):

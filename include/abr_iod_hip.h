@@ -651,6 +651,33 @@ int abr_mask_resize_pack_bits(const uint8_t* masks, int n, int Hs, int Ws, int H
 int abr_mask_pair_counts(const uint64_t* pred_bits, const uint64_t* gt_bits, const int64_t* pred_labels, const int64_t* gt_labels, int P, int T,
                          int H, int W, int64_t words, int32_t* inter, int32_t* area_p, int32_t* area_t, void* stream);
 
+/* =====================================================================================================
+ * 11. COCO run-length masks (csrc/rle.hip): what pycocotools' mask_utils.decode / encode compute, restated from the format (pycocotools
+ *     cannot be run where this library is built: compatibility rests on the restatement in DESIGN.md section 4 and its known answers).
+ *     An RLE of an h x w mask: pixels in COLUMN-major order p = x * h + y, counts = lengths of alternating runs, the first of zeros,
+ *     summing to h * w.  Compressed form: ASCII characters in [48,111]; the i-th stored value is counts[i] - counts[i-2] for i > 2 and
+ *     counts[i] otherwise, 5 bits per character low bits first, 0x20 = another character follows, 0x10 of the last = sign.
+ * ===================================================================================================== */
+/* Decode the n instances of ONE image (all h x w) in one call.  Give EITHER bytes (uint8 [n_items], the n compressed strings
+ * concatenated) OR counts (int32 [n_items], the n uncompressed count lists concatenated); offsets int64 [n+1]: instance k owns items
+ * [offsets[k], offsets[k+1]).  Outputs, either or both: masks uint8 [n,h,w] row-major 0/1 (4-byte aligned); bits [n,h,ceil(w/64)] in
+ * abr_mask_pack_bits' layout.  totals int64 [n]: the sum of instance k's counts -- the annotation is well formed iff totals[k] == h * w;
+ * bytes that have no sum give a negative code: -1 the last token is cut short, -2 a character outside [48,111], -3 a token longer than 7
+ * characters or a value outside int32, -4 a negative count.  An instance whose total is not h * w decodes to zeros.  No write lands outside
+ * masks / bits / totals / workspace whatever the bytes and offsets hold (offsets are clamped into [0, n_items]).
+ * workspace: abr_rle_decode_workspace_bytes(n, n_items) bytes.  n == 0: success, nothing launched. */
+int64_t abr_rle_decode_workspace_bytes(int n, int64_t n_items);
+int abr_rle_decode(const uint8_t* bytes, const int32_t* counts, const int64_t* offsets, int n, int64_t n_items, int h, int w, uint8_t* masks,
+                   uint64_t* bits, int64_t* totals, void* workspace, int64_t workspace_bytes, void* stream);
+/* Encode n masks of one size: EITHER masks uint8 [n,h,w] (a pixel is set iff it == 1, as in abr_mask_pack_bits) OR bits [n,h,ceil(w/64)].
+ * Outputs: offsets int64 [n+1] (instance k's compressed string is out_bytes[offsets[k] .. offsets[k+1])), nruns int32 [n] (its number of
+ * counts), out_bytes uint8 [capacity].  Capacity protocol: offsets and nruns are ALWAYS written; the characters are written only when
+ * offsets[n] <= capacity (all or nothing).  The caller reads offsets back (it needs them anyway) and, when offsets[n] > capacity, calls again
+ * with at least offsets[n] bytes; capacity 0 is a pure sizing call.  workspace: abr_rle_encode_workspace_bytes(n, h, w) bytes. */
+int64_t abr_rle_encode_workspace_bytes(int n, int h, int w);
+int abr_rle_encode(const uint8_t* masks, const uint64_t* bits, int n, int h, int w, uint8_t* out_bytes, int64_t capacity, int64_t* offsets,
+                   int32_t* nruns, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,9 @@ _SIGS = {
     "abr_rle_decode": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "abr_rle_encode_workspace_bytes": (_i64, [_i, _i, _i]),
     "abr_rle_encode": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "abr_poly_rasterize_workspace_bytes": (_i64, [_i64, _i, _i]),
+    "abr_poly_rasterize": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "abr_poly_mask_targets": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 # every symbol include/abr_iod_hip.h declares (tests/test_abi.py checks the library exports them all)

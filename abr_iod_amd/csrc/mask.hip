@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "mask_bilinear.h"
+#include "mask_match.h"
 
 namespace {
 
@@ -69,16 +70,6 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(const float4* __restrict
 // mask targets
 // ------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
-__device__ __forceinline__ float mask_box_iou(const float4 g, const float4 b) {
-    // structures/boxlist_ops.py:53-88, TO_REMOVE = 1 (the arithmetic of rpn.hip's box_iou)
-    const float area1 = (g.z - g.x + 1) * (g.w - g.y + 1);
-    const float area2 = (b.z - b.x + 1) * (b.w - b.y + 1);
-    const float lx = fmaxf(g.x, b.x), ly = fmaxf(g.y, b.y), rx = fminf(g.z, b.z), ry = fminf(g.w, b.w);
-    const float w = fmaxf(rx - lx + 1, 0.f), h = fmaxf(ry - ly + 1, 0.f);
-    const float inter = w * h;
-    return inter / (area1 + area2 - inter);
-}
-
 __device__ __forceinline__ int round_to_int(const float v) {   // Python round() of a float: half to even
     return (int)fminf(fmaxf(rintf(v), -1.0e9f), 1.0e9f);
 }
@@ -101,12 +92,7 @@ __global__ __launch_bounds__(256) void mask_targets_kernel(const T* const* __res
     if (threadIdx.x == 0) {
         const float4 b = make_float4(rois[row * 5 + 1], rois[row * 5 + 2], rois[row * 5 + 3], rois[row * 5 + 4]);
         const float4* gt = reinterpret_cast<const float4*>(gt_ptrs[img]);
-        float best = -1.f;
-        int bi = 0;
-        for (int g = 0; g < G; g++) {
-            const float v = mask_box_iou(gt[g], b);
-            if (v > best) { best = v; bi = g; }      // first max wins (torch.max)
-        }
+        const int bi = abr::mask_match_gt(gt, G, b);      // first maximum IoU (mask_match.h)
         // BinaryMaskList.crop (segmentation_mask.py:92-111)
         int xmin = round_to_int(b.x), ymin = round_to_int(b.y), xmax = round_to_int(b.z), ymax = round_to_int(b.w);
         xmin = min(max(xmin, 0), W - 1);

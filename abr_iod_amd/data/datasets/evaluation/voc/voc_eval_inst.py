@@ -55,7 +55,9 @@ def image_mask_counts(prediction, gt_boxlist, size, device=None):
         device = held.device if held.is_cuda else torch.device("cuda")
     pred_bits = _prediction_bits(field, size, device)
     gt = gt_boxlist.get_field("masks").instances
-    if hasattr(gt, "bits"):      # PackedMasks (decoded from run-length annotations straight into bits)
+    if hasattr(gt, "poly_offsets"):     # PolygonList: rasterised straight into bits on the device
+        gt = gt.to(device).pack()
+    if hasattr(gt, "bits"):     # PackedMasks (decoded from run-length annotations straight into bits)
         assert tuple(gt.size) == (int(size[0]), int(size[1])), "ground-truth masks {} are not at the image's size {}".format(gt, size)
         gt_bits = gt.bits.to(device)
     else:

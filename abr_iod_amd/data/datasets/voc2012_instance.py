@@ -6,7 +6,8 @@ images by id, annotations by image id in file order.  Kept from the reference:
     no keypoints) and at least one of them is of a NEW class (training) or of a new or old class (testing) (:80-100);
   * a sample's annotations are ALL of the image's (crowd included, :114-115) filtered to those classes (:124-130); boxes xywh -> xyxy, labels
     = category ids, "masks" = the annotations' run-length "segmentation" decoded by ops.rle_decode on the dataset's device (the reference:
-    pycocotools on the host), then clip_to_image(remove_empty=False) (:131-147);
+    pycocotools on the host), or, when the "segmentation"s are polygons, a PolygonList (structures/polygon.py), then
+    clip_to_image(remove_empty=False) (:131-147);
   * get_groundtruth (unclipped, :158-232), get_img_info (the JSON's image record), get_img_id, map_class_id_to_class_name.
 Samples have this package's form (data/datasets/voc.py): (uint8 device image, target, flip flag, index), for GPUTransform.collate."""
 import json
@@ -15,6 +16,7 @@ import os
 import torch
 
 from ...structures.bounding_box import BoxList
+from ...structures.polygon import PolygonList
 from ...structures.segmentation_mask import PackedMasks, SegmentationMask
 from ..gpu_transforms import to_device_u8
 from .voc import CLASSES
@@ -76,8 +78,27 @@ class PascalVOCDataset2012(object):
         target = BoxList(boxes, size, mode="xywh").convert("xyxy")
         target.add_field("labels", torch.tensor([obj["category_id"] for obj in anno], dtype=torch.int64))
         segs = [obj["segmentation"] for obj in anno]
-        target.add_field("masks", PackedMasks.from_rle(segs, size, self.device) if packed else SegmentationMask(segs, size, mode="mask", device=self.device))
+        target.add_field("masks", self._masks(segs, size, packed))
         return target
+
+    def _masks(self, segs, size, packed):
+        """run-length dicts: decoded (as ever); polygons (a list of flat coordinate lists per annotation): a PolygonList on the dataset's
+        device, or with packed=True rasterised straight into bits; an image that mixes both: the polygons are rasterised and everything
+        becomes one SegmentationMask (PackedMasks with packed=True)"""
+        poly = [i for i, seg in enumerate(segs) if isinstance(seg, (list, tuple))]
+        if not poly:
+            return PackedMasks.from_rle(segs, size, self.device) if packed else SegmentationMask(segs, size, mode="mask", device=self.device)
+        polys = PolygonList([segs[i] for i in poly], size, device=self.device)
+        if len(poly) == len(segs):
+            return polys.pack() if packed else polys
+        rle = [i for i in range(len(segs)) if i not in set(poly)]
+        rles = [segs[i] for i in rle]
+        a = polys.pack().bits if packed else polys.convert("mask").masks
+        b = PackedMasks.from_rle(rles, size, self.device).bits if packed else SegmentationMask(rles, size, mode="mask", device=self.device).masks
+        both = a.new_empty((len(segs),) + tuple(a.shape[1:]))
+        both[torch.tensor(poly, device=a.device)] = a
+        both[torch.tensor(rle, device=a.device)] = b
+        return PackedMasks(both, size) if packed else SegmentationMask(both, size, mode="mask")
 
     def get_groundtruth(self, index, packed=False):
         """the image's target at its original size; packed=True: "masks" as PackedMasks decoded straight into bits (evaluation)"""

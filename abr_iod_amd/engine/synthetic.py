@@ -1,6 +1,8 @@
 """Synthetic VOC-shaped workload for the benchmark / smoke test / parity tests:
 configs for an incremental task, seeded random-init source + target models, 600x1000 image batches with a few GT boxes.
 There is no network access for datasets or checkpoints; `data` is reported as "synthetic" by bench.py."""
+import math
+
 import torch
 
 from ..config import cfg as _default_cfg
@@ -104,11 +106,21 @@ def _box_masks(boxes, height, width, shape, dtype):
     return inside.to(dtype)
 
 
+def _box_polygons(boxes, sides=24):
+    """one polygon per xyxy box: the `sides`-gon inscribed in _box_masks' ellipse (no random numbers are drawn)"""
+    x1, y1, x2, y2 = (boxes[:, i].view(-1, 1) for i in range(4))
+    cx, cy, rx, ry = (x1 + x2) / 2, (y1 + y2) / 2, ((x2 - x1) / 2).clamp(min=0.5), ((y2 - y1) / 2).clamp(min=0.5)
+    a = torch.arange(sides, dtype=torch.float32).view(1, -1) * (2.0 * math.pi / sides)
+    xy = torch.stack((cx + rx * torch.cos(a), cy + ry * torch.sin(a)), dim=2)       # [n, sides, 2]
+    return [[poly.reshape(-1).tolist()] for poly in xy]
+
+
 def synthetic_batch(batch, height=600, width=1000, seed=42, label_range=(16, 21), device="cuda", max_boxes=5, masks=None, mask_dtype=torch.uint8):
     """images: uint8-valued U[0,255] BGR minus PIXEL_MEAN (transforms.py:161-165 + defaults.py:56-60);
     targets: 1..max_boxes GT boxes per image, w,h log-uniform in [32,480], labels over the task's NEW class ids.
     masks="ellipse" / "rect" (opt-in, MODEL.MASK_ON): a "masks" field (SegmentationMask, mode "mask", mask_dtype uint8 or float32) with one
-    instance inside each GT box; images, boxes and labels are the same with and without it."""
+    instance inside each GT box; masks="poly": the ellipse as a 24-gon in a PolygonList (structures/polygon.py); images, boxes and labels
+    are the same with and without it."""
     g = torch.Generator().manual_seed(seed)
     mean = torch.tensor([102.9801, 115.9465, 122.7717]).view(1, 3, 1, 1)
     images = torch.randint(0, 256, (batch, 3, height, width), generator=g).float() - mean
@@ -123,7 +135,10 @@ def synthetic_batch(batch, height=600, width=1000, seed=42, label_range=(16, 21)
         labels = torch.randint(label_range[0], label_range[1], (n,), generator=g)
         t = BoxList(boxes.to(device), (width, height), mode="xyxy")
         t.add_field("labels", labels.to(device))
-        if masks is not None:
+        if masks == "poly":
+            from ..structures.polygon import PolygonList
+            t.add_field("masks", PolygonList(_box_polygons(boxes), (width, height), device=device))
+        elif masks is not None:
             from ..structures.segmentation_mask import SegmentationMask
             t.add_field("masks", SegmentationMask(_box_masks(boxes, height, width, masks, mask_dtype).to(device), (width, height), mode="mask"))
         targets.append(t)

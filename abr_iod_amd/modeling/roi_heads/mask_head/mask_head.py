@@ -9,7 +9,8 @@ Mirrors:
 MI355X-first differences (results identical):
   * the positives of the box head's sampled set are compacted ON THE DEVICE into a fixed-size, -1 padded list (at most POSITIVE_FRACTION *
     BATCH_SIZE_PER_IMAGE rows per image): no nonzero(), no read-back; padding rows carry zeros through the predictor and the loss skips them.
-  * the mask targets of the whole batch are ONE launch (the reference crops and resizes per RoI on the host, loss.py:31).
+  * the mask targets of the whole batch are ONE launch (the reference crops and resizes per RoI on the host, loss.py:31), for bitmask
+    targets (ops.mask_targets) and for polygon targets (PolygonList fields, ops.poly_mask_targets) alike.
   * ConvTranspose2d(2, 2, 0) is a GEMM with 4 * C_mid output columns on the conv planner plus one depth-to-space + bias + ReLU pass.
 """
 import torch
@@ -19,6 +20,7 @@ from torch.autograd import Function
 from .... import ops
 from ....layers._layout import as_nhwc, from_nhwc
 from ....structures.bounding_box import BoxList
+from ....structures.polygon import PolygonList
 from ...backbone.resnet import Conv2d, _grad_buf
 
 
@@ -193,13 +195,21 @@ class MaskRCNNLossComputation(object):
             rois = torch.cat([torch.cat((torch.full((len(p), 1), float(i), device=dev), p.convert("xyxy").bbox), 1) for i, p in enumerate(proposals)])
         p_max = max(1, min(labels.numel(), self.max_pos_per_image * len(proposals)))
         pos_rows, pos_labels, inv, n_pos = ops.mask_compact_pos(labels, p_max)
-        masks = []
+        segs = []
         for p, t in zip(proposals, targets):
             seg = t.get_field("masks")
             if tuple(seg.size) != tuple(p.size):
                 raise AssertionError("{}, {}".format(seg, p))     # loss.py:27
-            masks.append(seg.masks)
-        mt = ops.mask_targets(masks, [t.convert("xyxy").bbox for t in targets], rois, pos_rows, self.discretization_size)
+            segs.append(seg)
+        gt_boxes = [t.convert("xyxy").bbox for t in targets]
+        n_poly = sum(isinstance(seg, PolygonList) for seg in segs)
+        if n_poly:       # polygon targets: cropped, scaled and rasterised per RoI on the device (the reference: pycocotools on the host)
+            if n_poly != len(segs):
+                raise TypeError("the \"masks\" fields of a batch must be all PolygonList or all SegmentationMask, got {}: convert the polygon "
+                                "lists with .convert(\"mask\")".format([type(seg).__name__ for seg in segs]))
+            mt = ops.poly_mask_targets(segs, gt_boxes, rois, pos_rows, self.discretization_size)
+        else:
+            mt = ops.mask_targets([seg.masks for seg in segs], gt_boxes, rois, pos_rows, self.discretization_size)
         return dict(pos_rows=pos_rows, pos_labels=pos_labels, inv=inv, n_pos=n_pos, mask_targets=mt)
 
     def __call__(self, sel, padded_logits, num_classes):

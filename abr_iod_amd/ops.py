@@ -1643,3 +1643,75 @@ def rle_encode(masks, width=None):
             capacity = total
         chars = buf[head: head + total].cpu().numpy().tobytes()
     return [{"size": [h, w], "counts": chars[int(offsets[i]): int(offsets[i + 1])].decode("ascii")} for i in range(n)]
+
+
+# ----------------------------------------------------------------------------------------------- polygon masks (csrc/poly.hip)
+def poly_rasterize(polys, packed=False, out=None, return_status=False):
+    """PolygonList of one image -> its instance masks where the list is: uint8 [n,h,w] of 0 / 1, or with packed=True the int64
+    [n,h,ceil(w/64)] words of mask_pack_bits (the bytes are never written).  What pycocotools' frPyObjects + merge + decode give
+    (DESIGN.md §4); an instance is the OR of its polygons.  `out`: a contiguous tensor of the result's shape and dtype to write into.
+    return_status=True: -> (masks, status int32 [n]), status[i] != 0 when a polygon of instance i was left out by the guard (a non-finite
+    coordinate: 1, one beyond +-32768 pixels: 2); nothing is read back.  A list on the CPU: the host codec (structures/polygon.py)."""
+    w, h = polys.int_size()
+    device = polys.coords.device
+    n = len(polys)
+    shape = (n, h, mask_words_per_row(w)) if packed else (n, h, w)
+    dtype = torch.int64 if packed else torch.uint8
+    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != device):
+        raise RuntimeError("poly_rasterize: `out` must be a contiguous {} tensor of shape {} on {}".format(dtype, shape, device))
+    if device.type == "cpu":
+        from .structures import polygon as host
+        m, st = host.rasterize(polys.coords.numpy(), polys._po, polys._io, h, w)
+        m, status = torch.from_numpy(m), torch.from_numpy(st)
+        if packed:
+            px = torch.zeros((n, h, shape[2] * 64), dtype=torch.int64)
+            px[:, :, :w] = m
+            m = (px.reshape(n, h, shape[2], 64) << torch.arange(64, dtype=torch.int64)).sum(-1)
+        m = m if out is None else out.copy_(m)
+        return (m, status) if return_status else m
+    if h * w >= 2 ** 31 - 64:
+        raise RuntimeError("poly_rasterize: bad size {}".format((h, w)))
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    status = torch.zeros((n,), dtype=torch.int32, device=device)
+    if n:
+        coords = L.f32c(polys.coords)
+        po, io = polys.poly_offsets.contiguous(), polys.inst_offsets.contiguous()
+        n_poly = po.numel() - 1
+        with torch.cuda.device(device):
+            ws_bytes = L.lib().abr_poly_rasterize_workspace_bytes(n_poly, h, w)
+            ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=device)
+            L.check(L.lib().abr_poly_rasterize(L.ptr(coords), L.ptr(po), L.ptr(io), n, n_poly, coords.shape[0], h, w, None if packed else L.ptr(out),
+                                               L.ptr(out) if packed else None, L.ptr(status), L.ptr(ws), ws_bytes, L.stream()), "poly_rasterize")
+    return (out, status) if return_status else out
+
+
+def poly_mask_targets(polys_per_image, gt_boxes, rois, pos_rows, M):
+    """polys_per_image: per-image PolygonList on the device, gt_boxes: per-image [n,4]; rois [K,5]; pos_rows [P] -> [P,M,M]: for each row the
+    polygons of the matched instance (first maximum IoU, as mask_targets) through PolygonInstance.crop(box).resize((M, M)), rasterised on the
+    M x M grid -- the reference's project_masks_on_boxes (mask_head/loss.py:11-42) for polygon targets, one launch for the batch"""
+    L.require_cuda(rois, pos_rows, *[p.coords for p in polys_per_image])
+    dev = rois.device
+    if len(polys_per_image) != len(gt_boxes) or not len(gt_boxes):
+        raise RuntimeError("poly_mask_targets: {} polygon lists for {} images".format(len(polys_per_image), len(gt_boxes)))
+    dims = []
+    for p, g in zip(polys_per_image, gt_boxes):
+        if len(p) != g.shape[0]:
+            raise RuntimeError("poly_mask_targets: {} polygon instances for {} ground-truth boxes".format(len(p), g.shape[0]))
+        w, h = p.int_size()
+        dims += [len(p), len(p._po) - 1, int(p.coords.shape[0]), h, w]
+    if int(M) > 64:
+        raise RuntimeError("poly_mask_targets: M = {} (the kernel's grid holds M <= 64)".format(M))
+    cs = [L.f32c(p.coords) for p in polys_per_image]
+    pos = [p.poly_offsets.contiguous() for p in polys_per_image]
+    ios = [p.inst_offsets.contiguous() for p in polys_per_image]
+    gs = [L.f32c(g) for g in gt_boxes]
+    rois = L.f32c(rois)
+    N, P = len(gs), pos_rows.numel()
+    out = torch.empty((P, M, M), dtype=_f32, device=dev)
+    dtab = h2d(dims, torch.int32, dev)
+    tab = _pointer_table(cs + pos + ios + gs, dev)     # ONE upload: four tables of N addresses (held in locals until the launch: _evict_oldest)
+    t0 = L.ptr(tab)
+    L.check(L.lib().abr_poly_mask_targets(t0, t0 + 8 * N, t0 + 16 * N, L.ptr(dtab), t0 + 24 * N, L.ptr(rois), L.ptr(pos_rows), P, rois.shape[0], N, int(M),
+                                          L.ptr(out), L.stream()), "poly_mask_targets")
+    return out

@@ -1,7 +1,7 @@
 """SegmentationMask over binary instance masks (mirror of maskrcnn_benchmark/structures/segmentation_mask.py:33-179, 445-545 for
 mode="mask"): ONE tensor [n,H,W] (uint8 or float32) on any device, with the reference's crop / resize / transpose / indexing, so that BoxList
 indexing, flipping and resizing carry a "masks" field as they do there.  This is the data path's API; the training step never calls it per
-RoI -- its targets come from ops.mask_targets.  mode="poly" needs pycocotools' rasteriser and is out of scope.  COCO run-length annotations (a list of RLE dicts, what the reference hands to
+RoI -- its targets come from ops.mask_targets.  mode="poly" raises: polygons live in structures/polygon.py's PolygonList.  COCO run-length annotations (a list of RLE dicts, what the reference hands to
 pycocotools' mask_utils.decode, segmentation_mask.py:57-63) are decoded by ops.rle_decode: on the device when one is given, else by the host codec
 (structures/rle.py)."""
 import torch
@@ -23,8 +23,8 @@ class SegmentationMask(object):
         """instances: [n,H,W] tensor, [H,W] tensor, list of [H,W] tensors, list of COCO RLE dicts or a SegmentationMask; size = (width, height);
         device: where RLE dicts are decoded (None: the CPU); tensors stay where they are"""
         if mode == "poly":
-            raise NotImplementedError("SegmentationMask mode 'poly': polygon masks need pycocotools' rasteriser, which this build does not carry; "
-                                      "rasterise on the host and pass mode='mask'")
+            raise NotImplementedError("SegmentationMask mode 'poly': polygons have a class of their own here, structures.polygon.PolygonList(polygons, "
+                                      "size); a BoxList carries it as its 'masks' field and .convert('mask') rasterises it")
         if mode != "mask":
             raise NotImplementedError("Unknown mode: %s" % str(mode))
         assert isinstance(size, (list, tuple)) and len(size) == 2

@@ -678,6 +678,32 @@ int64_t abr_rle_encode_workspace_bytes(int n, int h, int w);
 int abr_rle_encode(const uint8_t* masks, const uint64_t* bits, int n, int h, int w, uint8_t* out_bytes, int64_t capacity, int64_t* offsets,
                    int32_t* nruns, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* =====================================================================================================
+ * 12. Polygon instance masks (csrc/poly.hip): what pycocotools' rleFrPoly + merge + decode compute for COCO "segmentation" polygons,
+ *     restated from the algorithm.  Storage of one image: coords float32 [n_vert,2] (x, y); poly_offsets int64
+ *     [n_poly+1]: polygon p owns vertices [poly_offsets[p], poly_offsets[p+1]); inst_offsets int64 [n+1]: instance i owns polygons
+ *     [inst_offsets[i], inst_offsets[i+1]).  An instance is the OR of its polygons; one without polygons is all zeros.
+ *     Guard: a polygon with a non-finite coordinate (flag 1) or a coordinate c with |5 c| > 5 * 32768 (flag 2) contributes nothing.
+ * ===================================================================================================== */
+/* Rasterise the n instances of ONE image on its h x w grid.  Outputs, either or both: masks uint8 [n,h,w] row-major 0/1 (4-byte aligned);
+ * bits [n,h,ceil(w/64)] in abr_mask_pack_bits' layout (the bytes are never written when only bits are asked for).  status int32 [n]: the
+ * OR of the guard flags of the instance's polygons, 0 = fine.  No write lands outside masks / bits / status / workspace whatever the
+ * offsets hold (they are clamped into [0, n_vert] and [0, n_poly]).  workspace: abr_poly_rasterize_workspace_bytes(n_poly, h, w) bytes,
+ * 8-byte aligned (-1: bad sizes; h * w must stay below 2^31 - 64).  n == 0: success, nothing launched. */
+int64_t abr_poly_rasterize_workspace_bytes(int64_t n_poly, int h, int w);
+int abr_poly_rasterize(const float* coords, const int64_t* poly_offsets, const int64_t* inst_offsets, int n, int64_t n_poly, int64_t n_vert, int h,
+                       int w, uint8_t* masks, uint64_t* bits, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+/* The polygon twin of abr_mask_targets (mask_head/loss.py:11-42 over PolygonList): for row pos_rows[p] of rois [K,5] (image index, xyxy),
+ * the instance of its image with the first maximum IoU against gt_ptrs[img] [G,4]; its vertices through PolygonInstance.crop(box) and
+ * .resize((M, M)), fl32(fl32(c - lo) * fl32(M / (hi - lo))) with the box clamped as segmentation_mask.py:251-261 and the quotient formed
+ * in double; rasterised on the M x M grid.  Per-image device pointer tables coord_ptrs / poly_offset_ptrs / inst_offset_ptrs [N] and
+ * dims int32 [N,5] = (instances G, polygons, vertices, image height, image width).  out float32 [P_max,M,M] of 0 / 1; rows with
+ * pos_rows[p] < 0 (padding), an image index outside [0, N) or an image without instances give zeros.  M <= 64.  A guarded polygon
+ * contributes nothing.  No host read-back, no allocation; P_max == 0: success, nothing launched. */
+int abr_poly_mask_targets(const float* const* coord_ptrs, const int64_t* const* poly_offset_ptrs, const int64_t* const* inst_offset_ptrs,
+                          const int32_t* dims, const float* const* gt_ptrs, const float* rois, const int64_t* pos_rows, int P_max, int K, int N, int M,
+                          float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,17 @@ namespace abr {
 // diverged activation into a clean zero and hide it from the loss and from the range guard; the reference's run shows NaN (modeling/backbone/resnet.py:339-346).
 __device__ __forceinline__ float relu_f(const float v) { return v < 0.f ? 0.f : v; }
 
+// IoU of two boxes (x1, y1, x2, y2) as structures/boxlist_ops.py:53-88 computes it, TO_REMOVE = 1: the one definition behind the matchers of
+// rpn.hip and mask_match.h, which must agree bit for bit (nms.hip's `suppresses` is a different formulation).  One rounding per operation.
+__device__ __forceinline__ float box_iou(const float4 g, const float4 b) {
+#pragma clang fp contract(off)
+    const float area1 = (g.z - g.x + 1) * (g.w - g.y + 1);
+    const float area2 = (b.z - b.x + 1) * (b.w - b.y + 1);
+    const float lx = fmaxf(g.x, b.x), ly = fmaxf(g.y, b.y), rx = fminf(g.z, b.z), ry = fminf(g.w, b.w);
+    const float w = fmaxf(rx - lx + 1, 0.f), h = fmaxf(ry - ly + 1, 0.f);
+    const float inter = w * h;
+    return inter / (area1 + area2 - inter);
+}
 
 void set_error(const char* fmt, ...);
 

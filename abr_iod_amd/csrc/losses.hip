@@ -8,74 +8,39 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// Sigmoid focal loss -- csrc/cuda/SigmoidFocalLoss_cuda.cu:20-101 (sub-expressions with `1.` literals are
-// evaluated in double there; kept so, it is elementwise and fp64 is cheap on CDNA4).
+// Sigmoid focal loss -- csrc/cuda/SigmoidFocalLoss_cuda.cu:20-101, for T = float and T = double (AT_DISPATCH_FLOATING_TYPES, :128,172).
+// The reference's template keeps its expf / powf / logf calls and its `1.` literals with every T: float transcendentals inside double
+// sub-expressions (kept so, it is elementwise and fp64 is cheap on CDNA4); gamma / alpha are `const float` there too.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void focal_fwd(const float* __restrict__ logits, const int32_t* __restrict__ targets,
-                                                  int64_t total, int C, float gamma, float alpha,
-                                                  float* __restrict__ losses) {
+template <typename T>
+__global__ __launch_bounds__(256) void focal_fwd(const T* __restrict__ logits, const int32_t* __restrict__ targets, int64_t total, int C, float gamma,
+                                                  float alpha, T* __restrict__ losses) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int n = i / C, d = i % C, t = targets[n];
-        const float c1 = (t == d + 1), c2 = (t >= 0) & (t != d + 1);
-        const float zn = (float)(1.0 - alpha), zp = alpha, x = logits[i];
-        const float p = (float)(1. / (1. + expf(-x)));
-        const float term1 = (float)(powf((float)(1. - p), gamma) * logf(fmaxf(p, FLT_MIN)));
-        const float term2 =
-            (float)(powf(p, gamma) * (-1. * x * (x >= 0) - logf((float)(1. + expf((float)(x - 2. * x * (x >= 0)))))));
-        float l = 0.f;
+        const T c1 = (t == d + 1), c2 = (t >= 0) & (t != d + 1);
+        const T zn = (1.0 - alpha), zp = alpha, x = logits[i];
+        const T p = 1. / (1. + expf((float)-x));
+        const T term1 = powf((float)(1. - p), gamma) * logf((float)fmax(p, (T)FLT_MIN));
+        const T term2 = powf((float)p, gamma) * (-1. * x * (x >= 0) - logf((float)(1. + expf((float)(x - 2. * x * (x >= 0))))));
+        T l = 0;
         l += -c1 * term1 * zp;
         l += -c2 * term2 * zn;
         losses[i] = l;
     }
 }
 
-__global__ __launch_bounds__(256) void focal_bwd(const float* __restrict__ logits, const int32_t* __restrict__ targets,
-                                                  const float* __restrict__ d_losses, int64_t total, int C, float gamma,
-                                                  float alpha, float* __restrict__ d_logits) {
+template <typename T>
+__global__ __launch_bounds__(256) void focal_bwd(const T* __restrict__ logits, const int32_t* __restrict__ targets, const T* __restrict__ d_losses,
+                                                  int64_t total, int C, float gamma, float alpha, T* __restrict__ d_logits) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int n = i / C, d = i % C, t = targets[n];
-        const float c1 = (t == d + 1), c2 = (t >= 0) & (t != d + 1);
-        const float zn = (float)(1.0 - alpha), zp = alpha, x = logits[i];
-        const float p = (float)(1. / (1. + expf(-x)));
-        const float term1 = (float)(powf((float)(1. - p), gamma) * (1. - p - (p * gamma * logf(fmaxf(p, FLT_MIN)))));
-        const float term2 = (float)(powf(p, gamma) *
-                                    ((-1. * x * (x >= 0) - logf((float)(1. + expf((float)(x - 2. * x * (x >= 0)))))) *
-                                         (1. - p) * gamma - p));
-        float g = 0.f;
-        g += -c1 * term1 * zp;
-        g += -c2 * term2 * zn;
-        d_logits[i] = g * d_losses[i];
-    }
-}
-
-// float64 instantiation (AT_DISPATCH_FLOATING_TYPES, SigmoidFocalLoss_cuda.cu:128,172): the reference's template with T = double keeps its
-// expf / powf / logf calls, i.e. float transcendentals inside double arithmetic; the same expressions here.
-__global__ __launch_bounds__(256) void focal_fwd_f64(const double* __restrict__ logits, const int32_t* __restrict__ targets, int64_t total, int C,
-                                                      float gamma, float alpha, double* __restrict__ losses) {   // (gamma / alpha are `const float` in the reference's template too)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int n = i / C, d = i % C, t = targets[n];
-        const double c1 = (t == d + 1), c2 = (t >= 0) & (t != d + 1);
-        const double zn = (1.0 - alpha), zp = alpha, x = logits[i];
-        const double p = 1. / (1. + expf((float)-x));
-        const double term1 = powf((float)(1. - p), gamma) * logf((float)fmax(p, (double)FLT_MIN));
-        const double term2 = powf((float)p, gamma) * (-1. * x * (x >= 0) - logf((float)(1. + expf((float)(x - 2. * x * (x >= 0))))));
-        double l = 0.0;
-        l += -c1 * term1 * zp;
-        l += -c2 * term2 * zn;
-        losses[i] = l;
-    }
-}
-__global__ __launch_bounds__(256) void focal_bwd_f64(const double* __restrict__ logits, const int32_t* __restrict__ targets, const double* __restrict__ d_losses,
-                                                      int64_t total, int C, float gamma, float alpha, double* __restrict__ d_logits) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int n = i / C, d = i % C, t = targets[n];
-        const double c1 = (t == d + 1), c2 = (t >= 0) & (t != d + 1);
-        const double zn = (1.0 - alpha), zp = alpha, x = logits[i];
-        const double p = 1. / (1. + expf((float)-x));
-        const double term1 = powf((float)(1. - p), gamma) * (1. - p - (p * gamma * logf((float)fmax(p, (double)FLT_MIN))));
-        const double term2 = powf((float)p, gamma) *
-                             ((-1. * x * (x >= 0) - logf((float)(1. + expf((float)(x - 2. * x * (x >= 0)))))) * (1. - p) * gamma - p);
-        double g = 0.0;
+        const T c1 = (t == d + 1), c2 = (t >= 0) & (t != d + 1);
+        const T zn = (1.0 - alpha), zp = alpha, x = logits[i];
+        const T p = 1. / (1. + expf((float)-x));
+        const T term1 = powf((float)(1. - p), gamma) * (1. - p - (p * gamma * logf((float)fmax(p, (T)FLT_MIN))));
+        const T term2 = powf((float)p, gamma) *
+                        ((-1. * x * (x >= 0) - logf((float)(1. + expf((float)(x - 2. * x * (x >= 0)))))) * (1. - p) * gamma - p);
+        T g = 0;
         g += -c1 * term1 * zp;
         g += -c2 * term2 * zn;
         d_logits[i] = g * d_losses[i];
@@ -449,7 +414,7 @@ extern "C" int abr_sigmoid_focal_forward(const float* logits, const int32_t* tar
     if (N == 0) return ABR_OK;
     ABR_REQUIRE(logits && targets && losses, "sigmoid_focal_forward: null pointer");
     const int64_t total = (int64_t)N * C;
-    focal_fwd<<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, abr::as_stream(stream)>>>(
+    focal_fwd<float><<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, abr::as_stream(stream)>>>(
         logits, targets, total, C, gamma, alpha, losses);
     ABR_CHECK_LAUNCH("sigmoid_focal_forward");
     return ABR_OK;
@@ -461,7 +426,7 @@ extern "C" int abr_sigmoid_focal_backward(const float* logits, const int32_t* ta
     if (N == 0) return ABR_OK;
     ABR_REQUIRE(logits && targets && d_losses && d_logits, "sigmoid_focal_backward: null pointer");
     const int64_t total = (int64_t)N * C;
-    focal_bwd<<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, abr::as_stream(stream)>>>(
+    focal_bwd<float><<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, abr::as_stream(stream)>>>(
         logits, targets, d_losses, total, C, gamma, alpha, d_logits);
     ABR_CHECK_LAUNCH("sigmoid_focal_backward");
     return ABR_OK;
@@ -473,7 +438,7 @@ extern "C" int abr_sigmoid_focal_forward_f64(const double* logits, const int32_t
     if (N == 0) return ABR_OK;
     ABR_REQUIRE(logits && targets && losses, "sigmoid_focal_forward_f64: null pointer");
     const int64_t total = (int64_t)N * C;
-    focal_fwd_f64<<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, abr::as_stream(stream)>>>(logits, targets, total, C, gamma, alpha, losses);
+    focal_fwd<double><<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, abr::as_stream(stream)>>>(logits, targets, total, C, gamma, alpha, losses);
     ABR_CHECK_LAUNCH("sigmoid_focal_forward_f64");
     return ABR_OK;
 }
@@ -484,7 +449,7 @@ extern "C" int abr_sigmoid_focal_backward_f64(const double* logits, const int32_
     if (N == 0) return ABR_OK;
     ABR_REQUIRE(logits && targets && d_losses && d_logits, "sigmoid_focal_backward_f64: null pointer");
     const int64_t total = (int64_t)N * C;
-    focal_bwd_f64<<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, abr::as_stream(stream)>>>(logits, targets, d_losses, total, C, gamma, alpha,
+    focal_bwd<double><<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, abr::as_stream(stream)>>>(logits, targets, d_losses, total, C, gamma, alpha,
                                                                                                           d_logits);
     ABR_CHECK_LAUNCH("sigmoid_focal_backward_f64");
     return ABR_OK;

@@ -3,59 +3,57 @@
 //   pack          [n,H,W] uint8 / fp32 -> [n,H,ceil(W/64)] 64-bit words, bit x % 64 of word x / 64 set iff mask == 1
 //   resize + pack BinaryMaskList.resize (structures/segmentation_mask.py:113-135) of uint8 masks, fused: the resized image is never stored
 //   pair counts   |pred & gt| for every (prediction, ground truth) pair of one image, and every mask's own area, in ONE launch
-// A wave covers 64 consecutive pixels of a row and its ballot is the word (wave64).  All three are memory-bound and short.
+// A wave covers 64 consecutive pixels of a row and its ballot is the word (wave64, mask_out.h).  All three are memory-bound and short.
 #include <algorithm>
 
 #include "common.h"
 #include "mask_bilinear.h"
+#include "mask_out.h"
 
 namespace {
 
 constexpr int kPairChunk = 16;   // ground truths whose counts one thread keeps in registers per pass over its predicted words
 
+// the pixel predicates of the two packers (mask_out.h)
+template <typename T>
+struct PackPixel {
+    const T* masks;
+    int H, W;
+    __device__ __forceinline__ void instance(long long) {}
+    __device__ __forceinline__ bool operator()(long long i, int y, int x) const { return masks[(i * H + y) * W + x] == (T)1; }
+};
+
+// a destination pixel: the truncated bilinear sample of the source compared with 1
+struct ResizePixel {
+    const uint8_t* masks;
+    int Hs, Ws;
+    float sh, sw;
+    int four_weight;
+    __device__ __forceinline__ void instance(long long) {}
+    __device__ __forceinline__ bool operator()(long long i, int y, int x) const {
+        int y0, y1, x0, x1;
+        float ly, lx;
+        bilinear_tap(sh, y, Hs, y0, y1, ly);
+        bilinear_tap(sw, x, Ws, x0, x1, lx);
+        const uint8_t* m = masks + i * Hs * Ws;
+        const uint8_t* r0 = m + (int64_t)y0 * Ws;
+        const uint8_t* r1 = m + (int64_t)y1 * Ws;
+        const float v00 = (float)r0[x0], v01 = (float)r0[x1], v10 = (float)r1[x0], v11 = (float)r1[x1];
+        const float v = four_weight ? bilinear_mix(v00, v01, v10, v11, lx, ly) : bilinear_mix_separable(v00, v01, v10, v11, lx, ly);
+        return (unsigned char)(int)v == 1;     // .type_as(uint8 masks) truncates, then masklist_iou's == 1
+    }
+};
+
 template <typename T>
 __global__ __launch_bounds__(256) void mask_pack_bits_kernel(const T* __restrict__ masks, int64_t n_words, int H, int W, int Wq,
                                                              unsigned long long* __restrict__ bits) {
-    const int lane = threadIdx.x & 63;
-    const int64_t n_waves = (int64_t)gridDim.x * 4;
-    for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < n_words; w += n_waves) {   // (wave-uniform)
-        const int q = (int)(w % Wq);
-        const int64_t row = w / Wq;          // = i * H + y
-        const int x = q * 64 + lane;
-        const bool set = x < W && masks[row * W + x] == (T)1;
-        const unsigned long long word = __ballot(set);
-        if (lane == 0) bits[w] = word;
-    }
+    abr::mask_write_bits(PackPixel<T>{masks, H, W}, n_words, H, W, Wq, bits);
 }
 
-// One output word: 64 destination pixels of row y, each the truncated bilinear sample of the source compared with 1.
 __global__ __launch_bounds__(256) void mask_resize_pack_bits_kernel(const uint8_t* __restrict__ masks, int64_t n_words, int Hs, int Ws, int Hd,
                                                                     int Wd, int Wq, float sh, float sw, int four_weight,
                                                                     unsigned long long* __restrict__ bits) {
-    const int lane = threadIdx.x & 63;
-    const int64_t n_waves = (int64_t)gridDim.x * 4;
-    for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < n_words; w += n_waves) {
-        const int q = (int)(w % Wq);
-        const int64_t row = w / Wq;
-        const int y = (int)(row % Hd);
-        const int64_t i = row / Hd;
-        const int x = q * 64 + lane;
-        bool set = false;
-        if (x < Wd) {
-            int y0, y1, x0, x1;
-            float ly, lx;
-            bilinear_tap(sh, y, Hs, y0, y1, ly);
-            bilinear_tap(sw, x, Ws, x0, x1, lx);
-            const uint8_t* m = masks + i * Hs * Ws;
-            const uint8_t* r0 = m + (int64_t)y0 * Ws;
-            const uint8_t* r1 = m + (int64_t)y1 * Ws;
-            const float v00 = (float)r0[x0], v01 = (float)r0[x1], v10 = (float)r1[x0], v11 = (float)r1[x1];
-            const float v = four_weight ? bilinear_mix(v00, v01, v10, v11, lx, ly) : bilinear_mix_separable(v00, v01, v10, v11, lx, ly);
-            set = (unsigned char)(int)v == 1;     // .type_as(uint8 masks) truncates, then masklist_iou's == 1
-        }
-        const unsigned long long word = __ballot(set);
-        if (lane == 0) bits[w] = word;
-    }
+    abr::mask_write_bits(ResizePixel{masks, Hs, Ws, sh, sw, four_weight}, n_words, Hd, Wd, Wq, bits);
 }
 
 __device__ __forceinline__ int block_sum_int(int v, int* s4) {   // 256 threads; every thread returns the total
@@ -117,8 +115,6 @@ __global__ __launch_bounds__(256) void mask_pair_counts_kernel(const unsigned lo
     }
 }
 
-unsigned wave_grid(int64_t n_words) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_words + 3) / 4, 16384)); }
-
 bool image_ok(int H, int W) { return H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31); }
 
 }  // namespace
@@ -132,9 +128,9 @@ extern "C" int abr_mask_pack_bits(const void* masks, int is_u8, int n, int H, in
     hipStream_t st = abr::as_stream(stream);
     auto* out = reinterpret_cast<unsigned long long*>(bits);
     if (is_u8)
-        mask_pack_bits_kernel<uint8_t><<<wave_grid(n_words), 256, 0, st>>>(static_cast<const uint8_t*>(masks), n_words, H, W, Wq, out);
+        mask_pack_bits_kernel<uint8_t><<<abr::wave_grid(n_words), 256, 0, st>>>(static_cast<const uint8_t*>(masks), n_words, H, W, Wq, out);
     else
-        mask_pack_bits_kernel<float><<<wave_grid(n_words), 256, 0, st>>>(static_cast<const float*>(masks), n_words, H, W, Wq, out);
+        mask_pack_bits_kernel<float><<<abr::wave_grid(n_words), 256, 0, st>>>(static_cast<const float*>(masks), n_words, H, W, Wq, out);
     ABR_CHECK_LAUNCH("mask_pack_bits");
     return ABR_OK;
 }
@@ -147,7 +143,7 @@ extern "C" int abr_mask_resize_pack_bits(const uint8_t* masks, int n, int Hs, in
     const int Wq = (Wd + 63) / 64;
     const int64_t n_words = (int64_t)n * Hd * Wq;
     // area_pixel_compute_scale: float(input) / output
-    mask_resize_pack_bits_kernel<<<wave_grid(n_words), 256, 0, abr::as_stream(stream)>>>(masks, n_words, Hs, Ws, Hd, Wd, Wq, (float)Hs / (float)Hd,
+    mask_resize_pack_bits_kernel<<<abr::wave_grid(n_words), 256, 0, abr::as_stream(stream)>>>(masks, n_words, Hs, Ws, Hd, Wd, Wq, (float)Hs / (float)Hd,
                                                                                        (float)Ws / (float)Wd, bilinear_four_weight_path(Hd, Wd) ? 1 : 0,
                                                                                        reinterpret_cast<unsigned long long*>(bits));
     ABR_CHECK_LAUNCH("mask_resize_pack_bits");

@@ -18,7 +18,7 @@
 // are OR-ed into the instance's status word; so L <= 2 * 163841 and every loop below is bounded by the sizes the caller passed.
 //   abr_poly_rasterize     guard (a workgroup per instance) -> toggle planes of h w + 1 bits per polygon, zeroed -> edges: work items are
 //                          (edge, step d) pairs, each compares point d with d - 1 and XORs one bit -> prefix parity along the plane, a
-//                          workgroup per polygon, carried across words -> output: each pixel ORs its instance's planes at x h + y
+//                          workgroup per polygon, carried across words -> output (mask_out.h): each pixel ORs its instance's planes at x h + y
 //   abr_poly_mask_targets  a workgroup per RoI: match the instance (mask_match.h), crop + resize the vertices in registers, the same edge
 //                          walk into an LDS toggle grid per polygon, prefix parity, OR into an LDS accumulator, write [M,M] fp32
 // Safety: offsets are clamped into the buffers as the RLE decoder does; every address written is derived from n, h, w, M and P_max.
@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "mask_match.h"
+#include "mask_out.h"
 
 // every rounding below is part of the definition: one per operation, no fused multiply-add
 #pragma clang fp contract(off)
@@ -39,8 +40,6 @@ constexpr int kEdgeThreads = 256;
 constexpr int kScanThreads = 1024;
 constexpr int kMaxM = 64;                                   // the LDS grid of abr_poly_mask_targets
 constexpr int kMaxWords32 = (kMaxM * kMaxM + 1 + 31) / 32;  // 129
-
-__device__ __forceinline__ i64 clamp64(i64 v, i64 lo, i64 hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ------------------------------------------------------------------------------------------------------------------ the edge walk
 __device__ __forceinline__ int poly_guard(const float c) {
@@ -103,8 +102,8 @@ __device__ __forceinline__ i64 poly_crossing(const int u0, const int v0, const i
 struct PolyRange { i64 lo, hi; };
 __device__ __forceinline__ PolyRange poly_range(const i64* __restrict__ offsets, const i64 k, const i64 limit) {
     PolyRange r;
-    r.lo = clamp64(offsets[k], 0, limit);
-    r.hi = clamp64(offsets[k + 1], r.lo, limit);
+    r.lo = abr::clamp64(offsets[k], 0, limit);
+    r.hi = abr::clamp64(offsets[k + 1], r.lo, limit);
     return r;
 }
 
@@ -193,53 +192,30 @@ __global__ __launch_bounds__(kScanThreads) void poly_parity_kernel(const int32_t
     }
 }
 
-__device__ __forceinline__ bool poly_inst_pixel(const u64* __restrict__ planes, const i64 Cq, const PolyRange pr, const i64 pos) {
-    u64 any = 0;
-    for (i64 p = pr.lo; p < pr.hi; p++) any |= planes[p * Cq + (pos >> 6)] >> (pos & 63);
-    return (any & 1ull) != 0;
-}
+// the pixel predicate of the two outputs (mask_out.h): the OR of the instance's planes at the column-major position x h + y
+struct PolyPixel {
+    const u64* planes;
+    const i64* inst_offsets;
+    i64 n_poly, Cq;
+    int h;
+    PolyRange pr;
+    __device__ __forceinline__ void instance(i64 k) { pr = poly_range(inst_offsets, k, n_poly); }
+    __device__ __forceinline__ bool operator()(i64, int y, int x) const {
+        const i64 pos = (i64)x * h + y;
+        u64 any = 0;
+        for (i64 p = pr.lo; p < pr.hi; p++) any |= planes[p * Cq + (pos >> 6)] >> (pos & 63);
+        return (any & 1ull) != 0;
+    }
+};
 
-// 4 consecutive bytes of the flat [n,h,w] output per thread (rle_fill_u8_kernel's shape)
 __global__ __launch_bounds__(256) void poly_out_u8_kernel(const u64* __restrict__ planes, const i64* __restrict__ inst_offsets, i64 n_poly, i64 Cq, int h, int w,
                                                           i64 numel, uint8_t* __restrict__ out) {
-    const i64 hw = (i64)h * w;
-    const i64 n_quads = (numel + 3) / 4;
-    for (i64 t = (i64)blockIdx.x * 256 + threadIdx.x; t < n_quads; t += (i64)gridDim.x * 256) {
-        uint32_t word = 0;
-        const i64 f0 = t * 4;
-        i64 k_prev = -1;
-        PolyRange pr{0, 0};
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const i64 f = f0 + q;
-            if (f >= numel) break;
-            const i64 k = f / hw;
-            if (k != k_prev) { pr = poly_range(inst_offsets, k, n_poly); k_prev = k; }
-            const int rem = (int)(f - k * hw);
-            const int y = rem / w, x = rem - y * w;
-            word |= (uint32_t)poly_inst_pixel(planes, Cq, pr, (i64)x * h + y) << (8 * q);
-        }
-        if (f0 + 4 <= numel) *reinterpret_cast<uint32_t*>(out + f0) = word;
-        else for (int q = 0; f0 + q < numel; q++) out[f0 + q] = (uint8_t)(word >> (8 * q));
-    }
+    abr::mask_write_u8(PolyPixel{planes, inst_offsets, n_poly, Cq, h, {0, 0}}, numel, h, w, out);
 }
 
-// a wave per output word (abr_mask_pack_bits' layout): lane = pixel, ballot = word
 __global__ __launch_bounds__(256) void poly_out_bits_kernel(const u64* __restrict__ planes, const i64* __restrict__ inst_offsets, i64 n_poly, i64 Cq, int h, int w,
                                                             int Wq, i64 n_words, u64* __restrict__ bits) {
-    const int lane = threadIdx.x & 63;
-    const i64 n_waves = (i64)gridDim.x * 4;
-    for (i64 wd = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); wd < n_words; wd += n_waves) {     // (wave-uniform)
-        const int q = (int)(wd % Wq);
-        const i64 row = wd / Wq;
-        const int y = (int)(row % h);
-        const i64 k = row / h;
-        const PolyRange pr = poly_range(inst_offsets, k, n_poly);
-        const int x = q * 64 + lane;
-        const bool set = x < w && poly_inst_pixel(planes, Cq, pr, (i64)x * h + y);
-        const u64 word = __ballot(set);
-        if (lane == 0) bits[wd] = word;
-    }
+    abr::mask_write_bits(PolyPixel{planes, inst_offsets, n_poly, Cq, h, {0, 0}}, n_words, h, w, Wq, bits);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ M x M targets
@@ -348,7 +324,6 @@ __global__ __launch_bounds__(kEdgeThreads) void poly_targets_kernel(const float*
     }
 }
 
-unsigned wave_grid(int64_t n_words) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_words + 3) / 4, 16384)); }
 bool image_ok(int h, int w) { return h > 0 && w > 0 && (int64_t)h * w < ((int64_t)1 << 31) - 64; }
 int64_t plane_words(int h, int w) { return ((int64_t)h * w + 1 + 63) / 64; }
 int64_t flag_bytes(int64_t n_poly) { return (n_poly * 4 + 7) / 8 * 8; }
@@ -395,14 +370,13 @@ extern "C" int abr_poly_rasterize(const float* coords, const int64_t* poly_offse
     }
     if (masks) {
         const int64_t numel = (int64_t)n * h * w;
-        poly_out_u8_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / 4 + 256) / 256, 65536)), 256, 0, st>>>(planes, ioff, n_poly, Cq, h, w, numel,
-                                                                                                                     masks);
+        poly_out_u8_kernel<<<abr::quad_grid(numel), 256, 0, st>>>(planes, ioff, n_poly, Cq, h, w, numel, masks);
         ABR_CHECK_LAUNCH("poly_rasterize (masks)");
     }
     if (bits) {
         const int Wq = (w + 63) / 64;
         const int64_t n_words = (int64_t)n * h * Wq;
-        poly_out_bits_kernel<<<wave_grid(n_words), 256, 0, st>>>(planes, ioff, n_poly, Cq, h, w, Wq, n_words, reinterpret_cast<u64*>(bits));
+        poly_out_bits_kernel<<<abr::wave_grid(n_words), 256, 0, st>>>(planes, ioff, n_poly, Cq, h, w, Wq, n_words, reinterpret_cast<u64*>(bits));
         ABR_CHECK_LAUNCH("poly_rasterize (bits)");
     }
     return ABR_OK;

@@ -5,8 +5,8 @@
 //            "more follows", bit 0x10 of the last character = sign, character = value + 48
 //   decode   rle_scan_kernel, ONE workgroup per instance: token ends from the 0x20 bit -> block scan = token index -> the thread on a token's
 //            last character assembles it -> two interleaved prefix sums (even / odd indices) undo the delta -> prefix sum = run ends.
-//            rle_fill_*_kernel, the whole grid: every output pixel (a wave per 64-pixel word for the packed form) finds its run by a binary
-//            search of the run ends at its column-major index and takes the run's parity; writes are row-major and coalesced.
+//            rle_fill_*_kernel, the whole grid: every output pixel finds its run by a binary search of the run ends at its column-major
+//            index and takes the run's parity; the packed words and the row-major bytes are written by mask_out.h's two loops.
 //   encode   rle_colbits_kernel: the masks as bits in column-major order (a wave's ballot per 64 pixels); rle_runs_kernel, one workgroup per
 //            instance: transitions = word ^ (word << 1 | previous word's top bit), popcount + block scan = compaction of the run starts, then
 //            counts -> deltas -> characters per token -> block sum = the instance's bytes; rle_offsets_kernel: prefix sum over instances;
@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mask_out.h"
 
 namespace {
 
@@ -54,8 +55,6 @@ __device__ __forceinline__ i64 block_scan_incl(i64 v, i64* sm, i64& total) {
     return v + before;
 }
 
-__device__ __forceinline__ i64 clamp64(i64 v, i64 lo, i64 hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // ------------------------------------------------------------------------------------------------------------------------------- decode
 // vals: int32 [n_items] workspace, item j of instance k at offsets[k] + j.  compressed: items are bytes -> stored values -> run ends, in place;
 // else: items are the counts (`counts`), run ends written to vals.  nruns[k], totals[k]: see the header.
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(kScanThreads) void rle_scan_kernel(const uint8_t* _
     __shared__ i64 sm[16];
     __shared__ int s_err;
     const int k = blockIdx.x, tid = threadIdx.x;
-    const i64 lo = clamp64(offsets[k], 0, n_items), hi = clamp64(offsets[k + 1], lo, n_items);
+    const i64 lo = abr::clamp64(offsets[k], 0, n_items), hi = abr::clamp64(offsets[k + 1], lo, n_items);
     const i64 len = hi - lo;
     int32_t* v = vals + lo;
     if (tid == 0) s_err = 0;
@@ -149,56 +148,35 @@ __device__ __forceinline__ int rle_pixel(const int32_t* __restrict__ ends, int n
 
 struct RleInst { const int32_t* ends; int nr; };
 __device__ __forceinline__ RleInst rle_inst(const int32_t* vals, const i64* offsets, const int32_t* nruns, const i64* totals, i64 n_items, i64 hw, i64 k) {
-    const i64 lo = clamp64(offsets[k], 0, n_items), hi = clamp64(offsets[k + 1], lo, n_items);
+    const i64 lo = abr::clamp64(offsets[k], 0, n_items), hi = abr::clamp64(offsets[k + 1], lo, n_items);
     RleInst r;
     r.ends = vals + lo;
     r.nr = totals[k] == hw ? (int)min((i64)nruns[k], hi - lo) : 0;      // malformed: no run ends, every pixel 0
     return r;
 }
 
-// 4 consecutive bytes of the flat [n,h,w] output per thread, one dword store; the (numel % 4) tail bytes by the last threads
+// the pixel predicate of the two fills (mask_out.h): the run ends of the instance, fetched once per instance, searched at x * h + y
+struct RlePixel {
+    const int32_t* vals;
+    const i64* offsets;
+    const int32_t* nruns;
+    const i64* totals;
+    i64 n_items, hw;
+    int h;
+    RleInst r;
+    __device__ __forceinline__ void instance(i64 k) { r = rle_inst(vals, offsets, nruns, totals, n_items, hw, k); }
+    __device__ __forceinline__ bool operator()(i64, int y, int x) const { return rle_pixel(r.ends, r.nr, x * h + y) != 0; }
+};
+
 __global__ __launch_bounds__(256) void rle_fill_u8_kernel(const int32_t* __restrict__ vals, const i64* __restrict__ offsets, const int32_t* __restrict__ nruns,
                                                           const i64* __restrict__ totals, i64 n_items, int h, int w, i64 numel, uint8_t* __restrict__ out) {
-    const i64 hw = (i64)h * w;
-    const i64 n_quads = (numel + 3) / 4;
-    for (i64 t = (i64)blockIdx.x * 256 + threadIdx.x; t < n_quads; t += (i64)gridDim.x * 256) {
-        uint32_t word = 0;
-        const i64 f0 = t * 4;
-        i64 k_prev = -1;
-        RleInst r{nullptr, 0};
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const i64 f = f0 + q;
-            if (f >= numel) break;
-            const i64 k = f / hw;
-            if (k != k_prev) { r = rle_inst(vals, offsets, nruns, totals, n_items, hw, k); k_prev = k; }
-            const int rem = (int)(f - k * hw);
-            const int y = rem / w, x = rem - y * w;
-            word |= (uint32_t)rle_pixel(r.ends, r.nr, x * h + y) << (8 * q);
-        }
-        if (f0 + 4 <= numel) *reinterpret_cast<uint32_t*>(out + f0) = word;
-        else for (int q = 0; f0 + q < numel; q++) out[f0 + q] = (uint8_t)(word >> (8 * q));
-    }
+    abr::mask_write_u8(RlePixel{vals, offsets, nruns, totals, n_items, (i64)h * w, h, {nullptr, 0}}, numel, h, w, out);
 }
 
-// a wave per output word (ops.mask_pack_bits' layout): lane = pixel, ballot = word
 __global__ __launch_bounds__(256) void rle_fill_bits_kernel(const int32_t* __restrict__ vals, const i64* __restrict__ offsets, const int32_t* __restrict__ nruns,
                                                             const i64* __restrict__ totals, i64 n_items, int h, int w, int Wq, i64 n_words,
                                                             unsigned long long* __restrict__ bits) {
-    const int lane = threadIdx.x & 63;
-    const i64 hw = (i64)h * w;
-    const i64 n_waves = (i64)gridDim.x * 4;
-    for (i64 wd = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); wd < n_words; wd += n_waves) {     // (wave-uniform)
-        const int q = (int)(wd % Wq);
-        const i64 row = wd / Wq;
-        const int y = (int)(row % h);
-        const i64 k = row / h;
-        const RleInst r = rle_inst(vals, offsets, nruns, totals, n_items, hw, k);
-        const int x = q * 64 + lane;
-        const bool set = x < w && rle_pixel(r.ends, r.nr, x * h + y) != 0;
-        const unsigned long long word = __ballot(set);
-        if (lane == 0) bits[wd] = word;
-    }
+    abr::mask_write_bits(RlePixel{vals, offsets, nruns, totals, n_items, (i64)h * w, h, {nullptr, 0}}, n_words, h, w, Wq, bits);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------- encode
@@ -303,7 +281,7 @@ __global__ __launch_bounds__(kScanThreads) void rle_emit_kernel(const int32_t* _
     const int k = blockIdx.x, tid = threadIdx.x;
     if (offsets[n] > capacity) return;                       // all or nothing: the caller reads offsets[n] and comes back with room
     const int32_t* T = starts + (i64)k * hw;
-    const i64 nt = clamp64((i64)nruns[k] - 1, 0, hw);
+    const i64 nt = abr::clamp64((i64)nruns[k] - 1, 0, hw);
     const i64 lo = offsets[k], hi = offsets[k + 1];
     i64 carry = lo;
     for (i64 base = 0; base <= nt; base += kScanThreads) {
@@ -327,7 +305,6 @@ __global__ __launch_bounds__(kScanThreads) void rle_emit_kernel(const int32_t* _
     }
 }
 
-unsigned wave_grid(int64_t n_words) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_words + 3) / 4, 16384)); }
 bool image_ok(int h, int w) { return h > 0 && w > 0 && (int64_t)h * w < ((int64_t)1 << 31); }
 
 struct EncodeWs { size_t colbits, starts, nbytes, total; };
@@ -372,14 +349,13 @@ extern "C" int abr_rle_decode(const uint8_t* bytes, const int32_t* counts, const
     ABR_CHECK_LAUNCH("rle_decode (scan)");
     if (masks) {
         const int64_t numel = (int64_t)n * hw;
-        rle_fill_u8_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / 4 + 256) / 256, 65536)), 256, 0, st>>>(vals, off, nruns, tot, n_items, h, w,
-                                                                                                                     numel, masks);
+        rle_fill_u8_kernel<<<abr::quad_grid(numel), 256, 0, st>>>(vals, off, nruns, tot, n_items, h, w, numel, masks);
         ABR_CHECK_LAUNCH("rle_decode (fill)");
     }
     if (bits) {
         const int Wq = (w + 63) / 64;
         const int64_t n_words = (int64_t)n * h * Wq;
-        rle_fill_bits_kernel<<<wave_grid(n_words), 256, 0, st>>>(vals, off, nruns, tot, n_items, h, w, Wq, n_words, reinterpret_cast<unsigned long long*>(bits));
+        rle_fill_bits_kernel<<<abr::wave_grid(n_words), 256, 0, st>>>(vals, off, nruns, tot, n_items, h, w, Wq, n_words, reinterpret_cast<unsigned long long*>(bits));
         ABR_CHECK_LAUNCH("rle_decode (fill bits)");
     }
     return ABR_OK;
@@ -412,7 +388,7 @@ extern "C" int abr_rle_encode(const uint8_t* masks, const uint64_t* bits, int n,
     auto* starts = reinterpret_cast<int32_t*>(ws + e.starts);
     auto* nbytes = reinterpret_cast<i64*>(ws + e.nbytes);
     const int64_t hw = (int64_t)h * w, Cq = (hw + 63) / 64;
-    rle_colbits_kernel<<<wave_grid(n * Cq), 256, 0, st>>>(masks, reinterpret_cast<const unsigned long long*>(bits), h, w, (w + 63) / 64, Cq, n * Cq, colbits);
+    rle_colbits_kernel<<<abr::wave_grid(n * Cq), 256, 0, st>>>(masks, reinterpret_cast<const unsigned long long*>(bits), h, w, (w + 63) / 64, Cq, n * Cq, colbits);
     ABR_CHECK_LAUNCH("rle_encode (column-major bits)");
     rle_runs_kernel<<<n, kScanThreads, 0, st>>>(colbits, Cq, hw, starts, nruns, nbytes);
     ABR_CHECK_LAUNCH("rle_encode (runs)");

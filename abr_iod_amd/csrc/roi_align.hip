@@ -22,49 +22,57 @@
 
 namespace {
 
+// The sampling geometry, once, for T = float (every kernel below) and T = double (the NCHW pair's float64 entry points): the reference
+// dispatches float AND double (AT_DISPATCH_FLOATING_TYPES, ROIAlign_cuda.cu:283,329; ROIAlign_cpu.cpp:242), and its templates give the same
+// arithmetic with every T -- coordinates, weights and accumulation in T, the (i + .5f) sample offset a float literal converted to T
+// (ROIAlign_cuda.cu:104-109).
+template <typename T>
 struct RoiGeom {
-    float y0, x0, bh, bw;
+    T y0, x0, bh, bw;
     int gh, gw, b;
 };
 
+template <typename T>
 struct Tap {
     int p0, p1, p2, p3;  // flat y*W+x, or -1 when the sample is rejected
-    float w0, w1, w2, w3;
+    T w0, w1, w2, w3;
 };
 
 #pragma clang fp contract(off)
-__device__ __forceinline__ RoiGeom roi_geom(const float* __restrict__ r, float scale, int PH, int PW, int sr) {
-    RoiGeom g;
+template <typename T>
+__device__ __forceinline__ RoiGeom<T> roi_geom(const T* __restrict__ r, T scale, int PH, int PW, int sr) {
+    RoiGeom<T> g;
     g.b = (int)r[0];
-    const float sw = r[1] * scale, sh = r[2] * scale, ew = r[3] * scale, eh = r[4] * scale;  // no rounding
-    const float rw = fmaxf(ew - sw, 1.f), rh = fmaxf(eh - sh, 1.f);                          // malformed -> 1x1
+    const T sw = r[1] * scale, sh = r[2] * scale, ew = r[3] * scale, eh = r[4] * scale;  // no rounding
+    const T rw = fmax(ew - sw, (T)1), rh = fmax(eh - sh, (T)1);                          // malformed -> 1x1 (fmax / ceil: the overload of T)
     g.x0 = sw;
     g.y0 = sh;
-    g.bh = rh / (float)PH;
-    g.bw = rw / (float)PW;
-    g.gh = sr > 0 ? sr : (int)ceilf(rh / (float)PH);
-    g.gw = sr > 0 ? sr : (int)ceilf(rw / (float)PW);
+    g.bh = rh / (T)PH;
+    g.bw = rw / (T)PW;
+    g.gh = sr > 0 ? sr : (int)ceil(rh / (T)PH);
+    g.gw = sr > 0 ? sr : (int)ceil(rw / (T)PW);
     return g;
 }
 
 #pragma clang fp contract(off)
-__device__ __forceinline__ Tap make_tap(const RoiGeom& g, int H, int W, int ph, int pw, int iy, int ix) {
+template <typename T>
+__device__ __forceinline__ Tap<T> make_tap(const RoiGeom<T>& g, int H, int W, int ph, int pw, int iy, int ix) {
     // start + ph*bin + ((i+.5)*bin)/grid  -- keep exactly this association (ROIAlign_cpu.cpp:39-45)
-    float y = g.y0 + ph * g.bh + (float)(iy + .5f) * g.bh / (float)g.gh;
-    float x = g.x0 + pw * g.bw + (float)(ix + .5f) * g.bw / (float)g.gw;
-    Tap t;
-    if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) {
+    T y = g.y0 + ph * g.bh + (T)(iy + .5f) * g.bh / (T)g.gh;
+    T x = g.x0 + pw * g.bw + (T)(ix + .5f) * g.bw / (T)g.gw;
+    Tap<T> t;
+    if (y < (T)-1 || y > (T)H || x < (T)-1 || x > (T)W) {
         t.p0 = t.p1 = t.p2 = t.p3 = -1;
-        t.w0 = t.w1 = t.w2 = t.w3 = 0.f;
+        t.w0 = t.w1 = t.w2 = t.w3 = 0;
         return t;
     }
     if (y <= 0) y = 0;
     if (x <= 0) x = 0;
     int yl = (int)y, xl = (int)x, yh, xh;
-    if (yl >= H - 1) { yh = yl = H - 1; y = (float)yl; } else yh = yl + 1;
-    if (xl >= W - 1) { xh = xl = W - 1; x = (float)xl; } else xh = xl + 1;
-    const float ly = y - yl, lx = x - xl;
-    const float hy = 1.f - ly, hx = 1.f - lx;
+    if (yl >= H - 1) { yh = yl = H - 1; y = (T)yl; } else yh = yl + 1;
+    if (xl >= W - 1) { xh = xl = W - 1; x = (T)xl; } else xh = xl + 1;
+    const T ly = y - yl, lx = x - xl;
+    const T hy = (T)1 - ly, hx = (T)1 - lx;
     t.w0 = hy * hx; t.w1 = hy * lx; t.w2 = ly * hx; t.w3 = ly * lx;
     t.p0 = yl * W + xl; t.p1 = yl * W + xh; t.p2 = yh * W + xl; t.p3 = yh * W + xh;
     return t;
@@ -99,7 +107,7 @@ __global__ __launch_bounds__(256) void roi_align_fwd_nhwc(const float* __restric
     const int nbins = PHo * PWo;
     const int tch = 256 / bpb;  // samples per chunk per bin
 
-    const RoiGeom g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+    const RoiGeom<float> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
     const int ns = g.gh * g.gw;
     const float count = (float)ns;
 
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(256) void roi_align_fwd_nhwc(const float* __restric
             __syncthreads();
             {
                 const int s = sb + es;
-                Tap t;
+                Tap<float> t;
                 if (s < ns && ebin < nbins) {
                     t = make_tap(g, H, W, eph, epw, s / g.gw, s % g.gw);
                 } else {
@@ -187,7 +195,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float* __restric
     const int nbins = PHo * PWo;
     const int tch = 256 / bpb;
 
-    const RoiGeom g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+    const RoiGeom<float> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
     const int ns = g.gh * g.gw;
     const float count = (float)ns;
 
@@ -212,7 +220,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float* __restric
             __syncthreads();
             {
                 const int s = sb + es;
-                Tap t;
+                Tap<float> t;
                 if (s < ns && ebin < nbins) {
                     t = make_tap(g, H, W, eph, epw, s / g.gw, s % g.gw);
                 } else {
@@ -286,7 +294,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc_sep(const float* __res
     int* rng = reinterpret_cast<int*>(Wx + PWo * W);  // ymin, ymax, xmin, xmax
     const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
     const int n = bid / cchunks, chunk = bid % cchunks;
-    const RoiGeom g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+    const RoiGeom<float> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
     const float inv_count = 1.f / (float)(g.gh * g.gw);
 
     for (int i = threadIdx.x; i < PHo * H + PWo * W; i += 256) sm[i] = 0.f;
@@ -395,7 +403,7 @@ __global__ __launch_bounds__(64) void roi_bwd_tables_kernel(const float* __restr
     float* sx = sm + PHo * H;   // [PWo][Wp]
     int* rng = reinterpret_cast<int*>(sx + PWo * Wp);
     const int n = blockIdx.x;
-    const RoiGeom g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+    const RoiGeom<float> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
     const float inv_count = 1.f / (float)(g.gh * g.gw);
     for (int i = threadIdx.x; i < PHo * H + PWo * Wp; i += 64) sm[i] = 0.f;
     if (threadIdx.x == 0) { rng[0] = H; rng[1] = -1; rng[2] = W; rng[3] = -1; }
@@ -662,126 +670,41 @@ __global__ __launch_bounds__(256) void roi_align_bwd_gather_kernel(const float* 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// NCHW compatibility kernels (the reference's own tensor layout; drop-in for `_C.roi_align_*`).
+// NCHW compatibility kernels (the reference's own tensor layout; drop-in for `_C.roi_align_*`), for T = float and T = double.
 // One thread per (n, c, ph, pw) like the reference; pw fastest so a wave reads neighbouring taps.
 // ---------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
-__global__ __launch_bounds__(256) void roi_align_fwd_nchw(const float* __restrict__ feat, const float* __restrict__ rois,
-                                                           int64_t total, int C, int H, int W, float scale, int PH,
-                                                           int PW, int sr, float* __restrict__ out) {
+template <typename T>
+__global__ __launch_bounds__(256) void roi_align_fwd_nchw(const T* __restrict__ feat, const T* __restrict__ rois, int64_t total, int C, int H, int W,
+                                                           T scale, int PH, int PW, int sr, T* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int pw = i % PW, ph = (i / PW) % PH, c = (i / PW / PH) % C, n = i / PW / PH / C;
-        const RoiGeom g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
-        const float* plane = feat + ((size_t)g.b * C + c) * H * W;
-        float acc = 0.f;
+        const RoiGeom<T> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+        const T* plane = feat + ((size_t)g.b * C + c) * H * W;
+        T acc = 0;
         for (int iy = 0; iy < g.gh; iy++)
             for (int ix = 0; ix < g.gw; ix++) {
-                const Tap t = make_tap(g, H, W, ph, pw, iy, ix);
+                const Tap<T> t = make_tap(g, H, W, ph, pw, iy, ix);
                 if (t.p0 < 0) continue;
                 acc += t.w0 * plane[t.p0] + t.w1 * plane[t.p1] + t.w2 * plane[t.p2] + t.w3 * plane[t.p3];
             }
-        out[i] = acc / (float)(g.gh * g.gw);
+        out[i] = acc / (T)(g.gh * g.gw);
     }
 }
 
 #pragma clang fp contract(off)
-__global__ __launch_bounds__(256) void roi_align_bwd_nchw(const float* __restrict__ grad, const float* __restrict__ rois,
-                                                           int64_t total, int C, int H, int W, float scale, int PH,
-                                                           int PW, int sr, float* __restrict__ gfeat) {
+template <typename T>
+__global__ __launch_bounds__(256) void roi_align_bwd_nchw(const T* __restrict__ grad, const T* __restrict__ rois, int64_t total, int C, int H, int W,
+                                                           T scale, int PH, int PW, int sr, T* __restrict__ gfeat) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int pw = i % PW, ph = (i / PW) % PH, c = (i / PW / PH) % C, n = i / PW / PH / C;
-        const RoiGeom g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
-        float* plane = gfeat + ((size_t)g.b * C + c) * H * W;
-        const float gv = grad[i];
-        const float count = (float)(g.gh * g.gw);
+        const RoiGeom<T> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+        T* plane = gfeat + ((size_t)g.b * C + c) * H * W;
+        const T gv = grad[i];
+        const T count = (T)(g.gh * g.gw);
         for (int iy = 0; iy < g.gh; iy++)
             for (int ix = 0; ix < g.gw; ix++) {
-                const Tap t = make_tap(g, H, W, ph, pw, iy, ix);
-                if (t.p0 < 0) continue;
-                unsafeAtomicAdd(plane + t.p0, gv * t.w0 / count);
-                unsafeAtomicAdd(plane + t.p1, gv * t.w1 / count);
-                unsafeAtomicAdd(plane + t.p2, gv * t.w2 / count);
-                unsafeAtomicAdd(plane + t.p3, gv * t.w3 / count);
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// float64 instantiation of the NCHW pair: the reference dispatches float AND double (AT_DISPATCH_FLOATING_TYPES, ROIAlign_cuda.cu:283,329;
-// ROIAlign_cpu.cpp:242).  The same arithmetic with every T = double, as the reference's templates give it: coordinates, weights and the
-// accumulation in double, the (i + .5f) sample offset a float literal converted to T (ROIAlign_cuda.cu:104-109).
-// ---------------------------------------------------------------------------------------------------
-struct RoiGeomD {
-    double y0, x0, bh, bw;
-    int gh, gw, b;
-};
-#pragma clang fp contract(off)
-__device__ __forceinline__ RoiGeomD roi_geom_d(const double* __restrict__ r, double scale, int PH, int PW, int sr) {
-    RoiGeomD g;
-    g.b = (int)r[0];
-    const double sw = r[1] * scale, sh = r[2] * scale, ew = r[3] * scale, eh = r[4] * scale;
-    const double rw = fmax(ew - sw, 1.), rh = fmax(eh - sh, 1.);
-    g.x0 = sw; g.y0 = sh;
-    g.bh = rh / (double)PH;
-    g.bw = rw / (double)PW;
-    g.gh = sr > 0 ? sr : (int)ceil(rh / (double)PH);
-    g.gw = sr > 0 ? sr : (int)ceil(rw / (double)PW);
-    return g;
-}
-struct TapD {
-    int p0, p1, p2, p3;
-    double w0, w1, w2, w3;
-};
-#pragma clang fp contract(off)
-__device__ __forceinline__ TapD make_tap_d(const RoiGeomD& g, int H, int W, int ph, int pw, int iy, int ix) {
-    double y = g.y0 + ph * g.bh + (double)(iy + .5f) * g.bh / (double)g.gh;
-    double x = g.x0 + pw * g.bw + (double)(ix + .5f) * g.bw / (double)g.gw;
-    TapD t;
-    if (y < -1.0 || y > (double)H || x < -1.0 || x > (double)W) {
-        t.p0 = t.p1 = t.p2 = t.p3 = -1;
-        t.w0 = t.w1 = t.w2 = t.w3 = 0.;
-        return t;
-    }
-    if (y <= 0) y = 0;
-    if (x <= 0) x = 0;
-    int yl = (int)y, xl = (int)x, yh, xh;
-    if (yl >= H - 1) { yh = yl = H - 1; y = (double)yl; } else yh = yl + 1;
-    if (xl >= W - 1) { xh = xl = W - 1; x = (double)xl; } else xh = xl + 1;
-    const double ly = y - yl, lx = x - xl;
-    const double hy = 1. - ly, hx = 1. - lx;
-    t.w0 = hy * hx; t.w1 = hy * lx; t.w2 = ly * hx; t.w3 = ly * lx;
-    t.p0 = yl * W + xl; t.p1 = yl * W + xh; t.p2 = yh * W + xl; t.p3 = yh * W + xh;
-    return t;
-}
-#pragma clang fp contract(off)
-__global__ __launch_bounds__(256) void roi_align_fwd_nchw_f64(const double* __restrict__ feat, const double* __restrict__ rois, int64_t total, int C,
-                                                               int H, int W, double scale, int PH, int PW, int sr, double* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int pw = i % PW, ph = (i / PW) % PH, c = (i / PW / PH) % C, n = i / PW / PH / C;
-        const RoiGeomD g = roi_geom_d(rois + 5 * (size_t)n, scale, PH, PW, sr);
-        const double* plane = feat + ((size_t)g.b * C + c) * H * W;
-        double acc = 0.;
-        for (int iy = 0; iy < g.gh; iy++)
-            for (int ix = 0; ix < g.gw; ix++) {
-                const TapD t = make_tap_d(g, H, W, ph, pw, iy, ix);
-                if (t.p0 < 0) continue;
-                acc += t.w0 * plane[t.p0] + t.w1 * plane[t.p1] + t.w2 * plane[t.p2] + t.w3 * plane[t.p3];
-            }
-        out[i] = acc / (double)(g.gh * g.gw);
-    }
-}
-#pragma clang fp contract(off)
-__global__ __launch_bounds__(256) void roi_align_bwd_nchw_f64(const double* __restrict__ grad, const double* __restrict__ rois, int64_t total, int C,
-                                                               int H, int W, double scale, int PH, int PW, int sr, double* __restrict__ gfeat) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int pw = i % PW, ph = (i / PW) % PH, c = (i / PW / PH) % C, n = i / PW / PH / C;
-        const RoiGeomD g = roi_geom_d(rois + 5 * (size_t)n, scale, PH, PW, sr);
-        double* plane = gfeat + ((size_t)g.b * C + c) * H * W;
-        const double gv = grad[i];
-        const double count = (double)(g.gh * g.gw);
-        for (int iy = 0; iy < g.gh; iy++)
-            for (int ix = 0; ix < g.gw; ix++) {
-                const TapD t = make_tap_d(g, H, W, ph, pw, iy, ix);
+                const Tap<T> t = make_tap(g, H, W, ph, pw, iy, ix);
                 if (t.p0 < 0) continue;
                 unsafeAtomicAdd(plane + t.p0, gv * t.w0 / count);
                 unsafeAtomicAdd(plane + t.p1, gv * t.w1 / count);
@@ -796,11 +719,11 @@ __global__ void roi_align_taps_kernel(const float* __restrict__ rois, int K, int
     const int64_t total = (int64_t)K * PH * PW * max_s;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int s = i % max_s, pw = (i / max_s) % PW, ph = (i / max_s / PW) % PH, n = i / max_s / PW / PH;
-        const RoiGeom g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+        const RoiGeom<float> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
         if (s == 0 && ph == 0 && pw == 0) { grid[2 * n] = g.gh; grid[2 * n + 1] = g.gw; }
         int32_t* o = idx + i * 4;
         if (s >= g.gh * g.gw) { o[0] = o[1] = o[2] = o[3] = -2; continue; }
-        const Tap t = make_tap(g, H, W, ph, pw, s / g.gw, s % g.gw);
+        const Tap<float> t = make_tap(g, H, W, ph, pw, s / g.gw, s % g.gw);
         o[0] = t.p0; o[1] = t.p1; o[2] = t.p2; o[3] = t.p3;
     }
 }
@@ -820,6 +743,17 @@ void pick_shape(int cvecs, int nbins, int* tx, int* bpb) {
     *bpb = b;
 }
 
+// the NCHW pair's launch (forward or backward, float or double): one thread per (n, c, ph, pw), grid-stride
+template <typename T>
+int launch_nchw(void (*kernel)(const T*, const T*, int64_t, int, int, int, T, int, int, int, T*), const char* name, const T* in, const T* rois, int K,
+                int C, int H, int W, T scale, int PH, int PW, int sr, T* out, hipStream_t st) {
+    const int64_t total = (int64_t)K * C * PH * PW;
+    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
+    kernel<<<grid, 256, 0, st>>>(in, rois, total, C, H, W, scale, PH, PW, sr, out);
+    ABR_CHECK_LAUNCH(name);
+    return ABR_OK;
+}
+
 }  // namespace
 
 extern "C" int abr_roi_align_forward(const float* feat, const float* rois, int K, int B, int C, int H, int W,
@@ -833,9 +767,7 @@ extern "C" int abr_roi_align_forward(const float* feat, const float* rois, int K
     hipStream_t st = abr::as_stream(stream);
     if (layout == ABR_NCHW) {
         ABR_REQUIRE(bin_step == 1, "roi_align_forward: bin_step>1 needs NHWC");
-        const int64_t total = (int64_t)K * C * PH * PW;
-        const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-        roi_align_fwd_nchw<<<grid, 256, 0, st>>>(feat, rois, total, C, H, W, scale, PH, PW, sr, out);
+        return launch_nchw(roi_align_fwd_nchw<float>, "roi_align_forward", feat, rois, K, C, H, W, scale, PH, PW, sr, out, st);
     } else {
         const int PHo = (PH + bin_step - 1) / bin_step, PWo = (PW + bin_step - 1) / bin_step;
         const int nbins = PHo * PWo;
@@ -876,9 +808,7 @@ extern "C" int abr_roi_align_backward(const float* grad, const float* rois, int 
     ABR_REQUIRE(grad && rois, "roi_align_backward: null pointer");
     if (layout == ABR_NCHW) {
         ABR_REQUIRE(bin_step == 1, "roi_align_backward: bin_step>1 needs NHWC");
-        const int64_t total = (int64_t)K * C * PH * PW;
-        const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-        roi_align_bwd_nchw<<<grid, 256, 0, st>>>(grad, rois, total, C, H, W, scale, PH, PW, sr, gfeat);
+        return launch_nchw(roi_align_bwd_nchw<float>, "roi_align_backward", grad, rois, K, C, H, W, scale, PH, PW, sr, gfeat, st);
     } else {
         const int PHo = (PH + bin_step - 1) / bin_step, PWo = (PW + bin_step - 1) / bin_step;
         const int nbins = PHo * PWo;
@@ -918,11 +848,7 @@ extern "C" int abr_roi_align_forward_f64(const double* feat, const double* rois,
     ABR_REQUIRE(K >= 0 && B > 0 && C > 0 && H > 0 && W > 0 && PH > 0 && PW > 0, "roi_align_forward_f64: bad shape");
     if (K == 0) return ABR_OK;
     ABR_REQUIRE(feat && rois && out, "roi_align_forward_f64: null pointer");
-    const int64_t total = (int64_t)K * C * PH * PW;
-    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-    roi_align_fwd_nchw_f64<<<grid, 256, 0, abr::as_stream(stream)>>>(feat, rois, total, C, H, W, scale, PH, PW, sr, out);
-    ABR_CHECK_LAUNCH("roi_align_forward_f64");
-    return ABR_OK;
+    return launch_nchw(roi_align_fwd_nchw<double>, "roi_align_forward_f64", feat, rois, K, C, H, W, scale, PH, PW, sr, out, abr::as_stream(stream));
 }
 
 extern "C" int abr_roi_align_backward_f64(const double* grad, const double* rois, int K, int B, int C, int H, int W, double scale, int PH, int PW,
@@ -936,11 +862,7 @@ extern "C" int abr_roi_align_backward_f64(const double* grad, const double* rois
     }
     if (K == 0) return ABR_OK;
     ABR_REQUIRE(grad && rois, "roi_align_backward_f64: null pointer");
-    const int64_t total = (int64_t)K * C * PH * PW;
-    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-    roi_align_bwd_nchw_f64<<<grid, 256, 0, st>>>(grad, rois, total, C, H, W, scale, PH, PW, sr, gfeat);
-    ABR_CHECK_LAUNCH("roi_align_backward_f64");
-    return ABR_OK;
+    return launch_nchw(roi_align_bwd_nchw<double>, "roi_align_backward_f64", grad, rois, K, C, H, W, scale, PH, PW, sr, gfeat, st);
 }
 
 static inline int round8(int w) { return (w + 7) / 8 * 8; }

@@ -50,17 +50,6 @@ __global__ void decode_clip_kernel(const float* __restrict__ reg, int reg_stride
     }
 }
 
-#pragma clang fp contract(off)
-__device__ __forceinline__ float box_iou(const float4 g, const float4 b) {
-    // structures/boxlist_ops.py:53-88, TO_REMOVE = 1
-    const float area1 = (g.z - g.x + 1) * (g.w - g.y + 1);
-    const float area2 = (b.z - b.x + 1) * (b.w - b.y + 1);
-    const float lx = fmaxf(g.x, b.x), ly = fmaxf(g.y, b.y), rx = fminf(g.z, b.z), ry = fminf(g.w, b.w);
-    const float w = fmaxf(rx - lx + 1, 0.f), h = fmaxf(ry - ly + 1, 0.f);
-    const float inter = w * h;
-    return inter / (area1 + area2 - inter);
-}
-
 // pass 1: per-gt maximum IoU over all boxes (needed only for Matcher.set_low_quality_matches_, matcher.py:83-112)
 // maximum over a 256-thread workgroup (all threads call; s_m: 4 floats).  ONE atomic per workgroup and ground-truth box then goes to the
 // shared word: with one per WAVE, the ~560 waves of the RPN call queued on a handful of addresses (80 us for 35 910 anchors x 5 boxes)
@@ -79,7 +68,7 @@ __global__ __launch_bounds__(256) void gt_max_iou_kernel(const float* __restrict
         const float4 gb = reinterpret_cast<const float4*>(gt)[g];
         float m = 0.f;
         for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
-            m = fmaxf(m, box_iou(gb, reinterpret_cast<const float4*>(boxes)[j]));
+            m = fmaxf(m, abr::box_iou(gb, reinterpret_cast<const float4*>(boxes)[j]));
         m = block_max_256(m, s_m);
         if (threadIdx.x == 0) atomicMax(rowmax + g, __float_as_uint(m));  // IoU >= 0: bit pattern is monotone
     }
@@ -97,7 +86,7 @@ __global__ void match_encode_kernel(const float* __restrict__ boxes, int n, cons
         int bi = 0;
         bool lq = false;
         for (int g = 0; g < G; g++) {
-            const float v = box_iou(reinterpret_cast<const float4*>(gt)[g], b);
+            const float v = abr::box_iou(reinterpret_cast<const float4*>(gt)[g], b);
             if (v > best) { best = v; bi = g; }                                    // first max wins (torch.max)
             if (allow_lq && v == __uint_as_float(rowmax[g])) lq = true;
         }
@@ -171,7 +160,7 @@ __global__ void cand_match_kernel(const float* __restrict__ props, const float* 
     float best = -1.f;
     int bi = 0;
     for (int g = 0; g < G; g++) {
-        const float v = box_iou(reinterpret_cast<const float4*>(gt)[g], b);
+        const float v = abr::box_iou(reinterpret_cast<const float4*>(gt)[g], b);
         if (v > best) { best = v; bi = g; }                                    // first max wins (torch.max)
     }
     const int64_t m = best < lo ? -1 : (best < hi ? -2 : bi);                   // matcher.py:68-75
@@ -282,7 +271,7 @@ __global__ __launch_bounds__(256) void gt_max_iou_batched_kernel(const float* __
         const float4 gb = reinterpret_cast<const float4*>(gt)[g];
         float m = 0.f;
         for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
-            m = fmaxf(m, box_iou(gb, reinterpret_cast<const float4*>(boxes)[j]));
+            m = fmaxf(m, abr::box_iou(gb, reinterpret_cast<const float4*>(boxes)[j]));
         m = block_max_256(m, s_m);
         if (threadIdx.x == 0) atomicMax(rowmax + (size_t)i * g_max + g, __float_as_uint(m));
     }
@@ -304,7 +293,7 @@ __global__ void rpn_match_batched_kernel(const float* __restrict__ boxes, int n,
         int bi = 0;
         bool lq = false;
         for (int g = 0; g < G; g++) {
-            const float v = box_iou(reinterpret_cast<const float4*>(gt)[g], b);
+            const float v = abr::box_iou(reinterpret_cast<const float4*>(gt)[g], b);
             if (v > best) { best = v; bi = g; }
             if (v == __uint_as_float(rm[g])) lq = true;                            // allow_low_quality_matches (matcher.py:83-112)
         }

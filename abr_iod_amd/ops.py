@@ -19,6 +19,16 @@ def _empty(shape, like, dtype=_f32):
     return torch.empty(shape, dtype=dtype, device=like.device)
 
 
+def _cached_workspace(cache, nbytes, device, floor):
+    """a uint8 workspace of at least `nbytes` (`floor` when first made) that the op keeps between calls: one per (device, stream) -- calls on
+    one stream are ordered, and the source and target models may run on different streams"""
+    key = (device, L.stream())
+    ws = cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = cache[key] = torch.empty((max(nbytes, floor),), dtype=torch.uint8, device=device)
+    return ws
+
+
 # ----------------------------------------------------------------------------------------------- ROIAlign
 def roi_align_forward(feat, rois, spatial_scale, ph, pw, sampling_ratio, bin_step=1, out=None):
     """feat [B,H,W,C], rois [K,5] -> [K, ceil(ph/step), ceil(pw/step), C] (written into `out`, a contiguous tensor of that shape, when given)"""
@@ -50,10 +60,7 @@ def roi_align_backward(grad, rois, spatial_scale, ph, pw, sampling_ratio, B, H, 
         out = _empty((B, H, W, Ch), grad)
     if method == "gather" and Ch % 4 == 0 and -(-ph // bin_step) <= 8 and -(-pw // bin_step) <= 8:
         nbytes = L.lib().abr_roi_align_backward_ws_bytes(K, B, H, W, ph, pw, bin_step)
-        key = (grad.device,)
-        ws = _roi_bwd_ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = _roi_bwd_ws[key] = torch.empty((max(nbytes, 1 << 20),), dtype=torch.uint8, device=grad.device)
+        ws = _cached_workspace(_roi_bwd_ws, nbytes, grad.device, 1 << 20)
         L.check(L.lib().abr_roi_align_backward_gather(L.ptr(grad), L.ptr(rois), K, B, Ch, H, W, float(spatial_scale), ph, pw,
                                                       sampling_ratio, bin_step, int(acc), L.ptr(out), L.ptr(ws), ws.numel(),
                                                       L.stream()), "roi_align_backward_gather")
@@ -88,24 +95,25 @@ def nms_sorted_batched(boxes, counts, thr, max_keep, strict_gt=False):
     keep = torch.empty((N, max(max_keep, 1)), dtype=torch.int32, device=boxes.device)
     n_keep = torch.empty((N,), dtype=torch.int32, device=boxes.device)
     ws_bytes = L.lib().abr_nms_workspace_bytes(N, n)
-    key = (boxes.device, L.stream())  # one workspace per stream: the source and target models may run on different streams
-    ws = _nms_ws.get(key)
-    if ws is None or ws.numel() < ws_bytes:
-        ws = _nms_ws[key] = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=boxes.device)
+    ws = _cached_workspace(_nms_ws, ws_bytes, boxes.device, 8)
     L.check(L.lib().abr_nms_sorted_batched(L.ptr(boxes), L.ptr(counts), N, n, float(thr), int(strict_gt), max_keep,
                                            L.ptr(keep), L.ptr(n_keep), L.ptr(ws), ws_bytes, L.stream()), "nms")
     return keep, n_keep
 
 
 # ----------------------------------------------------------------------------------------------- losses
+def _ard_dims(f, layout):
+    """(N, Ch, HW) of a feature map [N,...,C] (NHWC) or [N,C,...] (NCHW)"""
+    if layout == L.NHWC:
+        return f.shape[0], f.shape[-1], f.shape[1:-1].numel()
+    return f.shape[0], f.shape[1], f.shape[2:].numel()
+
+
 def ard_forward(f_src, f_tgt, gamma, layout=L.NHWC):
     """f_* [N,HW,C] (NHWC) -> (loss[4] = total, afd, pad, -), coef [N,2,HW])"""
     L.require_cuda(f_src, f_tgt)
     f_src, f_tgt = L.f32c(f_src), L.f32c(f_tgt)
-    if layout == L.NHWC:
-        N, HW, Ch = f_src.shape[0], f_src.shape[1:-1].numel(), f_src.shape[-1]
-    else:
-        N, Ch, HW = f_src.shape[0], f_src.shape[1], f_src.shape[2:].numel()
+    N, Ch, HW = _ard_dims(f_src, layout)
     loss = _empty((4,), f_src)
     coef = _empty((max(N, 1), 2, HW), f_src)
     L.check(L.lib().abr_ard_forward(L.ptr(f_src), L.ptr(f_tgt), N, Ch, HW, float(gamma), layout, L.ptr(coef),
@@ -115,10 +123,7 @@ def ard_forward(f_src, f_tgt, gamma, layout=L.NHWC):
 
 def ard_backward(f_src, f_tgt, coef, gamma, gscale=1.0, gscale_dev=None, layout=L.NHWC):
     f_src, f_tgt = L.f32c(f_src), L.f32c(f_tgt)
-    if layout == L.NHWC:
-        N, HW, Ch = f_src.shape[0], f_src.shape[1:-1].numel(), f_src.shape[-1]
-    else:
-        N, Ch, HW = f_src.shape[0], f_src.shape[1], f_src.shape[2:].numel()
+    N, Ch, HW = _ard_dims(f_src, layout)
     grad = torch.empty_like(f_tgt)
     L.check(L.lib().abr_ard_backward(L.ptr(f_src), L.ptr(f_tgt), L.ptr(coef), N, Ch, HW, float(gamma), layout,
                                      float(gscale), L.ptr(gscale_dev), L.ptr(grad), L.stream()), "ard_backward")
@@ -1144,6 +1149,15 @@ def match_encode(boxes, gt, gt_labels, vis, hi, lo, allow_low_quality, weights, 
 
 
 _sample_calls = [0]
+
+
+def _draw_seed():
+    """a sampler launch's seed: one draw from torch's default CPU generator per launch (host-side, no device sync): torch.manual_seed()
+    therefore replays the sampler's choices, as it replays torch.randperm in the reference (balanced_positive_negative_sampler.py:44-49)"""
+    _sample_calls[0] += 1
+    return int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF
+
+
 _ptr_tables = {}
 
 
@@ -1208,8 +1222,7 @@ def roi_head_targets(props, scores, keep, n_keep, gt_boxes, gt_labels, hi, lo, w
         pos_rows=torch.empty((N * R,), dtype=i64, device=dev), col0=torch.empty((N * R,), dtype=i64, device=dev),
         n_gt=n_gt, g_max=g_max, keepalive=(gtb, gtl))
     if seed is None:
-        _sample_calls[0] += 1
-        seed = int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF
+        seed = _draw_seed()
     ngt_dev = _small_table(n_gt, i32, dev)
     gtb_tab, gtl_tab = _pointer_table(gtb, dev), _pointer_table(gtl, dev)   # (held in locals until the launch is enqueued: _evict_oldest)
     L.check(L.lib().abr_roi_head_targets(
@@ -1275,10 +1288,7 @@ def sample_pos_neg(labels, batch_size, max_pos, index_offset_per_image=0, seed=N
     neg = torch.empty((N, batch_size), dtype=torch.int64, device=dev)
     counts = torch.empty((N, 2), dtype=torch.int32, device=dev)
     if seed is None:
-        # one draw from torch's default CPU generator per launch (host-side, no device sync): torch.manual_seed() therefore replays the
-        # sampler's choices, as it replays torch.randperm in the reference (balanced_positive_negative_sampler.py:44-49)
-        _sample_calls[0] += 1
-        seed = int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF
+        seed = _draw_seed()
     is64 = labels.dtype == torch.int64
     if not is64 and labels.dtype != _f32:
         raise RuntimeError("sample_pos_neg: labels must be float32 or int64")
@@ -1470,6 +1480,25 @@ def mask_words_per_row(width):
     return (int(width) + 63) // 64
 
 
+def _mask_result(op, n, h, w, packed, out, device):
+    """(shape, dtype) of `op`'s instance masks -- uint8 [n,h,w], or packed the int64 [n,h,ceil(w/64)] words of mask_pack_bits -- after checking
+    a caller's `out` against them (`device` without an index, as in "cuda": any device of that type)"""
+    shape = (n, h, mask_words_per_row(w)) if packed else (n, h, w)
+    dtype = torch.int64 if packed else torch.uint8
+    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device.type != device.type
+                            or (device.index is not None and out.device != device)):
+        raise RuntimeError("{}: `out` must be a contiguous {} tensor of shape {} on {}".format(op, dtype, shape, device))
+    return shape, dtype
+
+
+def _pack_bits_host(m, w):
+    """CPU uint8 masks [n,h,w] -> their mask_pack_bits words, for the host codecs' packed=True"""
+    n, h, wq = m.shape[0], m.shape[1], mask_words_per_row(w)
+    px = torch.zeros((n, h, wq * 64), dtype=torch.int64)
+    px[:, :, :w] = m
+    return (px.reshape(n, h, wq, 64) << torch.arange(64, dtype=torch.int64)).sum(-1)
+
+
 def mask_pack_bits(masks):
     """masks [n,H,W] uint8 or float32 -> int64 [n,H,ceil(W/64)]: bit x % 64 of word x // 64 is set iff masks[i,y,x] == 1"""
     L.require_cuda(masks)
@@ -1560,17 +1589,12 @@ def rle_decode(rles, size, device="cuda", packed=False, out=None):
     h, w = int(size[0]), int(size[1])
     device = torch.device(device)
     n = len(rles)
-    shape = (n, h, mask_words_per_row(w)) if packed else (n, h, w)
-    dtype = torch.int64 if packed else torch.uint8
-    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device.type != device.type):
-        raise RuntimeError("rle_decode: `out` must be a contiguous {} tensor of shape {} on {}".format(dtype, shape, device))
+    shape, dtype = _mask_result("rle_decode", n, h, w, packed, out, device)
     if device.type == "cpu":
         from .structures import rle as host
         m = torch.from_numpy(host.decode(list(rles), (h, w)))
         if packed:
-            px = torch.zeros((n, h, shape[2] * 64), dtype=torch.int64)
-            px[:, :, :w] = m
-            m = (px.reshape(n, h, shape[2], 64) << torch.arange(64, dtype=torch.int64)).sum(-1)
+            m = _pack_bits_host(m, w)
         return m if out is None else out.copy_(m)
     if h <= 0 or w <= 0 or h * w >= 2 ** 31:
         raise RuntimeError("rle_decode: bad size {}".format((h, w)))
@@ -1655,18 +1679,13 @@ def poly_rasterize(polys, packed=False, out=None, return_status=False):
     w, h = polys.int_size()
     device = polys.coords.device
     n = len(polys)
-    shape = (n, h, mask_words_per_row(w)) if packed else (n, h, w)
-    dtype = torch.int64 if packed else torch.uint8
-    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != device):
-        raise RuntimeError("poly_rasterize: `out` must be a contiguous {} tensor of shape {} on {}".format(dtype, shape, device))
+    shape, dtype = _mask_result("poly_rasterize", n, h, w, packed, out, device)
     if device.type == "cpu":
         from .structures import polygon as host
         m, st = host.rasterize(polys.coords.numpy(), polys._po, polys._io, h, w)
         m, status = torch.from_numpy(m), torch.from_numpy(st)
         if packed:
-            px = torch.zeros((n, h, shape[2] * 64), dtype=torch.int64)
-            px[:, :, :w] = m
-            m = (px.reshape(n, h, shape[2], 64) << torch.arange(64, dtype=torch.int64)).sum(-1)
+            m = _pack_bits_host(m, w)
         m = m if out is None else out.copy_(m)
         return (m, status) if return_status else m
     if h * w >= 2 ** 31 - 64:

@@ -10,15 +10,15 @@ roi_align_bwd_nhwc; gather chunks = ceil(C / 256), xcd = the XCD mapping):
 
   kernel / instantiation                     reached by (CASES rows unless said otherwise)
   -----------------------------------------  -----------------------------------------------------------------------------------------
-  roi_align_fwd_nchw                         test_forward, every row with bin_step 1 (_C.roi_align_forward)
-  roi_align_fwd_nchw_f64                     test_f64_nchw_pair (edge zoo)
+  roi_align_fwd_nchw<float>                  test_forward, every row with bin_step 1 (_C.roi_align_forward)
+  roi_align_fwd_nchw<double>                 test_f64_nchw_pair (edge zoo)
   roi_align_fwd_nhwc<4>  cslices 1  (32, 8)  C = 4 ... 24, 8;   (64, 4) C = 252, 256;   (128, 2) C = 260, 512;
                                              (256, 1) C = 1024 on 5x5 (one pass) and C = 2048 on 5x5 (two passes);
                                              bpb cut to the bin count: pooled 1x1 (256, 1)
   roi_align_fwd_nhwc<4>  cslices 8           C = 1024 (32, 8), 1536 and 2048 (64, 4) on 38x63
   roi_align_fwd_nhwc<1>                      C = 1, 3, 5, 6 (32, 8);  C = 70 (128, 2);  C = 250 (256, 1);  C = 514 (256, 1, three passes)
-  roi_align_bwd_nchw                         test_backward[nchw], every row with bin_step 1;  accumulate = 1 in test_backward_accumulates
-  roi_align_bwd_nchw_f64                     test_f64_nchw_pair
+  roi_align_bwd_nchw<float>                  test_backward[nchw], every row with bin_step 1;  accumulate = 1 in test_backward_accumulates
+  roi_align_bwd_nchw<double>                 test_f64_nchw_pair
   roi_align_bwd_nhwc_sep<4>                  test_backward[scatter]: every C % 4 == 0 row with <= 8 kept bins per axis; channel chunks 1 (C <= 1024),
                                              2 (C = 1536, 2048)
   roi_align_bwd_nhwc_sep<1>                  test_backward[scatter]: C = 1, 3, 5, 6, 70, 250 (one chunk), 514 (three chunks)
@@ -268,6 +268,43 @@ def test_backward_overwrites_a_poisoned_output(c, kind):
     buf.fill_(SENTINEL)
     got = abi_backward(kind, c, grad[:0], rois[:0], buf)
     assert (got == 0).all(), "K = 0 without accumulate must zero the output"
+
+
+# --------------------------------------------------------------------------------------------------------------------------- workspace
+def test_gather_workspace_is_per_stream_and_reused():
+    """The gather backward keeps its workspace (weight tables, footprints, tile lists) between calls.  Two calls with different inputs, one on
+    the current stream and one on a side stream, enqueued back to back, must each return the bits of the same call made alone (the gather is
+    atomic-free, hence deterministic): they share nothing.  Two calls in a row on one stream reuse one workspace tensor."""
+    from abr_iod_amd import _lib as L, ops
+    K, B, H, W, C, P = 8, 1, 8, 8, 8, 7
+    rng = np.random.default_rng(7)
+
+    def inputs():
+        lo, size = rng.uniform(-1, 5, (K, 2)), rng.uniform(.5, 6, (K, 2))
+        rois = np.concatenate([np.zeros((K, 1)), lo, lo + size], 1).astype(np.float32)
+        return T(rng.standard_normal((K, P, P, C)).astype(np.float32)), T(rois)
+
+    def run(grad, rois):
+        return ops.roi_align_backward(grad, rois, 1.0, P, P, 2, B, H, W, C, method="gather")
+
+    def cached():
+        return sorted((str(k), id(v)) for k, v in ops._roi_bwd_ws.items())
+
+    (g0, r0), (g1, r1) = inputs(), inputs()
+    alone0 = N(run(g0, r0))
+    held = cached()
+    alone1 = N(run(g1, r1))
+    assert cached() == held and held, "a second call on the same stream must reuse the first one's workspace"
+    assert np.abs(alone0).max() > 0 and not np.array_equal(alone0, alone1)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())          # the inputs were uploaded on the current stream
+    got0, ws0 = run(g0, r0), ops._roi_bwd_ws[(g0.device, L.stream())]
+    with torch.cuda.stream(side):
+        got1, ws1 = run(g1, r1), ops._roi_bwd_ws[(g1.device, L.stream())]
+    torch.cuda.synchronize()
+    assert ws0.data_ptr() != ws1.data_ptr(), "the side stream's call takes a workspace of its own"
+    for got, alone, where in ((got0, alone0, "current"), (got1, alone1, "side")):
+        assert np.array_equal(N(got).view(np.int32), alone.view(np.int32)), f"the call on the {where} stream differs from the same call made alone"
 
 
 # --------------------------------------------------------------------------------------------------------------------------- full size

@@ -88,7 +88,9 @@ __device__ __forceinline__ void find_bin_from_top(const int* h, int nbins, int* 
 //      keys above the bin are survivors for certain, keys inside it are CANDIDATES; both are appended to per-image arrays as 64-bit
 //      (key << 32 | ~index) words (positions reserved per workgroup: two global atomics per slice);
 //   3. select (one workgroup per image): two more radix levels over the CANDIDATES only (a few thousand words, not the 143 640 keys) give the exact
-//      k-th key; candidates >= it join the survivors (ties included); the tail of the last 1024-word chunk is zero-filled; cleans the histogram;
+//      k-th key; candidates >= it join the survivors, ties included -- unless the ties would overflow the sort capacity: then three more levels
+//      over ~index pick exactly the lowest-index ties that are wanted, so k <= filled <= CAP always and the result never depends on which
+//      workgroup won an atomic; the tail of the last 1024-word chunk is zero-filled; cleans the histogram;
 //   4. chunk sort (one 256-thread workgroup per 1024 survivors): bitonic sort in LDS, descending;
 //   5. merge by rank (one workgroup per chunk): all sorted chunks of the image in LDS; an element's final position = its position in its own chunk
 //      + the number of larger elements in every other chunk (binary searches); words are unique (they carry the index), so positions are too;
@@ -172,11 +174,43 @@ __global__ __launch_bounds__(TT) void topk_select_kernel(int* __restrict__ hist_
         find_bin_from_top(h, 256, &s_bin, &s_krem);
         __syncthreads();
         const unsigned thr = (p24 << 8) | (unsigned)s_bin;
-        for (int j = threadIdx.x; j < ncand; j += TT) {   // ties included; dropped only when the sort capacity overflows
-            const unsigned long long w = cand[j];
-            if ((unsigned)(w >> 32) >= thr) {
-                const int pos = nsurv + atomicAdd(&s_fill, 1);
-                if (pos < CAP) surv[pos] = w;
+        // s_krem of the h[s_bin] words whose key IS thr are wanted; the survivors and the candidates above thr make up the other k - s_krem
+        const int want_eq = s_krem, n_eq = h[s_bin];
+        __syncthreads();
+        if (k - want_eq + n_eq <= CAP) {
+            for (int j = threadIdx.x; j < ncand; j += TT) {   // every tie of the k-th key joins: they fit, and the merge emits the first k
+                const unsigned long long w = cand[j];
+                if ((unsigned)(w >> 32) >= thr) {
+                    const int pos = nsurv + atomicAdd(&s_fill, 1);
+                    if (pos < CAP) surv[pos] = w;
+                }
+            }
+        } else {
+            // More ties of the k-th key than the sort holds (zero-padded batches: thousands of identical logits).  Which of them join must not be
+            // left to the order in which the atomics above and in the partition were won: the selection goes on over the words' low halves
+            // (~index: 12 + 12 + 8 bits, as over the keys) among the words whose key is thr, down to the k-th WORD, and exactly the words at or
+            // above it join -- the lowest indices of the tie group, nsurv + joined == k.
+            unsigned long long pre = 0ull;                    // the k-th word's low bits found so far
+            for (int lv = 0; lv < 3; lv++) {
+                const int sh = lv == 0 ? 20 : lv == 1 ? 8 : 0, bits = lv == 2 ? 8 : 12, nb = 1 << bits;
+                for (int i = threadIdx.x; i < nb; i += TT) h[i] = 0;
+                __syncthreads();
+                for (int j = threadIdx.x; j < ncand; j += TT) {
+                    const unsigned long long w = cand[j], low = w & 0xFFFFFFFFull;
+                    if ((unsigned)(w >> 32) == thr && (low >> (sh + bits)) == pre) atomicAdd(&h[(unsigned)(low >> sh) & (nb - 1)], 1);
+                }
+                __syncthreads();
+                find_bin_from_top(h, nb, &s_bin, &s_krem);
+                __syncthreads();
+                pre = (pre << bits) | (unsigned)s_bin;
+            }
+            const unsigned long long thrw = ((unsigned long long)thr << 32) | pre;
+            for (int j = threadIdx.x; j < ncand; j += TT) {
+                const unsigned long long w = cand[j];
+                if (w >= thrw) {
+                    const int pos = nsurv + atomicAdd(&s_fill, 1);
+                    if (pos < CAP) surv[pos] = w;
+                }
             }
         }
         __syncthreads();
@@ -215,14 +249,7 @@ __global__ __launch_bounds__(TT) void topk_merge_emit_kernel(const unsigned long
     unsigned long long* buf = reinterpret_cast<unsigned long long*>(smem);   // [nch][CH]: every sorted chunk of the image
     const int img = blockIdx.y, c = blockIdx.x;
     const int filled = cnt_all[img].filled;
-    if (c * CH >= filled) {
-        // (filled < k cannot happen unless the capacity overflowed: then the tail reads as zeros)
-        for (int j = max(filled, c * CH) + threadIdx.x; j < min(k, (c + 1) * CH); j += TT) {
-            if (scores) scores[(size_t)img * k + j] = 0.f;
-            idx[(size_t)img * k + j] = (int64_t)(~0u);
-        }
-        return;
-    }
+    if (c * CH >= filled) return;              // (filled >= k: the select phase joins every wanted word, and never more than CAP)
     const int nch = (filled + CH - 1) / CH;
     const uint4* src = reinterpret_cast<const uint4*>(surv_all + (size_t)img * CAP);
     uint4* dst = reinterpret_cast<uint4*>(buf);
@@ -283,6 +310,8 @@ static int topk_run(const float* logits, int64_t img_stride, int N, int n, int A
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(topk_merge_emit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort);
+        // (the largest admitted slice stages 48 KB beside the partition kernel's 16 KB histogram and its few scalars: a little over 64 KB in all)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(topk_partition_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 49152);
         attr = true;
     }
     // scratch per stream (launches on a stream are ordered), all of it at offsets that depend on CAPACITIES only:

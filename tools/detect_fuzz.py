@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Random / degenerate-input sweep of the detection kernels against the oracle (test infrastructure: oracle/ is the checker here, never the
-product): ROIAlign forward (bit-exact), backward in both forms, NMS keep lists (index-exact) and the fused sigmoid + top-k ranking -- with RoIs
+product): ROIAlign forward (bit-exact), backward in both forms, NMS keep lists (index-exact) and the fused sigmoid + top-k ranking (index-exact
+against tests/ranking_ref.py wherever the logits are quantised, all-tied images beyond the sort capacity included) -- with RoIs
 that are empty, inverted, far outside the map or larger than it, pooled sizes 1..9, sampling ratios 0..3, box lists full of duplicates and
 exact score / IoU ties, empty images.  GPU box: python tools/detect_fuzz.py [--cases 200] [--seed 0]"""
 import argparse
@@ -14,13 +15,16 @@ import torch  # noqa: E402
 from abr_iod_amd import _C, ops  # noqa: E402
 from oracle import ops as O  # noqa: E402
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from ranking_ref import topk_ref  # noqa: E402
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--cases", type=int, default=200)
 ap.add_argument("--seed", type=int, default=0)
 a = ap.parse_args()
 rng = np.random.default_rng(a.seed)
 fails = []
-count = {"roi_align_forward": 0, "roi_align_backward": 0, "nms": 0, "topk": 0}
+count = {"roi_align_forward": 0, "roi_align_backward": 0, "nms": 0, "topk": 0, "topk_exact": 0}
 
 
 def T(x):
@@ -107,12 +111,21 @@ for ci in range(a.cases):
             fails.append(("nms", (N, n, style, int(counts[i]), thr, mk, strict), int(nk[i]), len(want)))
     # ---------------------------------------------------------------- sigmoid + top-k ranking
     Nn, A = int(rng.integers(1, 5)), int(rng.choice([1, 3, 15]))
-    hw = int(rng.choice([1, 7, 64, 1000, 38 * 63]))
+    hw = int(rng.choice([1, 7, 64, 1000, 38 * 63, -1]))
     ld = A * 5 + int(rng.integers(0, 3))
-    y = torch.randn(Nn, hw, ld, device="cuda") * float(rng.choice([0.1, 3.0, 30.0]))
-    if rng.integers(0, 2):
-        y = torch.round(y * 2) / 2          # heavy exact ties
-    k = int(min(rng.choice([1, 10, 300, 1000, 6000, 12000]), hw * A))
+    tied = hw < 0
+    if tied:     # one logit everywhere, more keys per image than the ranking's 16384-word sort holds: the ties that are returned are the lowest indices
+        hw = -(-17000 // A)
+        y = torch.full((Nn, hw, ld), float(rng.integers(-16, 17)) / 2, device="cuda")
+    else:
+        y = torch.randn(Nn, hw, ld, device="cuda") * float(rng.choice([0.1, 3.0, 30.0]))
+    exact = tied or bool(rng.integers(0, 2))
+    if exact and not tied:
+        # heavy exact ties: multiples of 0.5 in [-8, 8] and the certain saturations (1.0f, 0.0f) -- logits whose order no expf rounding
+        # can change (tests/ranking_ref.py), so the indices are checked one by one as well
+        y = torch.round(y * 2) / 2
+        y = torch.where(y > 8, torch.full_like(y, 30.0), torch.where(y < -8, torch.full_like(y, -200.0), y))
+    k = int(min(rng.choice([1, 10, 300, 1000, 6000, 12000, 15360]), hw * A))
     sc, idx = ops.topk_sigmoid(y, A, k)
     s_all = torch.sigmoid(y[:, :, :A].reshape(Nn, -1))
     ref_s, _ = s_all.topk(k, dim=1, sorted=True)
@@ -123,8 +136,11 @@ for ci in range(a.cases):
     if ok:   # ties by ascending index: within a run of equal scores the indices ascend
         eq = sc[:, 1:] == sc[:, :-1]
         ok = bool(((idx[:, 1:] > idx[:, :-1]) | ~eq).all())
+    if ok and exact:   # ... and the members of every tie group, the one cut by k included, are the exact order's: its lowest indices
+        count["topk_exact"] += 1
+        ok = bool(torch.equal(idx.cpu(), torch.from_numpy(topk_ref(y.cpu().numpy(), A, k)[0])))
     if not ok:
-        fails.append(("topk", (Nn, hw, A, ld, k)))
+        fails.append(("topk", (Nn, hw, A, ld, k, exact, tied)))
     if (ci + 1) % 50 == 0:
         print("%d cases: %s, %d failures" % (ci + 1, count, len(fails)), flush=True)
 

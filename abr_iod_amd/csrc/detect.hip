@@ -280,17 +280,29 @@ extern "C" int abr_det_select(const float* prob, const float* boxes, const int32
     void* nms_ws = w;
     int m = 1;
     while (m < r_max) m <<= 1;
-    const size_t lds = (size_t)m * 8;
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(det_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t lds = (size_t)m * 8, lds_f = (size_t)r_max * 4;
+    // Both kernels' LDS is granted before anything is launched: a size the device refuses is an error here, not a failed launch halfway.
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(det_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            abr::set_error("det_select: %d proposals per image need %zu bytes of LDS for the sort: %s", r_max, lds, hipGetErrorString(e));
+            return ABR_E_LAUNCH;
+        }
+    }
+    if (lds_f > 32 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(det_final_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            abr::set_error("det_select: %d proposals per image need %zu bytes of LDS for the compaction: %s", r_max, lds_f, hipGetErrorString(e));
+            return ABR_E_LAUNCH;
+        }
+    }
     det_sort_kernel<<<dim3(C, N), TT, lds, st>>>(prob, boxes, row_offsets, C, r_max, score_thresh, s_boxes, s_scores, s_idx, counts);
     ABR_CHECK_LAUNCH("det_sort");
     const int rc = abr_nms_sorted_batched(s_boxes, counts, (int)L, r_max, nms_thresh, 0, r_max, keep, n_keep, nms_ws,
                                           abr_nms_workspace_bytes((int)L, r_max), stream);
     if (rc != ABR_OK) return rc;
-    const size_t lds_f = (size_t)r_max * 4;
-    if (lds_f > 32 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(det_final_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
     det_final_kernel<<<N, TT, lds_f, st>>>(s_boxes, s_scores, s_idx, keep, n_keep, C, r_max, detections_per_img, cap, out_boxes, out_scores,
                                        out_labels, out_count, bg_boxes, bg_scores, bg_count);
     ABR_CHECK_LAUNCH("det_final");

@@ -25,7 +25,8 @@ class PostProcessor(nn.Module):
         loop variable, inference.py:75-82)."""
         class_logits, box_regression = x
         K, C = class_logits.shape
-        box_regression = box_regression.reshape(K, -1)
+        # (no proposals in the whole batch: reshape(0, -1) cannot infer a width, and no delta is read)
+        box_regression = box_regression.reshape(K, -1) if K else box_regression.new_zeros((0, 4 * C))
         dev = class_logits.device
         counts = [len(b) for b in boxes]
         if sum(counts) != K:

@@ -203,6 +203,8 @@ def det_filter_results(prob, boxes, score_thresh=0.05, nms_thresh=0.5, detection
             rb.append(bj[keep]); rs.append(sj[keep]); rl.append(np.full(len(keep), j, np.int64))
         else:
             bg = (bj[keep], sj[keep])
+    if C == 1:  # background only: nothing to concatenate (torch.cat of an empty list is the reference's error; empty here)
+        rb, rs, rl = [boxes[:0, 0]], [prob[:0, 0]], [np.zeros(0, np.int64)]
     rb, rs, rl = np.concatenate(rb, 0), np.concatenate(rs, 0), np.concatenate(rl, 0)
     if len(rs) > detections_per_img > 0:
         thresh = np.sort(rs)[len(rs) - detections_per_img]      # kthvalue(n - D + 1)

@@ -180,6 +180,10 @@ _SIGS = {
     "abr_poly_rasterize_workspace_bytes": (_i64, [_i64, _i, _i]),
     "abr_poly_rasterize": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "abr_poly_mask_targets": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_coco_match_max_gt": (_i, []),
+    "abr_coco_box_iou": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
+    "abr_coco_mask_iou": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "abr_coco_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 # every symbol include/abr_iod_hip.h declares (tests/test_abi.py checks the library exports them all)

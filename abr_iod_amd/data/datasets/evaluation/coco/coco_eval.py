@@ -1,0 +1,221 @@
+"""COCO box and mask AP / AR (mirror of maskrcnn_benchmark/data/datasets/evaluation/coco/coco_eval.py: do_coco_evaluation, the
+prepare_for_coco_* functions, COCOResults, check_expected_results).  The reference hands the scoring to pycocotools' COCOeval, a host loop
+over every image, category, area range and IoU threshold.  Here the protocol is restated and split in two:
+  * the per-image work runs on the device for the whole dataset at once: pairwise IoU with crowd semantics (ops.coco_box_iou; for masks
+    ops.mask_pair_counts + ops.coco_mask_iou over run-length results decoded by ops.rle_decode) and the greedy matching for all area
+    ranges and thresholds (ops.coco_match);
+  * the short accumulation and the 12 summary numbers stay on the host in float64 (coco_eval_host.py).
+device="cpu" scores everything with the host restatement instead: the yardstick of the tests, never chosen silently.
+Not carried: box_only (proposal recall) and keypoints."""
+import json
+import logging
+import os
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from ..voc.coco_results import prepare_for_coco_segmentation  # noqa: F401
+from . import coco_eval_host as H
+
+
+def do_coco_evaluation(dataset, predictions, box_only, output_folder, iou_types, expected_results, expected_results_sigma_tol, device="cuda"):
+    logger = logging.getLogger("maskrcnn_benchmark.inference")
+    if box_only:
+        raise NotImplementedError("box_only (proposal recall of an RPN-only model) is not carried; evaluate with iou_types=('bbox',)")
+    unknown = [t for t in iou_types if t not in ("bbox", "segm")]
+    if unknown:
+        raise NotImplementedError("COCO evaluation of {} is not carried (bbox and segm are)".format(unknown))
+    logger.info("Preparing results for COCO format")
+    coco_results = {}
+    if "bbox" in iou_types:
+        logger.info("Preparing bbox results")
+        coco_results["bbox"] = prepare_for_coco_detection(predictions, dataset)
+    if "segm" in iou_types:
+        logger.info("Preparing segm results")
+        coco_results["segm"] = prepare_for_coco_segmentation(predictions, dataset)       # (encoded on the device whatever `device` scores)
+    results = COCOResults(*iou_types)
+    logger.info("Evaluating predictions")
+    for iou_type in iou_types:
+        if output_folder:
+            with open(os.path.join(output_folder, iou_type + ".json"), "w") as f:
+                json.dump(coco_results[iou_type], f)
+        res = evaluate_predictions_on_coco(dataset, coco_results[iou_type], iou_type, device=device)
+        logger.info(res.text())
+        results.update(res)
+    logger.info(results)
+    check_expected_results(results, expected_results, expected_results_sigma_tol)
+    if output_folder:
+        torch.save(results, os.path.join(output_folder, "coco_results.pth"))
+    return results, coco_results
+
+
+def prepare_for_coco_detection(predictions, dataset):
+    """predictions (BoxLists in dataset order) -> [{"image_id", "category_id", "bbox": xywh at the original image size, "score"}]"""
+    coco_results = []
+    for image_id, prediction in enumerate(predictions):
+        original_id = dataset.id_to_img_map[image_id]
+        if len(prediction) == 0:
+            continue
+        info = dataset.get_img_info(image_id)
+        prediction = prediction.copy_with_fields(["labels", "scores"]).resize((info["width"], info["height"])).convert("xywh")
+        boxes = prediction.bbox.tolist()
+        scores = prediction.get_field("scores").tolist()
+        labels = [dataset.contiguous_category_id_to_json_id[i] for i in prediction.get_field("labels").tolist()]
+        coco_results.extend({"image_id": original_id, "category_id": labels[k], "bbox": box, "score": scores[k]} for k, box in enumerate(boxes))
+    return coco_results
+
+
+class COCOEvalResult(object):
+    """what one iou_type's evaluation leaves: stats (the 12 numbers of COCOeval.summarize, coco_eval_host.STAT_NAMES), the precision
+    [T,R,K,A,M] and recall [T,K,A,M] tables, and how the groups were scored"""
+
+    def __init__(self, iou_type, stats, acc, n_groups, n_fallback):
+        self.iou_type, self.stats, self.precision, self.recall = iou_type, stats, acc["precision"], acc["recall"]
+        self.n_groups, self.n_fallback = n_groups, n_fallback
+
+    def text(self):
+        return H.summary_text(self.stats, self.iou_type)
+
+
+class COCOResults(object):
+    METRICS = {"bbox": ["AP", "AP50", "AP75", "APs", "APm", "APl"], "segm": ["AP", "AP50", "AP75", "APs", "APm", "APl"]}
+
+    def __init__(self, *iou_types):
+        assert all(t in COCOResults.METRICS for t in iou_types), iou_types
+        self.results = OrderedDict((t, OrderedDict((m, -1) for m in COCOResults.METRICS[t])) for t in iou_types)
+
+    def update(self, coco_eval):
+        if coco_eval is None:
+            return
+        assert isinstance(coco_eval, COCOEvalResult)
+        res = self.results[coco_eval.iou_type]
+        for idx, metric in enumerate(COCOResults.METRICS[coco_eval.iou_type]):
+            res[metric] = float(coco_eval.stats[idx])
+
+    def __repr__(self):
+        return repr(self.results)
+
+
+def check_expected_results(results, expected_results, sigma_tol):
+    """expected_results: [(task, metric, (mean, std))]; logs PASS / FAIL for mean - sigma_tol * std < value < mean + sigma_tol * std"""
+    if not expected_results:
+        return
+    logger = logging.getLogger("maskrcnn_benchmark.inference")
+    for task, metric, (mean, std) in expected_results:
+        actual = results.results[task][metric]
+        lo, hi = mean - sigma_tol * std, mean + sigma_tol * std
+        ok = lo < actual < hi
+        msg = "{} > {} sanity check (actual vs. expected): {:.3f} vs. mean={:.4f}, std={:.4}, range=({:.4f}, {:.4f})".format(
+            task, metric, actual, mean, std, lo, hi)
+        if ok:
+            logger.info("PASS: " + msg)
+        else:
+            logger.error("FAIL: " + msg)
+
+
+# ------------------------------------------------------------------------------------------------ groups
+def _image_mask_iou(dets, anns, size, masks_of, device):
+    """one image: result dicts with run-length "segmentation"s x annotations -> (float64 [P,T] IoU, [P] pixel counts), pairs of different
+    categories 0"""
+    from ..... import ops
+    width, height = size
+    P, T = len(dets), len(anns)
+    crowd = np.array([bool(a.get("iscrowd", 0)) for a in anns], bool)
+    dl = np.array([d["category_id"] for d in dets], np.int64)
+    gl = np.array([a["category_id"] for a in anns], np.int64)
+    rles = [d["segmentation"] for d in dets]
+    if device.type == "cuda":
+        pb = ops.rle_decode(rles, (height, width), device, packed=True)
+        if T == 0:
+            area_p = ops.mask_pair_counts(pb, pb[:1], width)[1] if P else torch.zeros((0,), dtype=torch.int32)
+            return np.zeros((P, 0)), area_p.cpu().numpy().astype(np.int64)
+        gb = masks_of(device, True)
+        inter, area_p, area_t = ops.mask_pair_counts(pb, gb, width, torch.from_numpy(dl), torch.from_numpy(gl))
+        return ops.coco_mask_iou(inter, area_p, area_t, crowd).cpu().numpy(), area_p.cpu().numpy().astype(np.int64)
+    pm = ops.rle_decode(rles, (height, width), "cpu").numpy().reshape(P, -1).astype(np.int64)
+    area_p = pm.sum(1)
+    if T == 0:
+        return np.zeros((P, 0)), area_p
+    gm = masks_of(device, False).numpy().reshape(T, -1).astype(np.int64)
+    inter = (pm @ gm.T) * (dl[:, None] == gl[None, :])
+    return H.mask_iou_from_counts(inter, area_p, gm.sum(1), crowd), area_p
+
+
+def build_groups(dataset, coco_results, iou_type, device):
+    """-> (groups, cat_ids).  A group: {"k": category index, "scores" (rank order), "det_area", "gt_area", "gt_crowd", and "det" / "gt"
+    xywh boxes (bbox) or "iou" float64 [D,G] (segm)}, images in dataset order, categories ascending inside an image"""
+    device = torch.device(device)
+    cat_ids = sorted(dataset.json_category_id_to_contiguous_id)
+    cat_index = {c: k for k, c in enumerate(cat_ids)}
+    by_image = {}
+    for r in coco_results:
+        by_image.setdefault(r["image_id"], []).append(r)
+    known = set(dataset.id_to_img_map.values())
+    stray = [i for i in by_image if i not in known]
+    if stray:
+        raise ValueError("results for image ids the dataset does not hold: {}".format(sorted(stray)[:5]))
+    groups = []
+    for index in range(len(dataset)):
+        dets = by_image.get(dataset.id_to_img_map[index], [])
+        anns = dataset.get_annotations(index)
+        if not dets and not anns:
+            continue
+        if iou_type == "segm" and dets:
+            info = dataset.get_img_info(index)
+            iou_img, area_img = _image_mask_iou(dets, anns, (int(info["width"]), int(info["height"])),
+                                                lambda dev, packed: dataset.annotation_masks(index, dev, packed), device)
+        for c in sorted(set(d["category_id"] for d in dets) | set(a["category_id"] for a in anns)):
+            if c not in cat_index:
+                raise ValueError("category id {} is not in the annotation file".format(c))
+            rows = np.array([i for i, d in enumerate(dets) if d["category_id"] == c], np.int64)
+            cols = np.array([j for j, a in enumerate(anns) if a["category_id"] == c], np.int64)
+            rows = rows[H.rank_detections([dets[i]["score"] for i in rows])]
+            g = {"k": cat_index[c], "scores": np.array([dets[i]["score"] for i in rows], np.float64),
+                 "gt_area": np.array([anns[j]["area"] for j in cols], np.float64),
+                 "gt_crowd": np.array([bool(anns[j].get("iscrowd", 0)) for j in cols], bool)}
+            if iou_type == "bbox":
+                g["det"] = np.array([dets[i]["bbox"] for i in rows], np.float64).reshape(-1, 4)
+                g["gt"] = np.array([anns[j]["bbox"] for j in cols], np.float64).reshape(-1, 4)
+                g["det_area"] = g["det"][:, 2] * g["det"][:, 3]
+            else:
+                g["iou"] = iou_img[np.ix_(rows, cols)] if len(rows) else np.zeros((0, len(cols)))
+                g["det_area"] = area_img[rows].astype(np.float64) if len(rows) else np.zeros((0,))
+            groups.append(g)
+    return groups, cat_ids
+
+
+def score_groups(groups, iou_type, device, area_rng=H.AREA_RNG, thrs=H.IOU_THRS):
+    """-> (per-group evaluateImg results, number of groups the match kernel left to the host)"""
+    from ..... import ops
+    device = torch.device(device)
+    if device.type != "cuda":
+        for g in groups:
+            if iou_type == "bbox":
+                g["iou"] = H.box_iou(g["det"], g["gt"], g["gt_crowd"])
+        return H.score_groups_host(groups, area_rng, thrs), 0
+    if not groups:
+        return [], 0
+    dc = np.array([len(g["scores"]) for g in groups], np.int64)
+    gc = np.array([len(g["gt_area"]) for g in groups], np.int64)
+    cat = lambda key, shape: np.concatenate([np.asarray(g[key]).reshape(shape) for g in groups])      # noqa: E731
+    crowd = cat("gt_crowd", (-1,))
+    if iou_type == "bbox":
+        iou, _ = ops.coco_box_iou(cat("det", (-1, 4)), cat("gt", (-1, 4)), crowd, dc, gc, device)
+    else:
+        iou = cat("iou", (-1,))
+    out = ops.coco_match(iou, dc, gc, cat("det_area", (-1,)), cat("gt_area", (-1,)), crowd, area_rng, thrs, device)
+    d_off, g_off = np.concatenate(([0], np.cumsum(dc))), np.concatenate(([0], np.cumsum(gc)))
+    res = [{"dt_gt": out["dt_gt"][:, :, d_off[i]: d_off[i + 1]], "dt_ig": out["dt_ig"][:, :, d_off[i]: d_off[i + 1]],
+            "gt_ig": out["gt_ig"][:, g_off[i]: g_off[i + 1]]} for i in range(len(groups))]
+    return res, out["n_fallback"]
+
+
+def evaluate_predictions_on_coco(dataset, coco_results, iou_type="bbox", device="cuda"):
+    groups, cat_ids = build_groups(dataset, coco_results, iou_type, device)
+    scored, n_fallback = score_groups(groups, iou_type, device)
+    cells = {}
+    for g, r in zip(groups, scored):
+        cells.setdefault(g["k"], []).append(dict(r, scores=g["scores"]))
+    acc = H.accumulate(cells, len(cat_ids))
+    return COCOEvalResult(iou_type, H.summarize(acc), acc, len(groups), n_fallback)

@@ -1,0 +1,170 @@
+"""The COCO detection protocol on the host, in float64 numpy: what pycocotools' COCOeval computes -- bbIou / rleIou, evaluateImg,
+accumulate, summarize -- restated from the protocol.  pycocotools cannot be installed where this project is built, so
+compatibility rests on this restatement and its answers worked out by hand (tests/test_coco_eval_host.py), as it does for run-length
+masks and polygons.  Three users: the groups the match kernel leaves to the host (more ground truths than ops.COCO_MATCH_MAX_GT), the
+accumulation behind both routes, and the tests of csrc/coco_eval.hip.
+
+A GROUP is one (image, category) pair: its detections in rank order (score descending, stable, the first maxDets[-1]) and its ground
+truths in file order.
+
+One deliberate difference: a match is recorded by the ground truth's ROW in its group, -1 = none.  pycocotools stores annotation ids
+and tests them with `> 0` / `== 0`, so an annotation (or detection) whose id is 0 reads as unmatched; that quirk is not reproduced."""
+import numpy as np
+
+IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+MAX_DETS = (1, 10, 100)
+AREA_RNG = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], np.float64)
+AREA_LABELS = ("all", "small", "medium", "large")
+STAT_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
+
+
+def rank_detections(scores, max_det=MAX_DETS[-1]):
+    """indices of the detections that count, in rank order: a stable sort by score descending (equal scores keep their order), cut at max_det"""
+    return np.argsort(-np.asarray(scores, np.float64), kind="mergesort")[:max_det]
+
+
+def box_iou(det, gt, gt_crowd):
+    """bbIou: det [D,4], gt [G,4] xywh -> float64 [D,G].  area = w * h (no + 1); a pair whose intersection has no positive width or height
+    gets 0; else i / (a_d + a_g - i), or i / a_d when the ground truth is a crowd"""
+    det, gt = np.asarray(det, np.float64).reshape(-1, 4), np.asarray(gt, np.float64).reshape(-1, 4)
+    crowd = np.asarray(gt_crowd).astype(bool).reshape(-1)
+    dx, dy, dw, dh = (det[:, k, None] for k in range(4))
+    gx, gy, gw, gh = (gt[None, :, k] for k in range(4))
+    w = np.minimum(dw + dx, gw + gx) - np.maximum(dx, gx)
+    h = np.minimum(dh + dy, gh + gy) - np.maximum(dy, gy)
+    i = w * h
+    da = np.broadcast_to(dw * dh, i.shape)
+    u = np.where(crowd[None, :], da, da + gw * gh - i)
+    out = np.zeros(i.shape, np.float64)
+    np.divide(i, u, out=out, where=(w > 0) & (h > 0))
+    return out
+
+
+def mask_iou_from_counts(inter, area_p, area_t, gt_crowd):
+    """rleIou from pixel counts: inter [P,T], area_p [P], area_t [T] integers -> float64 [P,T]; 0 where the masks do not meet"""
+    inter = np.asarray(inter, np.int64)
+    area_p, area_t = np.asarray(area_p, np.int64).reshape(-1), np.asarray(area_t, np.int64).reshape(-1)
+    crowd = np.asarray(gt_crowd).astype(bool).reshape(-1)
+    u = np.where(crowd[None, :], area_p[:, None], area_p[:, None] + area_t[None, :] - inter)
+    out = np.zeros(inter.shape, np.float64)
+    np.divide(inter.astype(np.float64), u.astype(np.float64), out=out, where=inter > 0)
+    return out
+
+
+def evaluate_img(iou, det_area, gt_area, gt_crowd, area_rng=AREA_RNG, thrs=IOU_THRS):
+    """evaluateImg of one group for every area range and IoU threshold.  iou float64 [D,G] (detections in rank order, ground truths in
+    file order) -> {"dt_gt": int32 [A,T,D] matched ground-truth row or -1, "dt_ig": bool [A,T,D], "gt_ig": bool [A,G]}"""
+    det_area, gt_area = np.asarray(det_area, np.float64).reshape(-1), np.asarray(gt_area, np.float64).reshape(-1)
+    crowd = np.asarray(gt_crowd).astype(bool).reshape(-1)
+    area_rng, thrs = np.asarray(area_rng, np.float64).reshape(-1, 2), np.asarray(thrs, np.float64).reshape(-1)
+    D, G, A, T = len(det_area), len(gt_area), len(area_rng), len(thrs)
+    iou = np.asarray(iou, np.float64).reshape(D, G)
+    dt_gt = np.full((A, T, D), -1, np.int32)
+    dt_ig = np.zeros((A, T, D), bool)
+    gt_ig = np.zeros((A, G), bool)
+    rows = iou.tolist()
+    for a, (lo, hi) in enumerate(area_rng):
+        ig = crowd | (gt_area < lo) | (gt_area > hi)
+        gt_ig[a] = ig
+        order = np.argsort(ig, kind="mergesort").tolist()       # the non-ignored first, stable
+        ig_l, crowd_l = ig.tolist(), crowd.tolist()
+        d_out = ((det_area < lo) | (det_area > hi)).tolist()
+        for t, thr in enumerate(thrs.tolist()):
+            taken = [False] * G
+            for d in range(D):
+                best, m = min(thr, 1 - 1e-10), -1
+                row = rows[d]
+                for g in order:
+                    if taken[g] and not crowd_l[g]:
+                        continue
+                    if m > -1 and not ig_l[m] and ig_l[g]:
+                        break
+                    if row[g] < best:
+                        continue
+                    best, m = row[g], g
+                if m == -1:
+                    dt_ig[a, t, d] = d_out[d]
+                    continue
+                taken[m] = True
+                dt_gt[a, t, d] = m
+                dt_ig[a, t, d] = ig_l[m]
+    return {"dt_gt": dt_gt, "dt_ig": dt_ig, "gt_ig": gt_ig}
+
+
+def accumulate(cells, n_cats, n_areas=len(AREA_RNG), n_thrs=len(IOU_THRS), max_dets=MAX_DETS, rec_thrs=REC_THRS):
+    """cells: {category index k: [group results in image order]}, a group result = {"scores": [D] in rank order, "dt_gt", "dt_ig", "gt_ig"}
+    (an (image, category) pair without detections and without ground truths has no entry, as evaluateImg returns None for it).
+    -> {"precision": [T,R,K,A,M], "recall": [T,K,A,M]}, -1 where a cell has no non-ignored ground truth"""
+    rec_thrs = np.asarray(rec_thrs, np.float64)
+    T, R, K, A, M = n_thrs, len(rec_thrs), n_cats, n_areas, len(max_dets)
+    precision = -np.ones((T, R, K, A, M))
+    recall = -np.ones((T, K, A, M))
+    for k in range(K):
+        E = cells.get(k, [])
+        if not E:
+            continue
+        for a in range(A):
+            gt_ig = np.concatenate([e["gt_ig"][a] for e in E])
+            npig = np.count_nonzero(~gt_ig)
+            if npig == 0:
+                continue
+            for m, max_det in enumerate(max_dets):
+                scores = np.concatenate([np.asarray(e["scores"], np.float64)[:max_det] for e in E])
+                inds = np.argsort(-scores, kind="mergesort")
+                dtm = np.concatenate([e["dt_gt"][a][:, :max_det] >= 0 for e in E], axis=1)[:, inds]
+                dt_ig = np.concatenate([e["dt_ig"][a][:, :max_det] for e in E], axis=1)[:, inds]
+                tp_sum = np.cumsum(dtm & ~dt_ig, axis=1).astype(np.float64)
+                fp_sum = np.cumsum(~dtm & ~dt_ig, axis=1).astype(np.float64)
+                for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
+                    nd = len(tp)
+                    rc = tp / npig
+                    pr = tp / (fp + tp + np.spacing(1))
+                    q = np.zeros((R,))
+                    recall[t, k, a, m] = rc[-1] if nd else 0
+                    if nd:
+                        pr = np.maximum.accumulate(pr[::-1])[::-1]       # monotone from the right
+                        at = np.searchsorted(rc, rec_thrs, side="left")
+                        ok = at < nd
+                        q[ok] = pr[at[ok]]
+                    precision[t, :, k, a, m] = q
+    return {"precision": precision, "recall": recall}
+
+
+def _mean_valid(s):
+    s = s[s > -1]
+    return -1.0 if s.size == 0 else float(np.mean(s))
+
+
+def summarize(acc, thrs=IOU_THRS, max_dets=MAX_DETS):
+    """the 12 numbers of COCOeval.summarize for bbox / segm, in STAT_NAMES' order"""
+    P, Rc = acc["precision"], acc["recall"]
+    last = len(max_dets) - 1
+
+    def ap(a=0, thr=None):
+        s = P[:, :, :, a, last]
+        return _mean_valid(s if thr is None else s[np.where(thr == thrs)[0]])
+
+    def ar(a=0, m=last):
+        return _mean_valid(Rc[:, :, a, m])
+
+    return np.array([ap(), ap(thr=.5), ap(thr=.75), ap(1), ap(2), ap(3), ar(m=0), ar(m=1), ar(m=2), ar(1), ar(2), ar(3)], np.float64)
+
+
+def summary_text(stats, iou_type):
+    """the lines COCOeval.summarize prints"""
+    rows = [("Average Precision", "AP", "0.50:0.95", "all", 100), ("Average Precision", "AP", "0.50", "all", 100),
+            ("Average Precision", "AP", "0.75", "all", 100), ("Average Precision", "AP", "0.50:0.95", "small", 100),
+            ("Average Precision", "AP", "0.50:0.95", "medium", 100), ("Average Precision", "AP", "0.50:0.95", "large", 100),
+            ("Average Recall", "AR", "0.50:0.95", "all", 1), ("Average Recall", "AR", "0.50:0.95", "all", 10),
+            ("Average Recall", "AR", "0.50:0.95", "all", 100), ("Average Recall", "AR", "0.50:0.95", "small", 100),
+            ("Average Recall", "AR", "0.50:0.95", "medium", 100), ("Average Recall", "AR", "0.50:0.95", "large", 100)]
+    lines = ["COCO {} summary".format(iou_type)]
+    for (title, kind, iou, area, md), v in zip(rows, stats):
+        lines.append(" {:<18} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(title + " (" + kind + ")", iou, area, md, v))
+    return "\n".join(lines)
+
+
+def score_groups_host(groups, area_rng=AREA_RNG, thrs=IOU_THRS):
+    """groups: list of {"iou" [D,G], "det_area", "gt_area", "gt_crowd"} -> list of evaluate_img results"""
+    return [evaluate_img(g["iou"], g["det_area"], g["gt_area"], g["gt_crowd"], area_rng, thrs) for g in groups]

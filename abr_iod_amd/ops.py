@@ -1734,3 +1734,135 @@ def poly_mask_targets(polys_per_image, gt_boxes, rois, pos_rows, M):
     L.check(L.lib().abr_poly_mask_targets(t0, t0 + 8 * N, t0 + 16 * N, L.ptr(dtab), t0 + 24 * N, L.ptr(rois), L.ptr(pos_rows), P, rois.shape[0], N, int(M),
                                           L.ptr(out), L.stream()), "poly_mask_targets")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- COCO scoring (csrc/coco_eval.hip)
+COCO_MATCH_MAX_GT = 128      # ABR_COCO_MATCH_MAX_GT: the ground truths per group coco_match's kernel holds
+
+
+def _coco_offsets(counts, dev):
+    """per-group counts -> (int64 numpy [n+1] offsets, the same on `dev`)"""
+    import numpy as np
+    off = np.zeros(len(counts) + 1, np.int64)
+    np.cumsum(np.asarray(counts, np.int64), out=off[1:])
+    return off, torch.from_numpy(off).to(dev)
+
+
+def _f64_dev(a, dev, shape):
+    import numpy as np
+    if isinstance(a, torch.Tensor):
+        return a.to(device=dev, dtype=torch.float64).reshape(shape).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))).to(dev)
+
+
+def _u8_dev(a, dev):
+    import numpy as np
+    if isinstance(a, torch.Tensor):
+        return a.to(device=dev, dtype=torch.uint8).reshape(-1).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.uint8).reshape(-1))).to(dev)
+
+
+def coco_box_iou(det, gt, gt_crowd, det_counts, gt_counts, device="cuda"):
+    """pycocotools' bbIou for every group of a batch in one launch.  det [D_total,4], gt [G_total,4] xywh (float64; numpy or tensors),
+    gt_crowd [G_total]; det_counts / gt_counts: detections / ground truths per group.  -> (iou float64 device [sum D_k * G_k], the groups'
+    row-major D_k x G_k matrices one after the other; iou_off int64 numpy [n+1])"""
+    import numpy as np
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("coco_box_iou runs on the device; the host restatement is evaluation/coco/coco_eval_host.py")
+    det_counts, gt_counts = np.asarray(det_counts, np.int64).reshape(-1), np.asarray(gt_counts, np.int64).reshape(-1)
+    if det_counts.shape != gt_counts.shape or (det_counts < 0).any() or (gt_counts < 0).any():
+        raise RuntimeError("coco_box_iou: one non-negative detection count and ground-truth count per group")
+    n = len(det_counts)
+    with torch.cuda.device(dev):
+        det_off, det_off_d = _coco_offsets(det_counts, dev)
+        gt_off, gt_off_d = _coco_offsets(gt_counts, dev)
+        iou_off, iou_off_d = _coco_offsets(det_counts * gt_counts, dev)
+        det, gt, crowd = _f64_dev(det, dev, (-1, 4)), _f64_dev(gt, dev, (-1, 4)), _u8_dev(gt_crowd, dev)
+        if det.shape[0] != det_off[-1] or gt.shape[0] != gt_off[-1] or crowd.numel() != gt_off[-1]:
+            raise RuntimeError("coco_box_iou: {} detections / {} ground truths / {} crowd flags for counts that sum to {} / {}".format(
+                det.shape[0], gt.shape[0], crowd.numel(), det_off[-1], gt_off[-1]))
+        total = int(iou_off[-1])
+        iou = torch.empty((total,), dtype=torch.float64, device=dev)
+        if n and total:
+            L.check(L.lib().abr_coco_box_iou(L.ptr(det), L.ptr(gt), L.ptr(crowd), L.ptr(det_off_d), L.ptr(gt_off_d), L.ptr(iou_off_d), n, total,
+                                             L.ptr(iou), L.stream()), "coco_box_iou")
+    return iou, iou_off
+
+
+def coco_mask_iou(inter, area_p, area_t, gt_crowd):
+    """the int32 counts of mask_pair_counts for one image + gt_crowd [T] -> float64 [P,T] mask IoU as pycocotools' rleIou defines it:
+    inter / (area_p + area_t - inter), inter / area_p for a crowd ground truth, 0 where the masks do not meet"""
+    L.require_cuda(inter, area_p, area_t)
+    if inter.dtype != torch.int32 or area_p.dtype != torch.int32 or area_t.dtype != torch.int32 or inter.dim() != 2:
+        raise RuntimeError("coco_mask_iou: expected the int32 [P,T], [P], [T] counts of mask_pair_counts")
+    P, T = inter.shape
+    dev = inter.device
+    crowd = _u8_dev(gt_crowd, dev)
+    if area_p.numel() != P or area_t.numel() != T or crowd.numel() != T:
+        raise RuntimeError("coco_mask_iou: {} / {} areas and {} crowd flags for {} x {} counts".format(area_p.numel(), area_t.numel(), crowd.numel(), P, T))
+    iou = torch.empty((P, T), dtype=torch.float64, device=dev)
+    if P and T:
+        with torch.cuda.device(dev):
+            L.check(L.lib().abr_coco_mask_iou(L.ptr(inter.contiguous()), L.ptr(area_p.contiguous()), L.ptr(area_t.contiguous()), L.ptr(crowd), P, T,
+                                              L.ptr(iou), L.stream()), "coco_mask_iou")
+    return iou
+
+
+def coco_match(iou, det_counts, gt_counts, det_area, gt_area, gt_crowd, area_rng, thrs, device="cuda"):
+    """pycocotools' evaluateImg for every group of a batch, all area ranges and all IoU thresholds in one launch.  iou: the flat float64
+    matrices of coco_box_iou's layout (device tensor or numpy); det_area [D_total], gt_area [G_total], gt_crowd [G_total]; area_rng [A,2]
+    (inclusive); thrs [T] float64, used as given.  -> dict of numpy arrays:
+        dt_gt   int32 [A,T,D_total]  the matched ground truth's row in its group, -1 = unmatched
+        dt_ig   bool  [A,T,D_total]  the detection is ignored
+        gt_ig   bool  [A,G_total]    the ground truth is ignored
+        n_fallback                   groups with more than COCO_MATCH_MAX_GT ground truths: scored by the host restatement
+                                     (coco_eval_host.evaluate_img), never truncated
+    Matches are recorded by row, not by annotation id."""
+    import numpy as np
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("coco_match runs on the device; the host restatement is evaluation/coco/coco_eval_host.py")
+    det_counts, gt_counts = np.asarray(det_counts, np.int64).reshape(-1), np.asarray(gt_counts, np.int64).reshape(-1)
+    if det_counts.shape != gt_counts.shape or (det_counts < 0).any() or (gt_counts < 0).any():
+        raise RuntimeError("coco_match: one non-negative detection count and ground-truth count per group")
+    area_rng, thrs = np.asarray(area_rng, np.float64).reshape(-1, 2), np.asarray(thrs, np.float64).reshape(-1)
+    A, T, n = area_rng.shape[0], thrs.shape[0], len(det_counts)
+    if not (1 <= A <= 8 and T >= 1 and A * T <= 64):
+        raise RuntimeError("coco_match: {} area ranges x {} thresholds (the kernel gives each pair one lane of a wave: A <= 8, A * T <= 64)".format(A, T))
+    with torch.cuda.device(dev):
+        det_off, det_off_d = _coco_offsets(det_counts, dev)
+        gt_off, gt_off_d = _coco_offsets(gt_counts, dev)
+        iou_off, iou_off_d = _coco_offsets(det_counts * gt_counts, dev)
+        Dt, Gt = int(det_off[-1]), int(gt_off[-1])
+        iou_d = _f64_dev(iou, dev, (-1,))
+        d_area, g_area, crowd = _f64_dev(det_area, dev, (-1,)), _f64_dev(gt_area, dev, (-1,)), _u8_dev(gt_crowd, dev)
+        if iou_d.numel() != iou_off[-1] or d_area.numel() != Dt or g_area.numel() != Gt or crowd.numel() != Gt:
+            raise RuntimeError("coco_match: the flat arrays do not have the lengths the counts sum to")
+        iou_arg = iou_d if iou_d.numel() else torch.zeros((1,), dtype=torch.float64, device=dev)      # (no pair at all: still a valid address)
+        dt_gt = torch.full((A, T, Dt), -1, dtype=torch.int32, device=dev)
+        dt_ig = torch.zeros((A, T, Dt), dtype=torch.uint8, device=dev)
+        gt_ig = torch.zeros((A, Gt), dtype=torch.uint8, device=dev)
+        n_over = torch.zeros((1,), dtype=torch.int32, device=dev)
+        if n:
+            rng_d, thr_d = torch.from_numpy(area_rng.copy()).to(dev), torch.from_numpy(thrs.copy()).to(dev)
+            L.check(L.lib().abr_coco_match(L.ptr(iou_arg), L.ptr(iou_off_d), L.ptr(det_off_d), L.ptr(gt_off_d), L.ptr(d_area), L.ptr(g_area), L.ptr(crowd),
+                                           n, Dt, Gt, L.ptr(rng_d), A, L.ptr(thr_d), T, L.ptr(dt_gt), L.ptr(dt_ig), L.ptr(gt_ig), L.ptr(n_over),
+                                           L.stream()), "coco_match")
+        out = {"dt_gt": dt_gt.cpu().numpy(), "dt_ig": dt_ig.cpu().numpy().astype(bool), "gt_ig": gt_ig.cpu().numpy().astype(bool)}
+        skipped = int(n_over.cpu().item())
+    over = np.nonzero(gt_counts > COCO_MATCH_MAX_GT)[0]
+    if skipped != len(over):
+        raise RuntimeError("coco_match: the kernel left {} groups to the host, the tables say {}".format(skipped, len(over)))
+    if len(over):
+        from .data.datasets.evaluation.coco import coco_eval_host as H
+        iou_h = iou_d.cpu().numpy() if any(det_counts[k] for k in over) else None
+        d_area_h, g_area_h, crowd_h = d_area.cpu().numpy(), g_area.cpu().numpy(), crowd.cpu().numpy().astype(bool)
+        for k in over:
+            D, G = int(det_counts[k]), int(gt_counts[k])
+            ds, gs = slice(det_off[k], det_off[k + 1]), slice(gt_off[k], gt_off[k + 1])
+            mat = iou_h[iou_off[k]: iou_off[k + 1]].reshape(D, G) if D else np.zeros((0, G))
+            r = H.evaluate_img(mat, d_area_h[ds], g_area_h[gs], crowd_h[gs], area_rng, thrs)
+            out["dt_gt"][:, :, ds], out["dt_ig"][:, :, ds], out["gt_ig"][:, gs] = r["dt_gt"], r["dt_ig"], r["gt_ig"]
+    out["n_fallback"] = len(over)
+    return out

@@ -704,6 +704,34 @@ int abr_poly_mask_targets(const float* const* coord_ptrs, const int64_t* const* 
                           const int32_t* dims, const float* const* gt_ptrs, const float* rois, const int64_t* pos_rows, int P_max, int K, int N, int M,
                           float* out, void* stream);
 
+/* =====================================================================================================
+ * 13. COCO detection scoring (csrc/coco_eval.hip): the per-image work of pycocotools' COCOeval -- computeIoU and evaluateImg -- restated
+ *     from the protocol.  A GROUP is one (image, category) pair: its detections in rank order (score descending,
+ *     stable, at most maxDets) and its ground truths in file order.  The groups of a batch lie flat: group k owns detections
+ *     [det_off[k], det_off[k+1]), ground truths [gt_off[k], gt_off[k+1]) and the row-major D_k x G_k float64 IoU matrix at iou_off[k]
+ *     (iou_off[k+1] - iou_off[k] == D_k * G_k); all three tables int64 [n_groups+1].  Every call is ONE launch for the batch.
+ * ===================================================================================================== */
+#define ABR_COCO_MATCH_MAX_GT 128
+/* the ground truths per group abr_coco_match holds (ABR_COCO_MATCH_MAX_GT) */
+int abr_coco_match_max_gt(void);
+/* bbIou: det [D_total,4], gt [G_total,4] float64 xywh, gt_crowd uint8 [G_total] -> iou float64 [total], total = iou_off[n_groups].
+ * area = w * h (no + 1); a pair whose intersection has no positive width or height gets 0; else i / (a_d + a_g - i), or i / a_d when the
+ * ground truth is a crowd.  One rounding per operation. */
+int abr_coco_box_iou(const double* det, const double* gt, const uint8_t* gt_crowd, const int64_t* det_off, const int64_t* gt_off,
+                     const int64_t* iou_off, int n_groups, int64_t total, double* iou, void* stream);
+/* The counts of abr_mask_pair_counts for one image (inter [P,T], area_p [P], area_t [T]) and gt_crowd uint8 [T] -> iou float64 [P,T]:
+ * inter / (area_p + area_t - inter), or inter / area_p for a crowd column; 0 where inter == 0.  P == 0 or T == 0: nothing launched. */
+int abr_coco_mask_iou(const int32_t* inter, const int32_t* area_p, const int32_t* area_t, const uint8_t* gt_crowd, int P, int T, double* iou,
+                      void* stream);
+/* evaluateImg for every group, all A area ranges (area_rng float64 [A,2], both ends inclusive) and all T IoU thresholds (thrs float64 [T],
+ * used as given) at once; A <= 8 and A * T <= 64.  det_area [D_total], gt_area [G_total] float64.  Outputs: dt_gt int32 [A,T,D_total]: the
+ * matched ground truth's ROW in its group, -1 = unmatched; dt_ig uint8 [A,T,D_total]: the detection is ignored; gt_ig uint8 [A,G_total]:
+ * the ground truth is ignored (a crowd, or its area outside the range).  A group with more than ABR_COCO_MATCH_MAX_GT ground truths is
+ * NOT scored: none of its outputs is written and *n_over (device int32, zeroed by the caller) counts it -- the caller scores it on the host. */
+int abr_coco_match(const double* iou, const int64_t* iou_off, const int64_t* det_off, const int64_t* gt_off, const double* det_area,
+                   const double* gt_area, const uint8_t* gt_crowd, int n_groups, int64_t d_total, int64_t g_total, const double* area_rng, int A,
+                   const double* thrs, int T, int32_t* dt_gt, uint8_t* dt_ig, uint8_t* gt_ig, int32_t* n_over, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

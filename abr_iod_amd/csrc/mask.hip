@@ -107,6 +107,7 @@ __global__ __launch_bounds__(256) void mask_targets_kernel(const T* const* __res
     const int xmin = s[1], ymin = s[2], cw = s[3], ch = s[4];
     const T* m = mask_ptrs[img] + (int64_t)s[0] * H * W;
     const float sh = (float)ch / (float)M, sw = (float)cw / (float)M;
+    const bool four_weight = bilinear_four_weight_path(M, M);   // torch's resize changes its operation order beyond M = 64 (mask_bilinear.h)
     for (int i = threadIdx.x; i < M * M; i += 256) {
         const int oy = i / M, ox = i - oy * M;
         int y0, y1, x0, x1;
@@ -115,7 +116,8 @@ __global__ __launch_bounds__(256) void mask_targets_kernel(const T* const* __res
         bilinear_tap(sw, ox, cw, x0, x1, lx);
         const T* r0 = m + (int64_t)(ymin + y0) * W + xmin;
         const T* r1 = m + (int64_t)(ymin + y1) * W + xmin;
-        float v = bilinear_mix((float)r0[x0], (float)r0[x1], (float)r1[x0], (float)r1[x1], lx, ly);
+        const float v00 = (float)r0[x0], v01 = (float)r0[x1], v10 = (float)r1[x0], v11 = (float)r1[x1];
+        float v = four_weight ? bilinear_mix(v00, v01, v10, v11, lx, ly) : bilinear_mix_separable(v00, v01, v10, v11, lx, ly);
         if (sizeof(T) == 1) v = (float)(unsigned char)(int)v;    // .type_as(uint8 masks): truncation
         o[i] = v;
     }

@@ -91,40 +91,7 @@ def test_compaction_matching_and_targets_vs_reference():
 
 
 # ------------------------------------------------------------------------------------------------ loss
-def _check_loss(logits_nchw, labels, targets, n_pos=None, tag=""):
-    """logits [P,K,M,M] fp32 (CPU), labels [P] (<= 0: skipped), targets [P,M,M] against float64 BCE; tolerances of test_gpu_loss_kernels.py:
-    1e-6 relative to the sum of |addends| for the loss, a few ulps of the largest term for each gradient element"""
-    from abr_iod_amd import ops
-    P, K, M, _ = logits_nchw.shape
-    ld = (K + 3) // 4 * 4
-    z = torch.zeros(P, M, M, ld)
-    z[..., :K] = logits_nchw.permute(0, 2, 3, 1)
-    args = (z.cuda(), K, labels.cuda(), targets.cuda())
-    nd = None if n_pos is None else torch.tensor([n_pos], dtype=torch.int32, device="cuda")
-    loss, grad = ops.mask_loss(*args, n_pos=nd, want_grad=True)
-    loss2, grad2 = ops.mask_loss(*args, n_pos=nd, want_grad=True)
-    assert torch.equal(loss, loss2) and torch.equal(grad, grad2), tag + ": two runs differ"
-    pos = (labels > 0).nonzero().flatten()
-    n = len(pos) if n_pos is None else n_pos
-    x64 = logits_nchw.double()
-    if n == 0 or len(pos) == 0:
-        assert float(loss) == 0.0 and not bool(grad.any()), tag
-        return float(loss)
-    sel = x64[pos, labels[pos]]
-    t64 = targets.double()[pos]
-    terms = sel.clamp(min=0) - sel * t64 + torch.log1p(torch.exp(-sel.abs()))
-    want = terms.sum() / (n * M * M)
-    # (the analytic gradient: autograd through max(x, 0) and |x| takes a one-sided derivative at x == 0, where the loss is smooth)
-    want_grad = torch.zeros_like(x64)
-    want_grad[pos, labels[pos]] = (torch.sigmoid(sel) - t64) / (n * M * M)
-    addends = float(terms.abs().sum() / (n * M * M))
-    print(tag, "loss", float(loss), "float64", float(want), "rel to addends", abs(float(loss) - float(want)) / max(addends, 1e-300))
-    assert abs(float(loss) - float(want)) <= 1e-6 * addends + 1e-30, tag
-    got = grad.cpu()[..., :K].permute(0, 3, 1, 2).double()
-    gtol = 8 * EPS / (n * M * M)
-    assert float((got - want_grad).abs().max()) <= gtol, (tag, float((got - want_grad).abs().max()), gtol)
-    assert not bool(grad.cpu()[..., K:].any())
-    return float(loss)
+from mask_loss_check import check_loss as _check_loss  # noqa: E402  (shared with tests/test_gpu_mask_kernels.py)
 
 
 def test_mask_loss_vs_float64_and_reference():

@@ -184,6 +184,13 @@ _SIGS = {
     "abr_coco_box_iou": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
     "abr_coco_mask_iou": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "abr_coco_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "abr_kp_select_targets": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "abr_kp_deconv_fold": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_kp_deconv_unfold": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_kp_upsample2x": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "abr_kp_loss_max_plane": (_i, []),
+    "abr_kp_loss": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "abr_kp_decode": (_i, [_vp, _i64, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 # every symbol include/abr_iod_hip.h declares (tests/test_abi.py checks the library exports them all)

@@ -195,6 +195,11 @@ class BoxRehearsalABR(object):
     # ------------------------------------------------------------------ entry point
     def transform_current_data_with_ABR(self, img, target):
         """MIX : MOS : NEW = 1 : 1 : 2 (:821-838)"""
+        if target is not None and target.has_field("keypoints"):
+            # the mixup and the mosaic rebuild their targets from boxes and labels alone: a pasted batch would reach the keypoint head without
+            # the field it needs
+            raise NotImplementedError("box rehearsal (ABR mixup / mosaic) with a \"keypoints\" target field: the pasted targets carry boxes and "
+                                      "labels only, so MODEL.KEYPOINT_ON cannot train on them; run keypoint training without the ABR transform")
         is_mosaic = is_mixup = False
         if random.randint(0, 1) == 0:
             if random.randint(0, 1) == 0:

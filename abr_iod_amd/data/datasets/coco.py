@@ -85,6 +85,9 @@ class COCODataset(object):
             if any(not isinstance(s, (list, tuple)) for s in segs):
                 raise ValueError("image {}: a non-crowd annotation whose segmentation is not a polygon list".format(self.ids[index]))
             target.add_field("masks", PolygonList(segs, size, device=self.device))
+        if anno and "keypoints" in anno[0]:      # coco.py:258-261: a person-keypoint file hands its keypoints to the model (MODEL.KEYPOINT_ON)
+            from ...structures.keypoint import PersonKeypoints
+            target.add_field("keypoints", PersonKeypoints(torch.tensor([obj["keypoints"] for obj in anno], dtype=torch.float32).to(self.device), size))
         return target.clip_to_image(remove_empty=True)
 
     def __getitem__(self, index):

@@ -6,7 +6,8 @@ over every image, category, area range and IoU threshold.  Here the protocol is 
     ranges and thresholds (ops.coco_match);
   * the short accumulation and the 12 summary numbers stay on the host in float64 (coco_eval_host.py).
 device="cpu" scores everything with the host restatement instead: the yardstick of the tests, never chosen silently.
-Not carried: box_only (proposal recall) and keypoints."""
+Not carried: box_only (proposal recall) and keypoint scoring (OKS): the keypoint head (MODEL.KEYPOINT_ON) puts a "keypoints" field on the
+detections, and do_coco_evaluation keeps raising for the "keypoints" iou type."""
 import json
 import logging
 import os

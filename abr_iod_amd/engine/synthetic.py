@@ -115,12 +115,15 @@ def _box_polygons(boxes, sides=24):
     return [[poly.reshape(-1).tolist()] for poly in xy]
 
 
-def synthetic_batch(batch, height=600, width=1000, seed=42, label_range=(16, 21), device="cuda", max_boxes=5, masks=None, mask_dtype=torch.uint8):
+def synthetic_batch(batch, height=600, width=1000, seed=42, label_range=(16, 21), device="cuda", max_boxes=5, masks=None, mask_dtype=torch.uint8,
+                    keypoints=None):
     """images: uint8-valued U[0,255] BGR minus PIXEL_MEAN (transforms.py:161-165 + defaults.py:56-60);
     targets: 1..max_boxes GT boxes per image, w,h log-uniform in [32,480], labels over the task's NEW class ids.
     masks="ellipse" / "rect" (opt-in, MODEL.MASK_ON): a "masks" field (SegmentationMask, mode "mask", mask_dtype uint8 or float32) with one
     instance inside each GT box; masks="poly": the ellipse as a 24-gon in a PolygonList (structures/polygon.py); images, boxes and labels
-    are the same with and without it."""
+    are the same with and without it.
+    keypoints=K (opt-in, MODEL.KEYPOINT_ON): a "keypoints" field (PersonKeypoints [n,K,3]) of fixed points inside each GT box, every fourth one
+    with visibility 0 (and x = y = 0, the COCO convention); no random number is drawn for them, so images, boxes and labels stay the same."""
     g = torch.Generator().manual_seed(seed)
     mean = torch.tensor([102.9801, 115.9465, 122.7717]).view(1, 3, 1, 1)
     images = torch.randint(0, 256, (batch, 3, height, width), generator=g).float() - mean
@@ -141,5 +144,20 @@ def synthetic_batch(batch, height=600, width=1000, seed=42, label_range=(16, 21)
         elif masks is not None:
             from ..structures.segmentation_mask import SegmentationMask
             t.add_field("masks", SegmentationMask(_box_masks(boxes, height, width, masks, mask_dtype).to(device), (width, height), mode="mask"))
+        if keypoints:
+            from ..structures.keypoint import PersonKeypoints
+            t.add_field("keypoints", PersonKeypoints(_box_keypoints(boxes, int(keypoints)).to(device), (width, height)))
         targets.append(t)
     return images.to(device), targets
+
+
+def _box_keypoints(boxes, K):
+    """[n,K,3]: keypoint k of instance j sits at a fixed fraction of its box, visibility 2; (j + k) % 4 == 3: not labelled (0, 0, 0)"""
+    n = boxes.shape[0]
+    j, k = torch.arange(n).view(n, 1), torch.arange(K).view(1, K)
+    fx = (((7 * k + 3 * j) % 11).float() + 0.5) / 11
+    fy = (((5 * k + 2 * j) % 13).float() + 0.5) / 13
+    x = boxes[:, 0:1] + fx * (boxes[:, 2:3] - boxes[:, 0:1])
+    y = boxes[:, 1:2] + fy * (boxes[:, 3:4] - boxes[:, 1:2])
+    vis = torch.where((j + k) % 4 == 3, 0.0, 2.0)
+    return torch.stack((x * (vis > 0), y * (vis > 0), vis), -1)

@@ -1,8 +1,11 @@
-"""CombinedROIHeads (mirror of maskrcnn_benchmark/modeling/roi_heads/roi_heads.py:9-77): the box head and, under MODEL.MASK_ON, the C4 mask
-head behind it (mask_head/mask_head.py).  KEYPOINT_ON is False in every configs/voc YAML (defaults.py:27) and not built."""
+"""CombinedROIHeads (mirror of maskrcnn_benchmark/modeling/roi_heads/roi_heads.py:9-77): the box head and, behind it, the C4 mask head under
+MODEL.MASK_ON (mask_head/mask_head.py) and the keypoint head under MODEL.KEYPOINT_ON (keypoint_head/keypoint_head.py; its own extractor on
+the backbone features, SHARE_BOX_FEATURE_EXTRACTOR False).  The keypoint head adds loss_kp in training and a "keypoints" field to the
+detections in eval; it has no distillation term (the reference has none): calculate_soften_label does not see it."""
 import torch
 
 from .box_head.box_head import build_roi_box_head
+from .keypoint_head.keypoint_head import build_roi_keypoint_head, check_keypoint_head_cfg
 from .mask_head.mask_head import build_roi_mask_head, check_mask_head_cfg
 
 
@@ -22,6 +25,10 @@ class CombinedROIHeads(torch.nn.ModuleDict):
         t = getattr(self.box.loss_evaluator, "_fused_targets", None)     # the fused sampler's RoI table and labels, already single device tensors
         return self.mask(x, detections, targets, fused=t)
 
+    def _keypoint_train(self, features, detections, targets):
+        t = getattr(self.box.loss_evaluator, "_fused_targets", None)
+        return self.keypoint(features, detections, targets, fused=t)
+
     def forward(self, features, proposals, targets=None):
         """training -> (x, detections, soften_results, losses, roi_align_features); eval -> (x, detections, results_background, [])
         (roi_heads.py:23-63)"""
@@ -31,12 +38,17 @@ class CombinedROIHeads(torch.nn.ModuleDict):
             x, detections, results_background = self.box(features, proposals, targets)
             if mask_on:     # roi_heads.py:33-45: the mask head runs the shared extractor on the DETECTIONS
                 x, detections, _ = self.mask(features, detections, targets)
+            if "keypoint" in self:
+                x, detections, _ = self.keypoint(features, detections, targets)
             return x, detections, results_background, []
         x, detections, soft_res, loss_box, roi_align_features = self.box(features, proposals, targets)
         losses.update(loss_box)
         if mask_on:         # training: the box head's layer4 rows of the positives, no second ROIAlign / layer4 pass
             _, detections, loss_mask = self._mask_train(x, detections, targets)
             losses.update(loss_mask)
+        if "keypoint" in self:     # its own ROIAlign + conv stack on the backbone features, for the sampled positives
+            _, detections, loss_kp = self._keypoint_train(features, detections, targets)
+            losses.update(loss_kp)
         return x, detections, soft_res, losses, roi_align_features
 
     def forward_joint(self, features, proposals, targets, soften_proposals):
@@ -48,6 +60,9 @@ class CombinedROIHeads(torch.nn.ModuleDict):
             losses.update(loss_mask)
             mask_logits = self.mask.calculate_soften_label(self.box.last_joint_soft_x)
             self.box.last_joint_soft_x = None
+        if "keypoint" in self:
+            _, detections, loss_kp = self._keypoint_train(features, detections, targets)
+            losses.update(loss_kp)
         return (x, detections, soft_res, losses, raf), (s_score, s_bbox, mask_logits, s_raf)
 
     def calculate_soften_label(self, features, proposals, targets=None):
@@ -58,13 +73,17 @@ class CombinedROIHeads(torch.nn.ModuleDict):
 
 
 def build_roi_heads(cfg, in_channels):
-    if cfg.MODEL.RETINANET_ON or cfg.MODEL.KEYPOINT_ON:
-        raise NotImplementedError("only the box and mask heads are on the hot path (SURVEY.md §2 rows 6b/7b)")
+    if cfg.MODEL.RETINANET_ON:
+        raise NotImplementedError("only the box, mask and keypoint heads are on the hot path (SURVEY.md §2 row 6b)")
     if cfg.MODEL.MASK_ON:
         check_mask_head_cfg(cfg)
+    if cfg.MODEL.KEYPOINT_ON:
+        check_keypoint_head_cfg(cfg)
     if cfg.MODEL.RPN_ONLY:
         return []
     heads = [("box", build_roi_box_head(cfg, in_channels))]
     if cfg.MODEL.MASK_ON:
         heads.append(("mask", build_roi_mask_head(cfg, in_channels, heads[0][1].feature_extractor)))
+    if cfg.MODEL.KEYPOINT_ON:
+        heads.append(("keypoint", build_roi_keypoint_head(cfg, in_channels)))
     return CombinedROIHeads(cfg, heads)

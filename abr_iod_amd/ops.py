@@ -1736,6 +1736,120 @@ def poly_mask_targets(polys_per_image, gt_boxes, rois, pos_rows, M):
     return out
 
 
+# ----------------------------------------------------------------------------------------------- keypoint head (csrc/keypoint.hip)
+def kp_pad(K):
+    """the planar heat maps' channel count: K rounded up to a multiple of 4"""
+    return (int(K) + 3) // 4 * 4
+
+
+def kp_select_targets(rois, labels, gt_boxes, keypoints, M, p_max):
+    """rois [R,5] / labels [R]: the box head's sampled set; gt_boxes: per-image [n,4]; keypoints: per-image [n,K,3] (x, y, visibility)
+    -> dict(pos_rows [p_max] int64 (-1 padded, ascending), inv [R], n_pos int32 [1], targets [p_max,K] int64, valid [p_max,K] uint8,
+    n_valid int32 [1]): the positives whose matched instance has a visible keypoint inside its box, and their heat-map indices on the
+    M x M map (abr_kp_select_targets); nothing is read back"""
+    L.require_cuda(rois, labels, *keypoints)
+    dev = rois.device
+    if len(gt_boxes) != len(keypoints) or not len(gt_boxes):
+        raise RuntimeError("kp_select_targets: {} keypoint tensors for {} images".format(len(keypoints), len(gt_boxes)))
+    K = int(keypoints[0].shape[1])
+    for k, g in zip(keypoints, gt_boxes):
+        if k.dim() != 3 or k.shape[1] != K or k.shape[2] != 3 or k.shape[0] != g.shape[0]:
+            raise RuntimeError("kp_select_targets: keypoints must be [n,{},3] with one row per ground-truth box, got {} for {} boxes".format(
+                K, tuple(k.shape), g.shape[0]))
+    ks, gs = [L.f32c(k) for k in keypoints], [L.f32c(g) for g in gt_boxes]
+    rois, labels = L.f32c(rois), labels.to(torch.int64).contiguous()
+    R, N, p_max = labels.numel(), len(gs), int(p_max)
+    i64 = torch.int64
+    out = dict(pos_rows=torch.empty((p_max,), dtype=i64, device=dev), inv=torch.empty((R,), dtype=i64, device=dev),
+               n_pos=torch.empty((1,), dtype=torch.int32, device=dev), targets=torch.empty((p_max, K), dtype=i64, device=dev),
+               valid=torch.empty((p_max, K), dtype=torch.uint8, device=dev), n_valid=torch.empty((1,), dtype=torch.int32, device=dev))
+    n_gt = _small_table([int(g.shape[0]) for g in gs], torch.int32, dev)
+    tab = _pointer_table(gs + ks, dev)       # ONE upload: two tables of N addresses (held in a local until the launch: _evict_oldest)
+    t0 = L.ptr(tab)
+    L.check(L.lib().abr_kp_select_targets(L.ptr(rois), L.ptr(labels), R, t0, t0 + 8 * N, L.ptr(n_gt), N, K, int(M), p_max, L.ptr(out["pos_rows"]),
+                                          L.ptr(out["inv"]), L.ptr(out["n_pos"]), L.ptr(out["targets"]), L.ptr(out["valid"]),
+                                          L.ptr(out["n_valid"]), L.stream()), "kp_select_targets")
+    return out
+
+
+def kp_deconv_fold(y, bias):
+    """y [P,h,w,16*Kp] (the deconvolution's GEMM, columns (ky*4+kx)*Kp + k), bias [K] -> planar [P,Kp,2h,2w] = ConvTranspose2d(., K, 4, 2, 1);
+    the planes k >= K are zeros"""
+    L.require_cuda(y, bias)
+    y, bias = L.f32c(y), L.f32c(bias)
+    P, h, w, c = y.shape
+    K = bias.numel()
+    Kp = kp_pad(K)
+    if c != 16 * Kp:
+        raise RuntimeError("kp_deconv_fold: {} columns for {} keypoints (want 16 * {})".format(c, K, Kp))
+    out = torch.empty((P, Kp, 2 * h, 2 * w), dtype=_f32, device=y.device)
+    L.check(L.lib().abr_kp_deconv_fold(L.ptr(y), L.ptr(bias), P, h, w, K, L.ptr(out), L.stream()), "kp_deconv_fold")
+    return out
+
+
+def kp_deconv_unfold(g, K):
+    """the fold's adjoint: g [P,Kp,2h,2w] -> [P,h,w,16*Kp] (zeros outside the map and in the columns k >= K)"""
+    L.require_cuda(g)
+    g = L.f32c(g)
+    P, Kp, H, W = g.shape
+    if Kp != kp_pad(K) or H % 2 or W % 2:
+        raise RuntimeError("kp_deconv_unfold: a {} gradient for {} keypoints".format(tuple(g.shape), K))
+    gy = torch.empty((P, H // 2, W // 2, 16 * Kp), dtype=_f32, device=g.device)
+    L.check(L.lib().abr_kp_deconv_unfold(L.ptr(g), P, H // 2, W // 2, int(K), L.ptr(gy), L.stream()), "kp_deconv_unfold")
+    return gy
+
+
+def kp_upsample2x(x, K):
+    """planar x [P,Kp,H,W] -> [P,K,2H,2W]: interpolate(scale_factor=2, mode="bilinear", align_corners=False) of the first K channels"""
+    L.require_cuda(x)
+    x = L.f32c(x)
+    P, Kp, H, W = x.shape
+    if Kp != kp_pad(K):
+        raise RuntimeError("kp_upsample2x: {} channels for {} keypoints".format(Kp, K))
+    out = torch.empty((P, int(K), 2 * H, 2 * W), dtype=_f32, device=x.device)
+    L.check(L.lib().abr_kp_upsample2x(L.ptr(x), P, int(K), H, W, L.ptr(out), L.stream()), "kp_upsample2x")
+    return out
+
+
+def kp_loss(x, K, targets, valid, n_valid, gscale=1.0, want_grad=False):
+    """x [P,Kp,H,W] planar low-resolution maps; targets [P,K] int64 / valid [P,K] uint8 on the UPSAMPLED 2H x 2W map; n_valid device int32
+    -> (loss [1], grad like x or None, row_sum [P,Kp] or None): 2x bilinear upsampling + cross-entropy over each valid row's 4 H W logits,
+    mean over n_valid rows (0: loss 0, zero gradients); the gradient is with respect to x"""
+    L.require_cuda(x, targets, valid, n_valid)
+    x = L.f32c(x)
+    P, Kp, H, W = x.shape
+    if Kp != kp_pad(K) or tuple(targets.shape) != (P, K) or tuple(valid.shape) != (P, K):
+        raise RuntimeError("kp_loss: maps {} with targets {} / valid {} for {} keypoints".format(tuple(x.shape), tuple(targets.shape), tuple(valid.shape), K))
+    if targets.dtype != torch.int64 or valid.dtype != torch.uint8 or n_valid.dtype != torch.int32:
+        raise RuntimeError("kp_loss: targets int64, valid uint8, n_valid int32")
+    loss = _empty((1,), x)
+    grad = torch.empty_like(x) if want_grad else None
+    row_sum = torch.empty((P, Kp), dtype=_f32, device=x.device) if want_grad else None
+    L.check(L.lib().abr_kp_loss(L.ptr(x), P, int(K), H, W, L.ptr(targets.contiguous()), L.ptr(valid.contiguous()), L.ptr(n_valid), float(gscale),
+                                L.ptr(loss), L.ptr(grad), L.ptr(row_sum), L.stream()), "kp_loss")
+    return loss, grad, row_sum
+
+
+def kp_decode(maps, boxes):
+    """maps [D,K,Hm,Wm] (each plane contiguous), boxes [D,4] xyxy -> (keypoints [D,K,3] = (x, y, 1), logits [D,K]): heatmaps_to_keypoints
+    (keypoint_head/inference.py:40-94) on the device -- the bicubic resize to the RoI restated, first maximum in row-major order"""
+    L.require_cuda(maps, boxes)
+    if maps.dtype != _f32 or maps.dim() != 4:
+        raise RuntimeError("kp_decode: maps must be float32 [D,K,Hm,Wm]")
+    D, K, Hm, Wm = maps.shape
+    if D and (maps.stride(3) != 1 or maps.stride(2) != Wm):
+        maps = maps.contiguous()
+    boxes = L.f32c(boxes)
+    if tuple(boxes.shape) != (D, 4):
+        raise RuntimeError("kp_decode: {} boxes for {} maps".format(tuple(boxes.shape), D))
+    xy = torch.empty((D, K, 3), dtype=_f32, device=maps.device)
+    logit = torch.empty((D, K), dtype=_f32, device=maps.device)
+    if D:
+        L.check(L.lib().abr_kp_decode(L.ptr(maps), maps.stride(0), maps.stride(1), L.ptr(boxes), D, K, Hm, Wm, L.ptr(xy), L.ptr(logit), L.stream()),
+                "kp_decode")
+    return xy, logit
+
+
 # ----------------------------------------------------------------------------------------------- COCO scoring (csrc/coco_eval.hip)
 COCO_MATCH_MAX_GT = 128      # ABR_COCO_MATCH_MAX_GT: the ground truths per group coco_match's kernel holds
 

@@ -732,6 +732,46 @@ int abr_coco_match(const double* iou, const int64_t* iou_off, const int64_t* det
                    const double* gt_area, const uint8_t* gt_crowd, int n_groups, int64_t d_total, int64_t g_total, const double* area_rng, int A,
                    const double* thrs, int T, int32_t* dt_gt, uint8_t* dt_ig, uint8_t* gt_ig, int32_t* n_over, void* stream);
 
+/* =====================================================================================================
+ * 14. Keypoint head (MODEL.KEYPOINT_ON; csrc/keypoint.hip; maskrcnn_benchmark/modeling/roi_heads/keypoint_head/).  The low-resolution heat
+ *     maps are PLANAR [P,Kp,H,W], Kp = K rounded up to a multiple of 4; channels k >= K are padding.  fp32 arithmetic, no read-back, no
+ *     floating-point atomics: every sum has a fixed order and two runs agree bit for bit.
+ * ===================================================================================================== */
+/* keypoint_head/loss.py:39-143 + structures/keypoint.py:154-188 for the whole batch in one launch.  rois [R,5] (image index, xyxy) and
+ * labels [R] are the box head's sampled set.  A row is kept when labels > 0 and the instance of its image with the first maximum IoU
+ * (gt_ptrs[img] [n_gt[img],4]) has a keypoint (kp_ptrs[img] [n_gt[img],K,3] = x, y, visibility) that is visible (> 0) and inside that
+ * instance's box (inclusive).  Kept rows in ascending order: pos_rows [P_max] int64 (-1 padded; rows past P_max are dropped), inv [R] =
+ * position in pos_rows or -1, *n_pos.  tgt [P_max,K] int64 = y * M + x with x = floor((kx - x1) * ((1 / (x2 - x1)) * M)) in fp32, torch's order (kx == x2
+ * gives M - 1; the same for y), 0 where valid [P_max,K] uint8 is 0: the keypoint is not visible or leaves [0, M) on an axis (inf and NaN
+ * of a zero-width RoI included).  *n_valid = the number of valid entries.  An image index outside [0, N) or n_gt[img] <= 0: row dropped. */
+int abr_kp_select_targets(const float* rois, const int64_t* labels, int R, const float* const* gt_ptrs, const float* const* kp_ptrs,
+                          const int32_t* n_gt, int N, int K, int M, int P_max, int64_t* pos_rows, int64_t* inv, int32_t* n_pos, int64_t* tgt,
+                          uint8_t* valid, int32_t* n_valid, void* stream);
+/* ConvTranspose2d(C, K, 4, stride 2, padding 1) behind its GEMM: y [P,h,w,16*Kp] (columns (ky*4+kx)*Kp + k) -> out [P,Kp,2h,2w] planar,
+ * out[p,k,oy,ox] = bias[k] + sum of y[p,iy,ix,(ky,kx,k)] over the at most 2 x 2 taps with oy = 2 iy - 1 + ky, ox = 2 ix - 1 + kx, added
+ * in (ky, kx) order; bias [K]; the planes k >= K are written as zeros. */
+int abr_kp_deconv_fold(const float* y, const float* bias, int P, int h, int w, int K, float* out, void* stream);
+/* the fold's exact adjoint: g [P,Kp,2h,2w] -> gy [P,h,w,16*Kp], zeros for taps outside the map and for columns k >= K */
+int abr_kp_deconv_unfold(const float* g, int P, int h, int w, int K, float* gy, void* stream);
+/* interpolate(scale_factor=2, mode="bilinear", align_corners=False): x [P,Kp,H,W] planar -> out [P,K,2H,2W] */
+int abr_kp_upsample2x(const float* x, int P, int K, int H, int W, float* out, void* stream);
+/* the largest H * W abr_kp_loss and Hm * Wm abr_kp_decode stage in LDS (4096 floats, 16 KB) */
+int abr_kp_loss_max_plane(void);
+/* keypoint_head/loss.py:145-169 on the low-resolution maps: the 2x bilinear upsampling and F.cross_entropy over the 4 H W upsampled logits
+ * of every row with valid[p,k] != 0, mean over *n_valid rows (device int32; 0 gives loss 0 and zero gradients).  x [P,Kp,H,W], tgt / valid
+ * [P,K] index the UPSAMPLED map (a target outside [0, 4 H W) makes its row invalid).  grad (optional) [P,Kp,H,W] is written whole: the
+ * gradient with respect to x, times gscale, zeros for invalid rows and padding channels; row_sum (optional, with grad) [P,Kp] = each
+ * plane's gradient sum (abr_bias_grad over it is the deconvolution's bias gradient).  H * W <= abr_kp_loss_max_plane(), P * Kp <= 65536. */
+int abr_kp_loss(const float* x, int P, int K, int H, int W, const int64_t* tgt, const uint8_t* valid, const int32_t* n_valid, float gscale,
+                float* loss_out, float* grad, float* row_sum, void* stream);
+/* keypoint_head/inference.py:40-94 on the device.  maps: plane (d, k) at maps + d * stride_d + k * stride_k, Hm x Wm contiguous; boxes
+ * [D,4] xyxy.  Each plane is resized to ceil(max(w, 1)) x ceil(max(h, 1)) by the bicubic rule (Keys' kernel, a = -0.75, source coordinate
+ * (d + 0.5) src / dst - 0.5, replicated borders, no antialiasing) and its first maximum in row-major order is taken (the lowest index among
+ * equal values; NaN values never win, a plane without a value above -inf gives index 0).  xy [D,K,3] = ((x_int + 0.5) w / ceil(w) + x1,
+ * the same for y, 1); logit [D,K] = the resized value there.  The grid's sides are clamped to 8192.  Hm * Wm <= abr_kp_loss_max_plane(). */
+int abr_kp_decode(const float* maps, int64_t stride_d, int64_t stride_k, const float* boxes, int D, int K, int Hm, int Wm, float* xy,
+                  float* logit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,11 @@ def fuzz_coverage_problems(cov, strata, per_stratum, ran=True):
         need(c["cases"] >= per_stratum, "%s: %d cases < %d" % (st, c["cases"], per_stratum))
         need(c["misrouted"] == 0, "%s: %d drawn cases the library routes elsewhere" % (st, c["misrouted"]))
         need(not ran or c["comparisons"] > 0, "%s: no comparison ran" % st)
+        if ran:     # every forward / input-gradient result that was compared had its amax word read and compared with max |result| as well
+            for m, n in sorted(c.get("fwd_dgrad", {}).items()):
+                k = c.get("amax_checks", {}).get(m, 0)
+                need(n == 0 or (k > 0 and k >= n), "%s: %s compared %d forward / input-gradient results but checked %d amax words" % (st, m, n, k))
+            need("fwd_dgrad" in c and "amax_checks" in c, "%s: the run does not report its amax checks" % st)
         routes, feats = c["routes"], c["features"]
         if st == "wino":
             for m in FUZZ_FULL:

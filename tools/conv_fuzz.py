@@ -15,6 +15,9 @@ stratum's fails the run:
   tail64           the fused bottleneck tail, bit-equal to the two convs it replaces, and both against float64
   dgrad_fused      the input gradient with the ReLU mask and / or a residual fused into its epilogue
 A configuration the library does not support must raise (counted, listed), never return wrong values.
+Every forward and input-gradient call asks for the output's amax word (emit_amax=True, in all arithmetics); where the result carries the
+tag, the word must hold exactly the bits of max |result| (the definition tests/amax_words.py::expect checks, restated below: the tool needs
+nothing from tests/ but conv_ref.py, so it also runs beside an older tests/ directory): counted as amax_checks per stratum and mode.
 GPU box: python tools/conv_fuzz.py [--cases 300] [--per-stratum 40] [--seed 0] [--strata any,wino,...]; --plan draws, asks the library for
 the routes and prints the counts without touching a device."""
 import argparse
@@ -51,7 +54,8 @@ WIDE_IN, WIDE_OUT = [128, 160, 192, 256, 320, 512], [128, 160, 192, 256, 512]
 EPS = 2.0 ** -24
 PTR = torch.zeros(4)     # stands for "a residual is given" in a route query (the route looks at the pointer only)
 fails, refused, ran = [], {}, 0
-cov = {}                 # stratum -> {"cases", "comparisons", "misrouted", "routes": {mode: {"op/route": n}}, "features": {...}, "reasons": {...}}
+cov = {}                 # stratum -> {"cases", "comparisons", "misrouted", "routes": {mode: {"op/route": n}}, "features": {...}, "reasons": {...},
+#                                       "fwd_dgrad": {mode: forward / input-gradient comparisons that ran}, "amax_checks": {mode: n}}
 cur = [None]             # the stratum being drawn
 
 
@@ -59,15 +63,62 @@ def nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous().float().cuda()
 
 
-def check(tag, case, got, want, tol):
+_hip = []
+
+
+def expect(word, epoch, t, what):
+    """the amax word at device address `word` carries `epoch` and exactly the bits of max |t| (integer order on magnitudes, read from the
+    tensor copied back from the device): tests/amax_words.py::expect"""
+    import ctypes
+    if not _hip:
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        _hip.append(hip)
+    host = ctypes.c_uint64(0)
+    torch.cuda.synchronize()
+    assert _hip[0].hipMemcpy(ctypes.byref(host), ctypes.c_void_p(word), 8, 2) == 0   # hipMemcpyDeviceToHost
+    got = (int(host.value) >> 32, int(host.value) & 0xFFFFFFFF)
+    want = (int(epoch) & 0xFFFFFFFF, int((t.detach().cpu().contiguous().view(torch.int32) & 0x7FFFFFFF).max()) if t.numel() else 0)
+    assert got == want, "%s amax word: epoch %d, bits 0x%08x; want epoch %d, bits 0x%08x = max |result|" % ((what,) + got + want)
+
+
+def check_amax(tag, case, src):
+    """src: the tensor a forward / input-gradient call returned (not a view of it: a view loses the tag), asked with emit_amax=True.  Its amax
+    word must hold exactly the bits of max |src|; a result without a tag is a failure (nothing is skipped silently)."""
+    mode = "bf16x6" if tag.startswith("tail64") else tag.split("/", 1)[1]
+    word, epoch = ops.amax_of(src)
+    if word is None:
+        fails.append((tag, case, "the result carries no amax tag"))
+        return
+    try:
+        expect(word, epoch, src, tag)
+    except AssertionError as e:
+        fails.append((tag, case, str(e)))
+    if cur[0]:
+        d = cov[cur[0]]["amax_checks"]
+        d[mode] = d.get(mode, 0) + 1
+
+
+def count(tag):
+    """one comparison of the current stratum; those of a forward / input-gradient result also per mode (fwd_dgrad)"""
     global ran
     ran += 1
     if cur[0]:
         cov[cur[0]]["comparisons"] += 1
+        op, _, mode = tag.partition("/")
+        if op in ("fwd", "fwd_keep_v", "dgrad"):
+            d = cov[cur[0]]["fwd_dgrad"]
+            d[mode] = d.get(mode, 0) + 1
+
+
+def check(tag, case, got, want, tol, src=None):
+    count(tag)
     err = (got.detach().cpu().double() - want).abs().max().item()
     lim = tol * max(1.0, want.abs().max().item())
     if not (err <= lim) or not bool(torch.isfinite(got).all()):
         fails.append((tag, case, err, lim))
+    if src is not None:
+        check_amax(tag, case, src)
 
 
 def attempt(tag, case, fn):
@@ -169,8 +220,8 @@ def run_dgrad(D, case, m, **kw):
     B, Cin, H, W, Cout, k, s, p = case
     wt = ops.conv_dgrad_weights(D.wg, D.scale.cuda())
     if s == 1:
-        return ops.conv_forward(D.gyg, wt, 1, k - 1 - p, math=m, **kw)
-    return ops.conv_forward(D.gyg, wt, 1, 0, out_hw=(H, W), out_stride=(s, s), math=m, **kw)
+        return ops.conv_forward(D.gyg, wt, 1, k - 1 - p, math=m, emit_amax=True, **kw)
+    return ops.conv_forward(D.gyg, wt, 1, 0, out_hw=(H, W), out_stride=(s, s), math=m, emit_amax=True, **kw)
 
 
 def draw_any(rng):
@@ -199,9 +250,9 @@ def stratum_any(n, seed):
             if m != ops.MATH_F32 and k == 7:
                 continue
             if Cin % 4 == 0 and step("fwd", name, route_fwd(case, m, use["residual"])[1]):
-                got = attempt("fwd/" + name, case, lambda: ops.conv_forward(D.xg, D.wg, s, p, math=m, **D.kw(use)))
+                got = attempt("fwd/" + name, case, lambda: ops.conv_forward(D.xg, D.wg, s, p, math=m, emit_amax=True, **D.kw(use)))
                 if got is not None:
-                    check("fwd/" + name, case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol)
+                    check("fwd/" + name, case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol, src=got)
             if k == 7:
                 continue      # the stem is frozen: no backward on the path
             if step("wgrad", name, route_fwd(case, m)[2]):
@@ -211,7 +262,7 @@ def stratum_any(n, seed):
             if (s == 1 or k == 1) and step("dgrad", name, route_dgrad(case, m)[1]):
                 dx = attempt("dgrad/" + name, case, lambda: run_dgrad(D, case, m))
                 if dx is not None:
-                    check("dgrad/" + name, case, dx.permute(0, 3, 1, 2), D.x.grad, tol * 2)
+                    check("dgrad/" + name, case, dx.permute(0, 3, 1, 2), D.x.grad, tol * 2, src=dx)
         if (ci + 1) % 50 == 0:
             print("%d cases, %d comparisons, %d failures, %d refusals" % (ci + 1, ran, len(fails), sum(len(v) for v in refused.values())), flush=True)
 
@@ -257,13 +308,13 @@ def stratum_wino(n, seed):
         for name, m, tol in FULL:
             _, fw, ww, _ = route_fwd(case, m)
             if step("fwd", name, fw, "wino", feats):
-                got = attempt("fwd/" + name, case, lambda: ops.conv_forward(D.xg, D.wg, 1, 1, math=m, **D.kw(use)))
+                got = attempt("fwd/" + name, case, lambda: ops.conv_forward(D.xg, D.wg, 1, 1, math=m, emit_amax=True, **D.kw(use)))
                 if got is not None:
-                    check("fwd/" + name, case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol)
+                    check("fwd/" + name, case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol, src=got)
             if step("dgrad", name, route_dgrad(case, m)[1], "wino", feats):
                 dx = attempt("dgrad/" + name, case, lambda: run_dgrad(D, case, m))
                 if dx is not None:
-                    check("dgrad/" + name, case, dx.permute(0, 3, 1, 2), D.x.grad, tol * 2)
+                    check("dgrad/" + name, case, dx.permute(0, 3, 1, 2), D.x.grad, tol * 2, src=dx)
             dw_ref = None
             if step("wgrad", name, ww, "wino", feats):
                 dw_ref = torch.zeros_like(D.wg)
@@ -276,10 +327,10 @@ def stratum_wino(n, seed):
                     misrouted("wino_v_alloc %s %s" % (name, case))
                     continue
                 v.fill_(float("nan"))
-                got = attempt("fwd_keep_v/" + name, case, lambda: ops.conv_forward(D.xg, D.wg, 1, 1, math=m, wino_v=v, **D.kw(use)))
+                got = attempt("fwd_keep_v/" + name, case, lambda: ops.conv_forward(D.xg, D.wg, 1, 1, math=m, wino_v=v, emit_amax=True, **D.kw(use)))
                 if got is None:
                     continue
-                check("fwd_keep_v/" + name, case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol)
+                check("fwd_keep_v/" + name, case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol, src=got)
                 dw = torch.zeros_like(D.wg)
                 if attempt("wgrad_kept_v/" + name, case, lambda: (ops.conv_wgrad(torch.full_like(D.xg, float("nan")), D.gyg, dw, 1, 1, scale=D.scale.cuda(),
                                                                                   math=m, wino_v=v), True)[1]):
@@ -314,9 +365,9 @@ def stratum_wino_wgrad_only(n, seed):
             run_f = step("fwd", name, fw, "direct")
             run_w = step("wgrad", name, route_fwd(case, m)[2], "wino", reason=None if fw or not ww else reason)
             if run_f:
-                got = attempt("fwd/" + name, case, lambda: ops.conv_forward(D.xg, D.wg, 1, 1, math=m, **D.kw(use)))
+                got = attempt("fwd/" + name, case, lambda: ops.conv_forward(D.xg, D.wg, 1, 1, math=m, emit_amax=True, **D.kw(use)))
                 if got is not None:
-                    check("fwd/" + name, case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol)
+                    check("fwd/" + name, case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol, src=got)
             if run_w:
                 # nothing is kept for a conv whose forward is direct (the residual is no part of the weight gradient's descriptor, so that
                 # reason is asked with it) ...
@@ -336,14 +387,14 @@ def ulp_err(y, y64, scale):
     return float(((y.detach().double().cpu() - y64).abs()[ok] / scale[ok]).max()) if bool(ok.any()) else 0.0
 
 
-def check_f16(tag, case, e16, e32):
+def check_f16(tag, case, e16, e32, src=None):
     """tests/test_gpu_f16_math.py's criterion: the error against float64 ON THE MODE'S ROUNDED OPERANDS is fp32 accumulation only: within
     max(2 x the fp32 kernel's on the same operands, 8 ulp) and below 32 ulp of sum |q(x)||q(w)|"""
-    global ran
-    ran += 1
-    cov[cur[0]]["comparisons"] += 1
+    count(tag)
     if not (e16 <= max(2.0 * e32, 8 * EPS)) or not (e16 <= 32 * EPS):
         fails.append((tag, case, "f16 %.1f ulp, f32 on the same operands %.1f ulp of sum|q(x)||q(w)|" % (e16 / EPS, e32 / EPS)))
+    if src is not None:
+        check_amax(tag, case, src)
 
 
 def stratum_f16(n, seed):
@@ -380,10 +431,10 @@ def stratum_f16(n, seed):
                 y64, s64 = y64 + rs, s64 + rs.abs()
             if use["relu"]:
                 y64 = torch.relu(y64)
-            y16 = attempt("fwd/f16", case, lambda: ops.conv_forward(D.xg, D.wg, s, p, math=m, **D.kw(use)))
+            y16 = attempt("fwd/f16", case, lambda: ops.conv_forward(D.xg, D.wg, s, p, math=m, emit_amax=True, **D.kw(use)))
             if y16 is not None:
                 y32 = ops.conv_forward(qx.float().cuda(), qw.float().cuda(), s, p, math=f32, **D.kw(use))
-                check_f16("fwd/f16", case + used(use), ulp_err(y16, y64, s64), ulp_err(y32, y64, s64))
+                check_f16("fwd/f16", case + used(use), ulp_err(y16, y64, s64), ulp_err(y32, y64, s64), src=y16)
         # weight gradient: any Cin % 4 == 0 stays in the mode
         if wm != m:
             misrouted("weight gradient of %s runs in %s" % (case, MATH_NAME[wm]))
@@ -411,11 +462,11 @@ def stratum_f16(n, seed):
                         z64, zs = torch.zeros(B, H, W, Cin, dtype=torch.float64), torch.zeros(B, H, W, Cin, dtype=torch.float64)
                         z64[:, ::s, ::s], zs[:, ::s, ::s] = y64, s64
                         y64, s64 = z64, zs
-                    check_f16("dgrad/f16", case, ulp_err(g16, y64, s64), ulp_err(g32, y64, s64))
+                    check_f16("dgrad/f16", case, ulp_err(g16, y64, s64), ulp_err(g32, y64, s64), src=g16)
             elif rm == f32 and step("dgrad", "f16->f32", dwino):
                 dx = attempt("dgrad/f16->f32", case, lambda: run_dgrad(D, case, m))
                 if dx is not None:
-                    check("dgrad/f16->f32", case, dx.permute(0, 3, 1, 2), D.x.grad, 2e-4)
+                    check("dgrad/f16->f32", case, dx.permute(0, 3, 1, 2), D.x.grad, 2e-4, src=dx)
         if (ci + 1) % 10 == 0:
             print("f16: %d cases, %d comparisons so far, %d failures" % (ci + 1, ran, len(fails)), flush=True)
 
@@ -446,9 +497,9 @@ def stratum_bf16_fallback(n, seed):
             misrouted("%s runs in %s / %s" % (case, MATH_NAME[rm], MATH_NAME[wm]))
             continue
         if step("fwd", "bf16->f32", fw):
-            got = attempt("fwd/bf16->f32", case, lambda: ops.conv_forward(D.xg, D.wg, s, p, math=m, **D.kw(use)))
+            got = attempt("fwd/bf16->f32", case, lambda: ops.conv_forward(D.xg, D.wg, s, p, math=m, emit_amax=True, **D.kw(use)))
             if got is not None:
-                check("fwd/bf16->f32", case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol)
+                check("fwd/bf16->f32", case + used(use), got.permute(0, 3, 1, 2), D.epilogue(use), tol, src=got)
         if step("wgrad", "bf16->f32", route_fwd(case, m)[2]):
             dw = torch.zeros_like(D.wg)
             if attempt("wgrad/bf16->f32", case, lambda: (ops.conv_wgrad(D.xg, D.gyg, dw, s, p, scale=D.scale.cuda(), math=m), True)[1]):
@@ -460,7 +511,7 @@ def stratum_bf16_fallback(n, seed):
             elif step("dgrad", "bf16->f32", dwino):
                 dx = attempt("dgrad/bf16->f32", case, lambda: run_dgrad(D, case, m))
                 if dx is not None:
-                    check("dgrad/bf16->f32", case, dx.permute(0, 3, 1, 2), D.x.grad, tol * 2)
+                    check("dgrad/bf16->f32", case, dx.permute(0, 3, 1, 2), D.x.grad, tol * 2, src=dx)
         if (ci + 1) % 10 == 0:
             print("bf16_fallback: %d cases, %d comparisons so far, %d failures" % (ci + 1, ran, len(fails)), flush=True)
 
@@ -497,14 +548,14 @@ def stratum_tail64(n, seed):
         if not ops.bottleneck_tail64_applies(o1, w2, w3, m):
             misrouted("bottleneck_tail64_applies refuses %s" % (case,))
             continue
-        o2 = attempt("tail64/two calls", case, lambda: ops.conv_forward(o1, w2, 1, 1, scale=s2, bias=b2, relu=True, math=m, w_version=ver))
-        want = attempt("tail64/two calls", case, lambda: ops.conv_forward(o2, w3, 1, 0, scale=s3, bias=b3, residual=idt, relu=True, math=m, w_version=ver))
+        o2 = attempt("tail64/two calls", case, lambda: ops.conv_forward(o1, w2, 1, 1, scale=s2, bias=b2, relu=True, math=m, w_version=ver, emit_amax=True))
+        want = attempt("tail64/two calls", case, lambda: ops.conv_forward(o2, w3, 1, 0, scale=s3, bias=b3, residual=idt, relu=True, math=m, w_version=ver, emit_amax=True))
         got = attempt("tail64/fused", case, lambda: ops.bottleneck_tail64(o1, w2, w3, s2, b2, s3, b3, idt, ver, ver))
         if want is None or got is None:
             continue
         check("tail64/fused bit-equal to two calls", case, got, want.cpu().double(), 0.0)
         check("tail64/fused", case, got.permute(0, 3, 1, 2), r3, 1e-4)
-        check("tail64/two calls", case, want.permute(0, 3, 1, 2), r3, 1e-4)
+        check("tail64/two calls", case, want.permute(0, 3, 1, 2), r3, 1e-4, src=want)
         if (ci + 1) % 10 == 0:
             print("tail64: %d cases, %d comparisons so far, %d failures" % (ci + 1, ran, len(fails)), flush=True)
 
@@ -538,7 +589,7 @@ def stratum_dgrad_fused(n, seed):
             kw = dict(mask=nhwc(D.xmask) if kind.get("mask") else None, residual=nhwc(D.xres) if kind.get("residual") else None)
             dx = attempt("dgrad/" + name, case, lambda: run_dgrad(D, case, m, **kw))
             if dx is not None:
-                check("dgrad/" + name, case + (feat[0],), dx.permute(0, 3, 1, 2), want, tol * 2)
+                check("dgrad/" + name, case + (feat[0],), dx.permute(0, 3, 1, 2), want, tol * 2, src=dx)
         if (ci + 1) % 10 == 0:
             print("dgrad_fused: %d cases, %d comparisons so far, %d failures" % (ci + 1, ran, len(fails)), flush=True)
 
@@ -547,7 +598,7 @@ RUN = dict(any=stratum_any, wino=stratum_wino, wino_wgrad_only=stratum_wino_wgra
            tail64=stratum_tail64, dgrad_fused=stratum_dgrad_fused)
 for st in strata:
     cur[0] = st
-    cov[st] = dict(cases=0, comparisons=0, misrouted=0, routes={}, features={}, reasons={})
+    cov[st] = dict(cases=0, comparisons=0, misrouted=0, routes={}, features={}, reasons={}, fwd_dgrad={}, amax_checks={})
     RUN[st](a.cases if st == "any" else a.per_stratum, a.seed)
 cur[0] = None
 
@@ -560,6 +611,8 @@ for st in strata:
         print("    %-10s %s" % (mode, "  ".join("%s %d" % kv for kv in sorted(c["routes"][mode].items()))))
     for reason in sorted(c["reasons"]):
         print("    off the forward route by %-18s %s" % (reason, "  ".join("%s %d" % kv for kv in sorted(c["reasons"][reason].items()))))
+    if c["amax_checks"]:
+        print("    amax words equal to max |result|: %s" % "  ".join("%s %d" % kv for kv in sorted(c["amax_checks"].items())))
 print("COVERAGE " + json.dumps(cov, sort_keys=True))
 print("refused (RuntimeError) configurations:")
 for (tag, msg), cs in sorted(refused.items()):

@@ -184,6 +184,8 @@ _SIGS = {
     "abr_coco_box_iou": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
     "abr_coco_mask_iou": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "abr_coco_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "abr_coco_match_ig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "abr_coco_oks": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
     "abr_kp_select_targets": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "abr_kp_deconv_fold": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "abr_kp_deconv_unfold": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

@@ -60,13 +60,14 @@ __global__ __launch_bounds__(256) void coco_mask_iou_kernel(const int32_t* __res
     iou[e] = i > 0 ? (double)i / (double)u : 0.0;     // (i > 0 implies u >= i > 0)
 }
 
-// One wave per group.  Lane p < A * T owns (area range p / T, threshold p % T).  Groups with more than kMaxGt ground truths are counted in
+// One wave per group.  Lane p < A * T owns (area range p / T, threshold p % T).  gt_ignore is the protocol's `ignore` flag of a ground truth
+// (boxes and masks: its crowd flag; keypoints: crowd or no labelled keypoint); gt_crowd alone lets a matched ground truth match again.  Groups with more than kMaxGt ground truths are counted in
 // *n_over and left untouched: the caller scores them on the host.
 __global__ __launch_bounds__(64) void coco_match_kernel(const double* __restrict__ iou, const int64_t* __restrict__ iou_off,
                                                         const int64_t* __restrict__ det_off, const int64_t* __restrict__ gt_off,
                                                         const double* __restrict__ det_area, const double* __restrict__ gt_area,
-                                                        const uint8_t* __restrict__ gt_crowd, const double* __restrict__ area_rng, int A,
-                                                        const double* __restrict__ thrs, int T, int64_t d_total, int64_t g_total,
+                                                        const uint8_t* __restrict__ gt_crowd, const uint8_t* __restrict__ gt_ignore,
+                                                        const double* __restrict__ area_rng, int A, const double* __restrict__ thrs, int T, int64_t d_total, int64_t g_total,
                                                         int32_t* __restrict__ dt_gt, uint8_t* __restrict__ dt_ig, uint8_t* __restrict__ gt_ig,
                                                         int32_t* __restrict__ n_over) {
     __shared__ double s_row[kMaxGt];                       // the current detection's IoUs, shared by all lanes
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(64) void coco_match_kernel(const double* __restrict
         for (int g = 0; g < G; g++) {
             const double a = gt_area[g0 + g];
             const bool crowd = gt_crowd[g0 + g] != 0;
-            const bool ignored = crowd || a < lo || a > hi;
+            const bool ignored = gt_ignore[g0 + g] != 0 || a < lo || a > hi;
             if (ignored) ig[g >> 6] |= 1ull << (g & 63); else s_order[lane][k++] = (uint8_t)g;
             if (crowd) cr[g >> 6] |= 1ull << (g & 63);
             gt_ig[(int64_t)lane * g_total + g0 + g] = ignored ? 1 : 0;
@@ -170,18 +171,27 @@ extern "C" int abr_coco_mask_iou(const int32_t* inter, const int32_t* area_p, co
     return ABR_OK;
 }
 
-extern "C" int abr_coco_match(const double* iou, const int64_t* iou_off, const int64_t* det_off, const int64_t* gt_off, const double* det_area,
-                              const double* gt_area, const uint8_t* gt_crowd, int n_groups, int64_t d_total, int64_t g_total,
-                              const double* area_rng, int A, const double* thrs, int T, int32_t* dt_gt, uint8_t* dt_ig, uint8_t* gt_ig,
-                              int32_t* n_over, void* stream) {
+extern "C" int abr_coco_match_ig(const double* iou, const int64_t* iou_off, const int64_t* det_off, const int64_t* gt_off, const double* det_area,
+                                 const double* gt_area, const uint8_t* gt_crowd, const uint8_t* gt_ignore, int n_groups, int64_t d_total,
+                                 int64_t g_total, const double* area_rng, int A, const double* thrs, int T, int32_t* dt_gt, uint8_t* dt_ig,
+                                 uint8_t* gt_ig, int32_t* n_over, void* stream) {
     ABR_REQUIRE(n_groups >= 0 && d_total >= 0 && g_total >= 0, "coco_match: bad args (n_groups, d_total, g_total >= 0)");
     ABR_REQUIRE(A >= 1 && A <= kMaxAreas && T >= 1 && A * T <= 64, "coco_match: bad args (1 <= A <= 8, T >= 1, A * T <= 64: one lane per pair)");
     if (n_groups == 0) return ABR_OK;
     ABR_REQUIRE(iou_off && det_off && gt_off && area_rng && thrs && n_over, "coco_match: null pointer");
-    ABR_REQUIRE((d_total == 0 || (det_area && dt_gt && dt_ig)) && (g_total == 0 || (gt_area && gt_crowd && gt_ig)) &&
+    ABR_REQUIRE((d_total == 0 || (det_area && dt_gt && dt_ig)) && (g_total == 0 || (gt_area && gt_crowd && gt_ignore && gt_ig)) &&
                     (d_total == 0 || g_total == 0 || iou), "coco_match: null pointer");
-    coco_match_kernel<<<n_groups, 64, 0, abr::as_stream(stream)>>>(iou, iou_off, det_off, gt_off, det_area, gt_area, gt_crowd, area_rng, A, thrs, T,
-                                                                   d_total, g_total, dt_gt, dt_ig, gt_ig, n_over);
+    coco_match_kernel<<<n_groups, 64, 0, abr::as_stream(stream)>>>(iou, iou_off, det_off, gt_off, det_area, gt_area, gt_crowd, gt_ignore, area_rng, A,
+                                                                   thrs, T, d_total, g_total, dt_gt, dt_ig, gt_ig, n_over);
     ABR_CHECK_LAUNCH("coco_match");
     return ABR_OK;
+}
+
+// boxes and masks: a ground truth is ignored exactly when it is a crowd
+extern "C" int abr_coco_match(const double* iou, const int64_t* iou_off, const int64_t* det_off, const int64_t* gt_off, const double* det_area,
+                              const double* gt_area, const uint8_t* gt_crowd, int n_groups, int64_t d_total, int64_t g_total,
+                              const double* area_rng, int A, const double* thrs, int T, int32_t* dt_gt, uint8_t* dt_ig, uint8_t* gt_ig,
+                              int32_t* n_over, void* stream) {
+    return abr_coco_match_ig(iou, iou_off, det_off, gt_off, det_area, gt_area, gt_crowd, gt_crowd, n_groups, d_total, g_total, area_rng, A, thrs, T,
+                             dt_gt, dt_ig, gt_ig, n_over, stream);
 }

@@ -1,13 +1,14 @@
-"""COCO box and mask AP / AR (mirror of maskrcnn_benchmark/data/datasets/evaluation/coco/coco_eval.py: do_coco_evaluation, the
+"""COCO box, mask and keypoint AP / AR (mirror of maskrcnn_benchmark/data/datasets/evaluation/coco/coco_eval.py: do_coco_evaluation, the
 prepare_for_coco_* functions, COCOResults, check_expected_results).  The reference hands the scoring to pycocotools' COCOeval, a host loop
 over every image, category, area range and IoU threshold.  Here the protocol is restated and split in two:
   * the per-image work runs on the device for the whole dataset at once: pairwise IoU with crowd semantics (ops.coco_box_iou; for masks
-    ops.mask_pair_counts + ops.coco_mask_iou over run-length results decoded by ops.rle_decode) and the greedy matching for all area
-    ranges and thresholds (ops.coco_match);
-  * the short accumulation and the 12 summary numbers stay on the host in float64 (coco_eval_host.py).
+    ops.mask_pair_counts + ops.coco_mask_iou over run-length results decoded by ops.rle_decode; for keypoints the object keypoint similarity,
+    ops.coco_oks) and the greedy matching for all area ranges and thresholds (ops.coco_match);
+  * the short accumulation and the summary numbers (12; 10 for keypoints) stay on the host in float64 (coco_eval_host.py).
 device="cpu" scores everything with the host restatement instead: the yardstick of the tests, never chosen silently.
-Not carried: box_only (proposal recall) and keypoint scoring (OKS): the keypoint head (MODEL.KEYPOINT_ON) puts a "keypoints" field on the
-detections, and do_coco_evaluation keeps raising for the "keypoints" iou type."""
+"keypoints" scores the "keypoints" field the keypoint head (MODEL.KEYPOINT_ON) puts on the detections, under the keypoint protocol's
+own parameters: at most 20 detections per image, the area ranges all / medium / large, ground truths without a labelled keypoint ignored.
+Not carried: box_only (proposal recall)."""
 import json
 import logging
 import os
@@ -24,9 +25,9 @@ def do_coco_evaluation(dataset, predictions, box_only, output_folder, iou_types,
     logger = logging.getLogger("maskrcnn_benchmark.inference")
     if box_only:
         raise NotImplementedError("box_only (proposal recall of an RPN-only model) is not carried; evaluate with iou_types=('bbox',)")
-    unknown = [t for t in iou_types if t not in ("bbox", "segm")]
+    unknown = [t for t in iou_types if t not in ("bbox", "segm", "keypoints")]
     if unknown:
-        raise NotImplementedError("COCO evaluation of {} is not carried (bbox and segm are)".format(unknown))
+        raise NotImplementedError("COCO evaluation of {} is not carried (bbox, segm and keypoints are)".format(unknown))
     logger.info("Preparing results for COCO format")
     coco_results = {}
     if "bbox" in iou_types:
@@ -35,6 +36,9 @@ def do_coco_evaluation(dataset, predictions, box_only, output_folder, iou_types,
     if "segm" in iou_types:
         logger.info("Preparing segm results")
         coco_results["segm"] = prepare_for_coco_segmentation(predictions, dataset)       # (encoded on the device whatever `device` scores)
+    if "keypoints" in iou_types:
+        logger.info("Preparing keypoints results")
+        coco_results["keypoints"] = prepare_for_coco_keypoint(predictions, dataset)
     results = COCOResults(*iou_types)
     logger.info("Evaluating predictions")
     for iou_type in iou_types:
@@ -67,9 +71,31 @@ def prepare_for_coco_detection(predictions, dataset):
     return coco_results
 
 
+def prepare_for_coco_keypoint(predictions, dataset):
+    """predictions (BoxLists with a "keypoints" field, in dataset order) -> [{"image_id", "category_id", "keypoints": [x, y, v] * K at the
+    original image size, "score": the box score}]"""
+    coco_results = []
+    for image_id, prediction in enumerate(predictions):
+        original_id = dataset.id_to_img_map[image_id]
+        if len(prediction) == 0:
+            continue
+        if not prediction.has_field("keypoints"):
+            raise ValueError('image {}: the prediction has no "keypoints" field (its fields: {}); keypoint scoring needs a model with '
+                             'MODEL.KEYPOINT_ON'.format(original_id, prediction.fields()))
+        info = dataset.get_img_info(image_id)
+        size = (info["width"], info["height"])
+        prediction = prediction.copy_with_fields(["labels", "scores", "keypoints"]).resize(size)
+        scores = prediction.get_field("scores").tolist()
+        labels = [dataset.contiguous_category_id_to_json_id[i] for i in prediction.get_field("labels").tolist()]
+        keypoints = prediction.get_field("keypoints").resize(size)        # (BoxList.resize has resized the field: a ratio of 1, as in the reference)
+        keypoints = keypoints.keypoints.reshape(keypoints.keypoints.shape[0], -1).tolist()
+        coco_results.extend({"image_id": original_id, "category_id": labels[k], "keypoints": kp, "score": scores[k]} for k, kp in enumerate(keypoints))
+    return coco_results
+
+
 class COCOEvalResult(object):
-    """what one iou_type's evaluation leaves: stats (the 12 numbers of COCOeval.summarize, coco_eval_host.STAT_NAMES), the precision
-    [T,R,K,A,M] and recall [T,K,A,M] tables, and how the groups were scored"""
+    """what one iou_type's evaluation leaves: stats (the numbers of COCOeval.summarize: 12 in coco_eval_host.STAT_NAMES' order, for
+    keypoints 10 in KP_STAT_NAMES'), the precision [T,R,K,A,M] and recall [T,K,A,M] tables, and how the groups were scored"""
 
     def __init__(self, iou_type, stats, acc, n_groups, n_fallback):
         self.iou_type, self.stats, self.precision, self.recall = iou_type, stats, acc["precision"], acc["recall"]
@@ -80,7 +106,8 @@ class COCOEvalResult(object):
 
 
 class COCOResults(object):
-    METRICS = {"bbox": ["AP", "AP50", "AP75", "APs", "APm", "APl"], "segm": ["AP", "AP50", "AP75", "APs", "APm", "APl"]}
+    METRICS = {"bbox": ["AP", "AP50", "AP75", "APs", "APm", "APl"], "segm": ["AP", "AP50", "AP75", "APs", "APm", "APl"],
+               "keypoints": ["AP", "AP50", "AP75", "APm", "APl"]}
 
     def __init__(self, *iou_types):
         assert all(t in COCOResults.METRICS for t in iou_types), iou_types
@@ -143,10 +170,22 @@ def _image_mask_iou(dets, anns, size, masks_of, device):
     return H.mask_iou_from_counts(inter, area_p, gm.sum(1), crowd), area_p
 
 
-def build_groups(dataset, coco_results, iou_type, device):
+def _keypoint_rows(items, K, what):
+    """the "keypoints" lists of results or annotations -> float64 [n,K,3]"""
+    for it in items:
+        if len(it.get("keypoints", ())) != 3 * K:
+            raise ValueError('{} of image {}: "keypoints" holds {} numbers, {} keypoints need {}'.format(
+                what, it["image_id"], len(it.get("keypoints", ())), K, 3 * K))
+    return np.array([it["keypoints"] for it in items], np.float64).reshape(-1, K, 3)
+
+
+def build_groups(dataset, coco_results, iou_type, device, n_keypoints=None):
     """-> (groups, cat_ids).  A group: {"k": category index, "scores" (rank order), "det_area", "gt_area", "gt_crowd", and "det" / "gt"
-    xywh boxes (bbox) or "iou" float64 [D,G] (segm)}, images in dataset order, categories ascending inside an image"""
+    xywh boxes (bbox), "iou" float64 [D,G] (segm) or "det_kp" / "gt_kp" [.,K,3], "gt_box" and "gt_ignore" (keypoints, K = n_keypoints;
+    ranked detections cut at 20; gt_ignore = crowd or num_keypoints == 0, the annotation's own count or else its v > 0)}, images in
+    dataset order, categories ascending inside an image"""
     device = torch.device(device)
+    max_det = H.KP_MAX_DETS[-1] if iou_type == "keypoints" else H.MAX_DETS[-1]
     cat_ids = sorted(dataset.json_category_id_to_contiguous_id)
     cat_index = {c: k for k, c in enumerate(cat_ids)}
     by_image = {}
@@ -171,7 +210,7 @@ def build_groups(dataset, coco_results, iou_type, device):
                 raise ValueError("category id {} is not in the annotation file".format(c))
             rows = np.array([i for i, d in enumerate(dets) if d["category_id"] == c], np.int64)
             cols = np.array([j for j, a in enumerate(anns) if a["category_id"] == c], np.int64)
-            rows = rows[H.rank_detections([dets[i]["score"] for i in rows])]
+            rows = rows[H.rank_detections([dets[i]["score"] for i in rows], max_det)]
             g = {"k": cat_index[c], "scores": np.array([dets[i]["score"] for i in rows], np.float64),
                  "gt_area": np.array([anns[j]["area"] for j in cols], np.float64),
                  "gt_crowd": np.array([bool(anns[j].get("iscrowd", 0)) for j in cols], bool)}
@@ -179,6 +218,15 @@ def build_groups(dataset, coco_results, iou_type, device):
                 g["det"] = np.array([dets[i]["bbox"] for i in rows], np.float64).reshape(-1, 4)
                 g["gt"] = np.array([anns[j]["bbox"] for j in cols], np.float64).reshape(-1, 4)
                 g["det_area"] = g["det"][:, 2] * g["det"][:, 3]
+            elif iou_type == "keypoints":
+                gts = [anns[j] for j in cols]
+                g["det_kp"] = _keypoint_rows([dets[i] for i in rows], n_keypoints, "a result")
+                g["gt_kp"] = _keypoint_rows(gts, n_keypoints, "an annotation")
+                g["gt_box"] = np.array([a["bbox"] for a in gts], np.float64).reshape(-1, 4)
+                g["det_area"] = H.keypoint_det_area(g["det_kp"])
+                labelled = np.array([a["num_keypoints"] if "num_keypoints" in a else np.count_nonzero(kp[:, 2] > 0)
+                                     for a, kp in zip(gts, g["gt_kp"])], np.int64)
+                g["gt_ignore"] = g["gt_crowd"] | (labelled == 0)
             else:
                 g["iou"] = iou_img[np.ix_(rows, cols)] if len(rows) else np.zeros((0, len(cols)))
                 g["det_area"] = area_img[rows].astype(np.float64) if len(rows) else np.zeros((0,))
@@ -186,14 +234,20 @@ def build_groups(dataset, coco_results, iou_type, device):
     return groups, cat_ids
 
 
-def score_groups(groups, iou_type, device, area_rng=H.AREA_RNG, thrs=H.IOU_THRS):
-    """-> (per-group evaluateImg results, number of groups the match kernel left to the host)"""
+def score_groups(groups, iou_type, device, area_rng=None, thrs=H.IOU_THRS, sigmas=None):
+    """-> (per-group evaluateImg results, number of groups the match kernel left to the host).  area_rng None: the protocol's own
+    (H.KP_AREA_RNG for keypoints, else H.AREA_RNG); sigmas [K]: the per-keypoint constants of OKS (keypoints only)"""
     from ..... import ops
     device = torch.device(device)
+    kp = iou_type == "keypoints"
+    if area_rng is None:
+        area_rng = H.KP_AREA_RNG if kp else H.AREA_RNG
     if device.type != "cuda":
         for g in groups:
             if iou_type == "bbox":
                 g["iou"] = H.box_iou(g["det"], g["gt"], g["gt_crowd"])
+            elif kp:
+                g["iou"] = H.oks(g["det_kp"], g["gt_kp"], g["gt_box"], g["gt_area"], sigmas)
         return H.score_groups_host(groups, area_rng, thrs), 0
     if not groups:
         return [], 0
@@ -203,20 +257,49 @@ def score_groups(groups, iou_type, device, area_rng=H.AREA_RNG, thrs=H.IOU_THRS)
     crowd = cat("gt_crowd", (-1,))
     if iou_type == "bbox":
         iou, _ = ops.coco_box_iou(cat("det", (-1, 4)), cat("gt", (-1, 4)), crowd, dc, gc, device)
+    elif kp:
+        K = len(sigmas)
+        iou, _ = ops.coco_oks(cat("det_kp", (-1, K, 3)), cat("gt_kp", (-1, K, 3)), cat("gt_box", (-1, 4)), cat("gt_area", (-1,)), sigmas, dc, gc, device)
     else:
         iou = cat("iou", (-1,))
-    out = ops.coco_match(iou, dc, gc, cat("det_area", (-1,)), cat("gt_area", (-1,)), crowd, area_rng, thrs, device)
+    out = ops.coco_match(iou, dc, gc, cat("det_area", (-1,)), cat("gt_area", (-1,)), crowd, area_rng, thrs, device,
+                         gt_ignore=cat("gt_ignore", (-1,)) if kp else None)
     d_off, g_off = np.concatenate(([0], np.cumsum(dc))), np.concatenate(([0], np.cumsum(gc)))
     res = [{"dt_gt": out["dt_gt"][:, :, d_off[i]: d_off[i + 1]], "dt_ig": out["dt_ig"][:, :, d_off[i]: d_off[i + 1]],
             "gt_ig": out["gt_ig"][:, g_off[i]: g_off[i + 1]]} for i in range(len(groups))]
     return res, out["n_fallback"]
 
 
-def evaluate_predictions_on_coco(dataset, coco_results, iou_type="bbox", device="cuda"):
-    groups, cat_ids = build_groups(dataset, coco_results, iou_type, device)
-    scored, n_fallback = score_groups(groups, iou_type, device)
+def _keypoint_sigmas(dataset, coco_results, kpt_oks_sigmas):
+    """the OKS constants, one per keypoint: COCO's 17 person-keypoint sigmas unless given; K is read off the first result or annotation"""
+    first = next((r for r in coco_results if "keypoints" in r), None)
+    if first is None:
+        first = next((a for index in range(len(dataset)) for a in dataset.get_annotations(index) if "keypoints" in a), None)
+    K = len(first["keypoints"]) // 3 if first is not None else len(H.KPT_OKS_SIGMAS)
+    if kpt_oks_sigmas is None:
+        if K != len(H.KPT_OKS_SIGMAS):
+            raise ValueError("keypoint scoring: {} keypoints per instance and no kpt_oks_sigmas given; the default sigmas are those of COCO's "
+                             "{} person keypoints".format(K, len(H.KPT_OKS_SIGMAS)))
+        return H.KPT_OKS_SIGMAS
+    sigmas = np.asarray(kpt_oks_sigmas, np.float64).reshape(-1)
+    if len(sigmas) != K:
+        raise ValueError("keypoint scoring: {} kpt_oks_sigmas for {} keypoints per instance".format(len(sigmas), K))
+    return sigmas
+
+
+def evaluate_predictions_on_coco(dataset, coco_results, iou_type="bbox", device="cuda", kpt_oks_sigmas=None):
+    if iou_type != "keypoints":
+        groups, cat_ids = build_groups(dataset, coco_results, iou_type, device)
+        scored, n_fallback = score_groups(groups, iou_type, device)
+    else:
+        sigmas = _keypoint_sigmas(dataset, coco_results, kpt_oks_sigmas)
+        groups, cat_ids = build_groups(dataset, coco_results, iou_type, device, n_keypoints=len(sigmas))
+        scored, n_fallback = score_groups(groups, iou_type, device, sigmas=sigmas)
     cells = {}
     for g, r in zip(groups, scored):
         cells.setdefault(g["k"], []).append(dict(r, scores=g["scores"]))
+    if iou_type == "keypoints":
+        acc = H.accumulate(cells, len(cat_ids), n_areas=len(H.KP_AREA_RNG), max_dets=H.KP_MAX_DETS)
+        return COCOEvalResult(iou_type, H.summarize_keypoints(acc), acc, len(groups), n_fallback)
     acc = H.accumulate(cells, len(cat_ids))
     return COCOEvalResult(iou_type, H.summarize(acc), acc, len(groups), n_fallback)

@@ -1,7 +1,7 @@
 """The COCO detection protocol on the host, in float64 numpy: what pycocotools' COCOeval computes -- bbIou / rleIou, evaluateImg,
-accumulate, summarize -- restated from the protocol.  pycocotools cannot be installed where this project is built, so
-compatibility rests on this restatement and its answers worked out by hand (tests/test_coco_eval_host.py), as it does for run-length
-masks and polygons.  Three users: the groups the match kernel leaves to the host (more ground truths than ops.COCO_MATCH_MAX_GT), the
+accumulate, summarize, and for the "keypoints" iou type computeOks with the keypoint parameters -- restated from the protocol
+(DESIGN.md §4).  pycocotools cannot be installed where this project is built, so compatibility rests on this restatement and its
+answers worked out by hand (tests/test_coco_eval_host.py, tests/test_coco_keypoints_host.py), as it does for run-length masks and polygons.  Three users: the groups the match kernel leaves to the host (more ground truths than ops.COCO_MATCH_MAX_GT), the
 accumulation behind both routes, and the tests of csrc/coco_eval.hip.
 
 A GROUP is one (image, category) pair: its detections in rank order (score descending, stable, the first maxDets[-1]) and its ground
@@ -17,6 +17,12 @@ MAX_DETS = (1, 10, 100)
 AREA_RNG = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], np.float64)
 AREA_LABELS = ("all", "small", "medium", "large")
 STAT_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
+# the keypoint protocol's own parameters (COCOeval's Params.setKpParams): one maxDets, no "small" range, a sigma per person keypoint
+KP_MAX_DETS = (20,)
+KP_AREA_RNG = np.array([[0 ** 2, 1e5 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], np.float64)
+KP_AREA_LABELS = ("all", "medium", "large")
+KP_STAT_NAMES = ("AP", "AP50", "AP75", "APm", "APl", "AR", "AR50", "AR75", "ARm", "ARl")
+KPT_OKS_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
 
 
 def rank_detections(scores, max_det=MAX_DETS[-1]):
@@ -52,11 +58,63 @@ def mask_iou_from_counts(inter, area_p, area_t, gt_crowd):
     return out
 
 
-def evaluate_img(iou, det_area, gt_area, gt_crowd, area_rng=AREA_RNG, thrs=IOU_THRS):
+def keypoint_det_area(det_kp):
+    """loadRes' area of a keypoint result: det_kp [D,K,3] -> [D], (max x - min x) * (max y - min y) over all K points, whatever v is"""
+    kp = np.asarray(det_kp, np.float64)
+    if kp.size == 0:
+        return np.zeros(len(kp), np.float64)
+    kp = kp.reshape(len(kp), -1, 3)
+    x, y = kp[:, :, 0], kp[:, :, 1]
+    return (x.max(1) - x.min(1)) * (y.max(1) - y.min(1))
+
+
+def oks(det_kp, gt_kp, gt_box, gt_area, sigmas=KPT_OKS_SIGMAS):
+    """computeOks: det_kp [D,K,3], gt_kp [G,K,3] (x, y, v), gt_box [G,4] xywh, gt_area [G], sigmas [K] -> float64 [D,G].  With k1 = the
+    ground truth's keypoints of v > 0: the mean of exp(-e_k) over them, e_k = (dx_k^2 + dy_k^2) / (2 sigma_k)^2 / (area + 2^-52) / 2; with
+    k1 == 0 the mean over all K, dx and dy being the distances to the box doubled about itself.  Crowds get no special value.
+    The sum runs serially in keypoint order (np.sum, which pycocotools uses, adds pairwise and can differ in the last bits)."""
+    var = (np.asarray(sigmas, np.float64).reshape(-1) * 2) ** 2
+    K = len(var)
+    det_kp, gt_kp = np.asarray(det_kp, np.float64).reshape(-1, K, 3), np.asarray(gt_kp, np.float64).reshape(-1, K, 3)
+    gt_box, gt_area = np.asarray(gt_box, np.float64).reshape(-1, 4), np.asarray(gt_area, np.float64).reshape(-1)
+    G = gt_kp.shape[0]
+    if K < 1 or len(gt_box) != G or len(gt_area) != G:
+        raise ValueError("oks: {} sigmas, {} boxes and {} areas for {} ground truths".format(K, len(gt_box), len(gt_area), G))
+    D = det_kp.shape[0]
+    out = np.zeros((D, G), np.float64)
+    z = np.zeros((D, K))
+    xd, yd = det_kp[:, :, 0], det_kp[:, :, 1]
+    for j in range(G):
+        xg, yg, vg = gt_kp[j, :, 0], gt_kp[j, :, 1], gt_kp[j, :, 2]
+        k1 = np.count_nonzero(vg > 0)
+        if k1 > 0:
+            dx, dy = xd - xg, yd - yg
+        else:
+            bb = gt_box[j]
+            x0, x1, y0, y1 = bb[0] - bb[2], bb[0] + bb[2] * 2, bb[1] - bb[3], bb[1] + bb[3] * 2
+            dx = np.maximum(z, x0 - xd) + np.maximum(z, xd - x1)
+            dy = np.maximum(z, y0 - yd) + np.maximum(z, yd - y1)
+        with np.errstate(over="ignore", divide="ignore"):
+            e = (dx * dx + dy * dy) / var / (gt_area[j] + np.spacing(1)) / 2
+        if k1 > 0:
+            e = e[:, vg > 0]
+        t = np.exp(-e)
+        acc = np.zeros(D, np.float64)
+        for k in range(t.shape[1]):
+            acc = acc + t[:, k]
+        out[:, j] = acc / t.shape[1]
+    return out
+
+
+def evaluate_img(iou, det_area, gt_area, gt_crowd, area_rng=AREA_RNG, thrs=IOU_THRS, gt_ignore=None):
     """evaluateImg of one group for every area range and IoU threshold.  iou float64 [D,G] (detections in rank order, ground truths in
-    file order) -> {"dt_gt": int32 [A,T,D] matched ground-truth row or -1, "dt_ig": bool [A,T,D], "gt_ig": bool [A,G]}"""
+    file order) -> {"dt_gt": int32 [A,T,D] matched ground-truth row or -1, "dt_ig": bool [A,T,D], "gt_ig": bool [A,G]}.
+    gt_ignore [G] is the protocol's `ignore` flag of a ground truth: None = its crowd flag (boxes, masks); keypoints pass crowd or
+    num_keypoints == 0.  A ground truth is ignored when the flag is set or its area is outside the range; the crowd flag alone lets a
+    matched ground truth be matched again."""
     det_area, gt_area = np.asarray(det_area, np.float64).reshape(-1), np.asarray(gt_area, np.float64).reshape(-1)
     crowd = np.asarray(gt_crowd).astype(bool).reshape(-1)
+    flag = crowd if gt_ignore is None else np.asarray(gt_ignore).astype(bool).reshape(-1)
     area_rng, thrs = np.asarray(area_rng, np.float64).reshape(-1, 2), np.asarray(thrs, np.float64).reshape(-1)
     D, G, A, T = len(det_area), len(gt_area), len(area_rng), len(thrs)
     iou = np.asarray(iou, np.float64).reshape(D, G)
@@ -65,7 +123,7 @@ def evaluate_img(iou, det_area, gt_area, gt_crowd, area_rng=AREA_RNG, thrs=IOU_T
     gt_ig = np.zeros((A, G), bool)
     rows = iou.tolist()
     for a, (lo, hi) in enumerate(area_rng):
-        ig = crowd | (gt_area < lo) | (gt_area > hi)
+        ig = flag | (gt_area < lo) | (gt_area > hi)
         gt_ig[a] = ig
         order = np.argsort(ig, kind="mergesort").tolist()       # the non-ignored first, stable
         ig_l, crowd_l = ig.tolist(), crowd.tolist()
@@ -151,6 +209,21 @@ def summarize(acc, thrs=IOU_THRS, max_dets=MAX_DETS):
     return np.array([ap(), ap(thr=.5), ap(thr=.75), ap(1), ap(2), ap(3), ar(m=0), ar(m=1), ar(m=2), ar(1), ar(2), ar(3)], np.float64)
 
 
+def summarize_keypoints(acc, thrs=IOU_THRS):
+    """the 10 numbers of COCOeval.summarize for keypoints, in KP_STAT_NAMES' order; acc was accumulated with KP_AREA_RNG and KP_MAX_DETS"""
+    P, Rc = acc["precision"], acc["recall"]
+
+    def ap(a=0, thr=None):
+        s = P[:, :, :, a, 0]
+        return _mean_valid(s if thr is None else s[np.where(thr == thrs)[0]])
+
+    def ar(a=0, thr=None):
+        s = Rc[:, :, a, 0]
+        return _mean_valid(s if thr is None else s[np.where(thr == thrs)[0]])
+
+    return np.array([ap(), ap(thr=.5), ap(thr=.75), ap(1), ap(2), ar(), ar(thr=.5), ar(thr=.75), ar(1), ar(2)], np.float64)
+
+
 def summary_text(stats, iou_type):
     """the lines COCOeval.summarize prints"""
     rows = [("Average Precision", "AP", "0.50:0.95", "all", 100), ("Average Precision", "AP", "0.50", "all", 100),
@@ -159,6 +232,9 @@ def summary_text(stats, iou_type):
             ("Average Recall", "AR", "0.50:0.95", "all", 1), ("Average Recall", "AR", "0.50:0.95", "all", 10),
             ("Average Recall", "AR", "0.50:0.95", "all", 100), ("Average Recall", "AR", "0.50:0.95", "small", 100),
             ("Average Recall", "AR", "0.50:0.95", "medium", 100), ("Average Recall", "AR", "0.50:0.95", "large", 100)]
+    if iou_type == "keypoints":
+        rows = [(title, kind, iou, area, KP_MAX_DETS[0]) for title, kind in (("Average Precision", "AP"), ("Average Recall", "AR"))
+                for iou, area in (("0.50:0.95", "all"), ("0.50", "all"), ("0.75", "all"), ("0.50:0.95", "medium"), ("0.50:0.95", "large"))]
     lines = ["COCO {} summary".format(iou_type)]
     for (title, kind, iou, area, md), v in zip(rows, stats):
         lines.append(" {:<18} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(title + " (" + kind + ")", iou, area, md, v))
@@ -166,5 +242,5 @@ def summary_text(stats, iou_type):
 
 
 def score_groups_host(groups, area_rng=AREA_RNG, thrs=IOU_THRS):
-    """groups: list of {"iou" [D,G], "det_area", "gt_area", "gt_crowd"} -> list of evaluate_img results"""
-    return [evaluate_img(g["iou"], g["det_area"], g["gt_area"], g["gt_crowd"], area_rng, thrs) for g in groups]
+    """groups: list of {"iou" [D,G], "det_area", "gt_area", "gt_crowd" and, for keypoints, "gt_ignore"} -> list of evaluate_img results"""
+    return [evaluate_img(g["iou"], g["det_area"], g["gt_area"], g["gt_crowd"], area_rng, thrs, g.get("gt_ignore")) for g in groups]

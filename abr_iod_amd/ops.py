@@ -1923,13 +1923,48 @@ def coco_mask_iou(inter, area_p, area_t, gt_crowd):
     return iou
 
 
-def coco_match(iou, det_counts, gt_counts, det_area, gt_area, gt_crowd, area_rng, thrs, device="cuda"):
+def coco_oks(det_kp, gt_kp, gt_box, gt_area, sigmas, det_counts, gt_counts, device="cuda"):
+    """pycocotools' computeOks for every group of a batch in one launch.  det_kp [D_total,K,3], gt_kp [G_total,K,3] (x, y, visibility),
+    gt_box [G_total,4] xywh, gt_area [G_total], sigmas [K] (float64; numpy or tensors); det_counts / gt_counts: detections / ground truths
+    per group.  -> (oks float64 device [sum D_k * G_k] in coco_box_iou's layout, iou_off int64 numpy [n+1])"""
+    import numpy as np
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("coco_oks runs on the device; the host restatement is evaluation/coco/coco_eval_host.py")
+    det_counts, gt_counts = np.asarray(det_counts, np.int64).reshape(-1), np.asarray(gt_counts, np.int64).reshape(-1)
+    if det_counts.shape != gt_counts.shape or (det_counts < 0).any() or (gt_counts < 0).any():
+        raise RuntimeError("coco_oks: one non-negative detection count and ground-truth count per group")
+    n = len(det_counts)
+    with torch.cuda.device(dev):
+        var = (_f64_dev(sigmas, dev, (-1,)) * 2) ** 2
+        K = var.numel()
+        if K < 1:
+            raise RuntimeError("coco_oks: no sigmas (one per keypoint)")
+        det_off, det_off_d = _coco_offsets(det_counts, dev)
+        gt_off, gt_off_d = _coco_offsets(gt_counts, dev)
+        iou_off, iou_off_d = _coco_offsets(det_counts * gt_counts, dev)
+        det_kp, gt_kp = _f64_dev(det_kp, dev, (-1, K, 3)), _f64_dev(gt_kp, dev, (-1, K, 3))
+        gt_box, gt_area = _f64_dev(gt_box, dev, (-1, 4)), _f64_dev(gt_area, dev, (-1,))
+        if det_kp.shape[0] != det_off[-1] or gt_kp.shape[0] != gt_off[-1] or gt_box.shape[0] != gt_off[-1] or gt_area.numel() != gt_off[-1]:
+            raise RuntimeError("coco_oks: {} detections / {} ground truths / {} boxes / {} areas of {} keypoints for counts that sum to {} / {}".format(
+                det_kp.shape[0], gt_kp.shape[0], gt_box.shape[0], gt_area.numel(), K, det_off[-1], gt_off[-1]))
+        total = int(iou_off[-1])
+        oks = torch.empty((total,), dtype=torch.float64, device=dev)
+        if n and total:
+            L.check(L.lib().abr_coco_oks(L.ptr(det_kp), L.ptr(gt_kp), L.ptr(gt_box), L.ptr(gt_area), L.ptr(var), K, L.ptr(det_off_d), L.ptr(gt_off_d),
+                                         L.ptr(iou_off_d), n, total, L.ptr(oks), L.stream()), "coco_oks")
+    return oks, iou_off
+
+
+def coco_match(iou, det_counts, gt_counts, det_area, gt_area, gt_crowd, area_rng, thrs, device="cuda", gt_ignore=None):
     """pycocotools' evaluateImg for every group of a batch, all area ranges and all IoU thresholds in one launch.  iou: the flat float64
     matrices of coco_box_iou's layout (device tensor or numpy); det_area [D_total], gt_area [G_total], gt_crowd [G_total]; area_rng [A,2]
     (inclusive); thrs [T] float64, used as given.  -> dict of numpy arrays:
         dt_gt   int32 [A,T,D_total]  the matched ground truth's row in its group, -1 = unmatched
         dt_ig   bool  [A,T,D_total]  the detection is ignored
         gt_ig   bool  [A,G_total]    the ground truth is ignored
+    gt_ignore [G_total]: the protocol's `ignore` flag of a ground truth (keypoints: crowd or no labelled keypoint); None = gt_crowd, as
+    for boxes and masks.  It decides beside the area range whether a ground truth is ignored; gt_crowd alone lets one match again.
         n_fallback                   groups with more than COCO_MATCH_MAX_GT ground truths: scored by the host restatement
                                      (coco_eval_host.evaluate_img), never truncated
     Matches are recorded by row, not by annotation id."""
@@ -1951,7 +1986,9 @@ def coco_match(iou, det_counts, gt_counts, det_area, gt_area, gt_crowd, area_rng
         Dt, Gt = int(det_off[-1]), int(gt_off[-1])
         iou_d = _f64_dev(iou, dev, (-1,))
         d_area, g_area, crowd = _f64_dev(det_area, dev, (-1,)), _f64_dev(gt_area, dev, (-1,)), _u8_dev(gt_crowd, dev)
-        if iou_d.numel() != iou_off[-1] or d_area.numel() != Dt or g_area.numel() != Gt or crowd.numel() != Gt:
+        ignore = None if gt_ignore is None else _u8_dev(gt_ignore, dev)
+        if iou_d.numel() != iou_off[-1] or d_area.numel() != Dt or g_area.numel() != Gt or crowd.numel() != Gt or (
+                ignore is not None and ignore.numel() != Gt):
             raise RuntimeError("coco_match: the flat arrays do not have the lengths the counts sum to")
         iou_arg = iou_d if iou_d.numel() else torch.zeros((1,), dtype=torch.float64, device=dev)      # (no pair at all: still a valid address)
         dt_gt = torch.full((A, T, Dt), -1, dtype=torch.int32, device=dev)
@@ -1960,9 +1997,12 @@ def coco_match(iou, det_counts, gt_counts, det_area, gt_area, gt_crowd, area_rng
         n_over = torch.zeros((1,), dtype=torch.int32, device=dev)
         if n:
             rng_d, thr_d = torch.from_numpy(area_rng.copy()).to(dev), torch.from_numpy(thrs.copy()).to(dev)
-            L.check(L.lib().abr_coco_match(L.ptr(iou_arg), L.ptr(iou_off_d), L.ptr(det_off_d), L.ptr(gt_off_d), L.ptr(d_area), L.ptr(g_area), L.ptr(crowd),
-                                           n, Dt, Gt, L.ptr(rng_d), A, L.ptr(thr_d), T, L.ptr(dt_gt), L.ptr(dt_ig), L.ptr(gt_ig), L.ptr(n_over),
-                                           L.stream()), "coco_match")
+            head = (L.ptr(iou_arg), L.ptr(iou_off_d), L.ptr(det_off_d), L.ptr(gt_off_d), L.ptr(d_area), L.ptr(g_area), L.ptr(crowd))
+            tail = (n, Dt, Gt, L.ptr(rng_d), A, L.ptr(thr_d), T, L.ptr(dt_gt), L.ptr(dt_ig), L.ptr(gt_ig), L.ptr(n_over), L.stream())
+            if ignore is None:
+                L.check(L.lib().abr_coco_match(*head, *tail), "coco_match")
+            else:
+                L.check(L.lib().abr_coco_match_ig(*head, L.ptr(ignore), *tail), "coco_match")
         out = {"dt_gt": dt_gt.cpu().numpy(), "dt_ig": dt_ig.cpu().numpy().astype(bool), "gt_ig": gt_ig.cpu().numpy().astype(bool)}
         skipped = int(n_over.cpu().item())
     over = np.nonzero(gt_counts > COCO_MATCH_MAX_GT)[0]
@@ -1972,11 +2012,12 @@ def coco_match(iou, det_counts, gt_counts, det_area, gt_area, gt_crowd, area_rng
         from .data.datasets.evaluation.coco import coco_eval_host as H
         iou_h = iou_d.cpu().numpy() if any(det_counts[k] for k in over) else None
         d_area_h, g_area_h, crowd_h = d_area.cpu().numpy(), g_area.cpu().numpy(), crowd.cpu().numpy().astype(bool)
+        ignore_h = None if ignore is None else ignore.cpu().numpy().astype(bool)
         for k in over:
             D, G = int(det_counts[k]), int(gt_counts[k])
             ds, gs = slice(det_off[k], det_off[k + 1]), slice(gt_off[k], gt_off[k + 1])
             mat = iou_h[iou_off[k]: iou_off[k + 1]].reshape(D, G) if D else np.zeros((0, G))
-            r = H.evaluate_img(mat, d_area_h[ds], g_area_h[gs], crowd_h[gs], area_rng, thrs)
+            r = H.evaluate_img(mat, d_area_h[ds], g_area_h[gs], crowd_h[gs], area_rng, thrs, None if ignore_h is None else ignore_h[gs])
             out["dt_gt"][:, :, ds], out["dt_ig"][:, :, ds], out["gt_ig"][:, gs] = r["dt_gt"], r["dt_ig"], r["gt_ig"]
     out["n_fallback"] = len(over)
     return out

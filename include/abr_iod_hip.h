@@ -705,7 +705,8 @@ int abr_poly_mask_targets(const float* const* coord_ptrs, const int64_t* const* 
                           float* out, void* stream);
 
 /* =====================================================================================================
- * 13. COCO detection scoring (csrc/coco_eval.hip): the per-image work of pycocotools' COCOeval -- computeIoU and evaluateImg -- restated
+ * 13. COCO detection scoring (csrc/coco_eval.hip, csrc/coco_oks.hip): the per-image work of pycocotools' COCOeval -- computeIoU / computeOks
+ *     and evaluateImg -- restated
  *     from the protocol.  A GROUP is one (image, category) pair: its detections in rank order (score descending,
  *     stable, at most maxDets) and its ground truths in file order.  The groups of a batch lie flat: group k owns detections
  *     [det_off[k], det_off[k+1]), ground truths [gt_off[k], gt_off[k+1]) and the row-major D_k x G_k float64 IoU matrix at iou_off[k]
@@ -731,6 +732,20 @@ int abr_coco_mask_iou(const int32_t* inter, const int32_t* area_p, const int32_t
 int abr_coco_match(const double* iou, const int64_t* iou_off, const int64_t* det_off, const int64_t* gt_off, const double* det_area,
                    const double* gt_area, const uint8_t* gt_crowd, int n_groups, int64_t d_total, int64_t g_total, const double* area_rng, int A,
                    const double* thrs, int T, int32_t* dt_gt, uint8_t* dt_ig, uint8_t* gt_ig, int32_t* n_over, void* stream);
+/* abr_coco_match with the protocol's `ignore` flag beside the crowd flag: gt_ignore uint8 [G_total]; a ground truth is ignored when
+ * gt_ignore is set or its area is outside the range, and gt_crowd alone lets a matched ground truth be matched again.  Keypoints:
+ * gt_ignore = crowd or no labelled keypoint.  abr_coco_match is this entry with gt_ignore = gt_crowd. */
+int abr_coco_match_ig(const double* iou, const int64_t* iou_off, const int64_t* det_off, const int64_t* gt_off, const double* det_area,
+                      const double* gt_area, const uint8_t* gt_crowd, const uint8_t* gt_ignore, int n_groups, int64_t d_total, int64_t g_total,
+                      const double* area_rng, int A, const double* thrs, int T, int32_t* dt_gt, uint8_t* dt_ig, uint8_t* gt_ig, int32_t* n_over,
+                      void* stream);
+/* computeOks (csrc/coco_oks.hip): det_kp [D_total,K,3], gt_kp [G_total,K,3] float64 (x, y, visibility), gt_box [G_total,4] xywh, gt_area
+ * [G_total], var [K] = (2 sigma_k)^2 -> oks float64 [total] in abr_coco_box_iou's layout.  With k1 = the ground truth's keypoints of
+ * visibility > 0: k1 > 0: the mean over those of exp(-((xd-xg)^2 + (yd-yg)^2) / var_k / (area + 2^-52) / 2); k1 == 0: the mean over all K
+ * with the distances to the box doubled about itself ([x - w, x + 2w] x [y - h, y + 2h]) in place of the differences.  One rounding per
+ * operation, the sum serial in keypoint order; crowds get no special value.  Any K >= 1, no cap on D or G. */
+int abr_coco_oks(const double* det_kp, const double* gt_kp, const double* gt_box, const double* gt_area, const double* var, int K,
+                 const int64_t* det_off, const int64_t* gt_off, const int64_t* iou_off, int n_groups, int64_t total, double* oks, void* stream);
 
 /* =====================================================================================================
  * 14. Keypoint head (MODEL.KEYPOINT_ON; csrc/keypoint.hip; maskrcnn_benchmark/modeling/roi_heads/keypoint_head/).  The low-resolution heat

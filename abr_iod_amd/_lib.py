@@ -193,6 +193,8 @@ _SIGS = {
     "abr_kp_loss_max_plane": (_i, []),
     "abr_kp_loss": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "abr_kp_decode": (_i, [_vp, _i64, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "abr_proposal_cover_max_prop": (_i, []),
+    "abr_proposal_cover": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 # every symbol include/abr_iod_hip.h declares (tests/test_abi.py checks the library exports them all)

@@ -8,7 +8,9 @@ over every image, category, area range and IoU threshold.  Here the protocol is 
 device="cpu" scores everything with the host restatement instead: the yardstick of the tests, never chosen silently.
 "keypoints" scores the "keypoints" field the keypoint head (MODEL.KEYPOINT_ON) puts on the detections, under the keypoint protocol's
 own parameters: at most 20 detections per image, the area ranges all / medium / large, ground truths without a labelled keypoint ignored.
-Not carried: box_only (proposal recall)."""
+box_only (predictions that carry an "objectness" field: RPN proposals) scores proposal recall instead, the reference's
+evaluate_box_proposals: AR at 100 and 1000 proposals for all / small / medium / large ground truths.  The greedy
+cover of every image, limit and area range runs in one launch (ops.proposal_cover); the restatement (coco_eval_host.proposal_recall_host, float32 as the reference computes it) is what device="cpu" runs."""
 import json
 import logging
 import os
@@ -21,10 +23,29 @@ from ..voc.coco_results import prepare_for_coco_segmentation  # noqa: F401
 from . import coco_eval_host as H
 
 
+class MissingObjectness(ValueError, NotImplementedError):
+    """box_only was asked of predictions that carry no "objectness" field: a bad value for the caller, and, for detections, a score this
+    module does not produce (their boxes are not ranked as proposals).  Callers written while box_only was not carried at all caught
+    NotImplementedError for exactly this call; they keep working."""
+
+
 def do_coco_evaluation(dataset, predictions, box_only, output_folder, iou_types, expected_results, expected_results_sigma_tol, device="cuda"):
     logger = logging.getLogger("maskrcnn_benchmark.inference")
     if box_only:
-        raise NotImplementedError("box_only (proposal recall of an RPN-only model) is not carried; evaluate with iou_types=('bbox',)")
+        logger.info("Evaluating bbox proposals")
+        res = COCOResults("box_proposal")
+        areas = ("all", "small", "medium", "large")
+        cells, n_fallback = score_proposals(proposal_images(predictions, dataset), H.PROPOSAL_LIMITS,
+                                            [H.PROPOSAL_AREA_RNG[H.PROPOSAL_AREAS[a]] for a in areas], None, device)
+        for key, limit, area in H.PROPOSAL_METRICS:          # the eight cells come out of ONE ops.proposal_cover call
+            res.results["box_proposal"][key] = cells[H.PROPOSAL_LIMITS.index(limit)][areas.index(area)]["ar"].item()
+        if n_fallback:
+            logger.info("{} images were left to the host restatement (more proposals or ground truths than the kernel holds)".format(n_fallback))
+        logger.info(res)
+        check_expected_results(res, expected_results, expected_results_sigma_tol)
+        if output_folder:
+            torch.save(res, os.path.join(output_folder, "box_proposals.pth"))
+        return res, None
     unknown = [t for t in iou_types if t not in ("bbox", "segm", "keypoints")]
     if unknown:
         raise NotImplementedError("COCO evaluation of {} is not carried (bbox, segm and keypoints are)".format(unknown))
@@ -93,6 +114,70 @@ def prepare_for_coco_keypoint(predictions, dataset):
     return coco_results
 
 
+# ------------------------------------------------------------------------------------------------ proposal recall
+def proposal_images(predictions, dataset):
+    """predictions (BoxLists with an "objectness" field, in dataset order) -> the images coco_eval_host's proposal-recall section takes:
+    the proposals resized to the original image size (BoxList.resize) and ALL annotations of the image as the file gives them"""
+    images = []
+    for image_id, prediction in enumerate(predictions):
+        original_id = dataset.id_to_img_map[image_id]
+        if not prediction.has_field("objectness"):
+            raise MissingObjectness('image {}: the prediction has no "objectness" field (its fields: {}); proposal recall (box_only) scores '
+                                    'RPN proposals'.format(original_id, prediction.fields()))
+        info = dataset.get_img_info(image_id)
+        prediction = prediction.copy_with_fields(["objectness"]).resize((info["width"], info["height"])).convert("xyxy")
+        anno = dataset.get_annotations(image_id)
+        images.append({"boxes": prediction.bbox.detach().to("cpu", torch.float32).reshape(-1, 4),
+                       "objectness": prediction.get_field("objectness").detach().cpu().reshape(-1),
+                       "gt_boxes": [obj["bbox"] for obj in anno], "gt_area": [obj["area"] for obj in anno],
+                       "gt_crowd": [obj.get("iscrowd", 0) != 0 for obj in anno]})
+    return images
+
+
+def score_proposals(images, limits, area_ranges, thresholds=None, device="cuda"):
+    """The dataset-free core of proposal recall: images (see coco_eval_host) x limits [L] x area_ranges [A] of (lo, hi) ->
+    ([L][A] result dicts of evaluate_box_proposals, the number of images the kernel left to the host).  device "cuda": one
+    ops.proposal_cover launch for all L x A cells; "cpu": the host restatement, cell by cell."""
+    from ..... import ops
+    device = torch.device(device)
+    thresholds = H.proposal_thresholds() if thresholds is None else torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1)
+    limits = [int(v) for v in limits]
+    if device.type != "cuda":
+        return [[H.proposal_recall_host(images, thresholds, limit=lim, area_range=tuple(r)) for r in area_ranges] for lim in limits], 0
+    props, gts, areas = [], [], []
+    for im in images:
+        boxes = torch.as_tensor(im["boxes"], dtype=torch.float32).reshape(-1, 4)
+        props.append(boxes[H.proposal_rank(im["objectness"], max(limits))])
+        g, a = H.proposal_ground_truth(im["gt_boxes"], im["gt_area"], im["gt_crowd"])
+        gts.append(g)
+        areas.append(a)
+    cat = lambda ts, shape: (torch.cat(ts) if ts else torch.zeros((0,) + shape[1:])).reshape(shape)      # noqa: E731
+    out = ops.proposal_cover(cat(props, (-1, 4)), cat(gts, (-1, 4)), cat(areas, (-1,)), [len(p) for p in props], [len(g) for g in gts],
+                             np.asarray(area_ranges, np.float32).reshape(-1, 2), limits, thresholds, device)
+    cells = []
+    for li in range(len(limits)):
+        row = []
+        for a in range(len(area_ranges)):
+            v = torch.from_numpy(out["overlaps"][li, a])
+            row.append(H.proposal_summary(torch.sort(v[v >= 0])[0], out["hits"][li, a], int(out["num_pos"][a]), thresholds))
+        cells.append(row)
+    return cells, out["n_fallback"]
+
+
+def evaluate_box_proposals(predictions, dataset, thresholds=None, area="all", limit=None, device="cuda"):
+    """the reference's evaluate_box_proposals (coco_eval.py:245-356) plus `device` -> {"ar", "recalls", "thresholds", "gt_overlaps",
+    "num_pos"}; limit None: every proposal counts.  See coco_eval_host.proposal_recall_host for the protocol and its one deviation.
+    Where device="cuda" differs from "cpu": more than 16 thresholds raise (ops.proposal_cover takes at most 16), and an image with more
+    proposals inside the limit than ops.PROPOSAL_COVER_MAX_PROP (1024; only limit None or a limit above it lets that happen) or more than
+    ops.COCO_MATCH_MAX_GT non-crowd ground truths is scored by the host restatement inside the call -- same numbers, host speed."""
+    assert area in H.PROPOSAL_AREAS, "Unknown area range: {}".format(area)
+    images = proposal_images(predictions, dataset)
+    if torch.device(device).type != "cuda":
+        return H.proposal_recall_host(images, thresholds, area=area, limit=limit)
+    lim = max([len(im["boxes"]) for im in images] + [1]) if limit is None else limit
+    return score_proposals(images, [lim], [H.PROPOSAL_AREA_RNG[H.PROPOSAL_AREAS[area]]], thresholds, device)[0][0][0]
+
+
 class COCOEvalResult(object):
     """what one iou_type's evaluation leaves: stats (the numbers of COCOeval.summarize: 12 in coco_eval_host.STAT_NAMES' order, for
     keypoints 10 in KP_STAT_NAMES'), the precision [T,R,K,A,M] and recall [T,K,A,M] tables, and how the groups were scored"""
@@ -107,7 +192,8 @@ class COCOEvalResult(object):
 
 class COCOResults(object):
     METRICS = {"bbox": ["AP", "AP50", "AP75", "APs", "APm", "APl"], "segm": ["AP", "AP50", "AP75", "APs", "APm", "APl"],
-               "keypoints": ["AP", "AP50", "AP75", "APm", "APl"]}
+               "keypoints": ["AP", "AP50", "AP75", "APm", "APl"],
+               "box_proposal": ["AR@100", "ARs@100", "ARm@100", "ARl@100", "AR@1000", "ARs@1000", "ARm@1000", "ARl@1000"]}
 
     def __init__(self, *iou_types):
         assert all(t in COCOResults.METRICS for t in iou_types), iou_types

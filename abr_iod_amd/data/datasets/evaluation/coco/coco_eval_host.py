@@ -8,7 +8,10 @@ A GROUP is one (image, category) pair: its detections in rank order (score desce
 truths in file order.
 
 One deliberate difference: a match is recorded by the ground truth's ROW in its group, -1 = none.  pycocotools stores annotation ids
-and tests them with `> 0` / `== 0`, so an annotation (or detection) whose id is 0 reads as unmatched; that quirk is not reproduced."""
+and tests them with `> 0` / `== 0`, so an annotation (or detection) whose id is 0 reads as unmatched; that quirk is not reproduced.
+
+The last section restates proposal recall (evaluate_box_proposals, the box_only metric of RPN proposals) in torch float32, the
+arithmetic the reference runs it in: the yardstick of csrc/proposal_recall.hip and what device="cpu" scores with."""
 import numpy as np
 
 IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
@@ -244,3 +247,115 @@ def summary_text(stats, iou_type):
 def score_groups_host(groups, area_rng=AREA_RNG, thrs=IOU_THRS):
     """groups: list of {"iou" [D,G], "det_area", "gt_area", "gt_crowd" and, for keypoints, "gt_ignore"} -> list of evaluate_img results"""
     return [evaluate_img(g["iou"], g["det_area"], g["gt_area"], g["gt_crowd"], area_rng, thrs, g.get("gt_ignore")) for g in groups]
+
+
+# ------------------------------------------------------------------------------------------------ proposal recall
+# evaluate_box_proposals (maskrcnn_benchmark's coco_eval.py:245-356) restated line for line, in torch float32 as the reference computes
+# it.  An IMAGE is a dict: "boxes" [P,4] xyxy at the original image size and "objectness" [P] (the proposals, in any order), "gt_boxes"
+# [G,4] xywh, "gt_area" [G] and "gt_crowd" [G] (the annotations, in file order).  Nothing here knows a dataset.
+PROPOSAL_LIMITS = (100, 1000)
+PROPOSAL_AREAS = {"all": 0, "small": 1, "medium": 2, "large": 3, "96-128": 4, "128-256": 5, "256-512": 6, "512-inf": 7}
+PROPOSAL_AREA_RNG = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2], [96 ** 2, 128 ** 2],
+                     [128 ** 2, 256 ** 2], [256 ** 2, 512 ** 2], [512 ** 2, 1e5 ** 2]]
+PROPOSAL_METRICS = [("AR{}@{:d}".format(s, lim), lim, a) for lim in PROPOSAL_LIMITS for a, s in (("all", ""), ("small", "s"), ("medium", "m"), ("large", "l"))]
+
+
+def proposal_thresholds():
+    import torch
+    return torch.arange(0.5, 0.95 + 1e-5, 0.05, dtype=torch.float32)
+
+
+def proposal_rank(objectness, limit=None):
+    """indices of the proposals in rank order: objectness descending, equal values in their incoming order, cut at limit"""
+    import torch
+    inds = torch.sort(torch.as_tensor(objectness).reshape(-1), descending=True, stable=True)[1]
+    return inds if limit is None else inds[:limit]
+
+
+def proposal_ground_truth(gt_boxes, gt_area, gt_crowd):
+    """the non-crowd annotations -> (float32 [G,4] xyxy with the reference's + 1 convention: x2 = x + max(w - 1, 0); float32 [G] areas: the
+    annotations' `area` fields ROUNDED to float32, as torch.as_tensor(list) leaves them before they are compared with a range)"""
+    import torch
+    keep = [i for i, c in enumerate(gt_crowd) if not c]
+    box = torch.as_tensor(np.asarray(gt_boxes, np.float64).reshape(-1, 4)[keep], dtype=torch.float32).reshape(-1, 4)
+    x, y, w, h = box.unbind(-1)
+    xyxy = torch.stack((x, y, x + (w - 1).clamp(min=0), y + (h - 1).clamp(min=0)), -1)
+    return xyxy, torch.as_tensor(np.asarray(gt_area, np.float64).reshape(-1)[keep], dtype=torch.float32).reshape(-1)
+
+
+def proposal_iou(prop, gt):
+    """boxlist_iou: float32 [P,4] x [G,4] xyxy -> [P,G], one rounding per operation, in the reference's operation order"""
+    import torch
+    area1 = (prop[:, 2] - prop[:, 0] + 1) * (prop[:, 3] - prop[:, 1] + 1)
+    area2 = (gt[:, 2] - gt[:, 0] + 1) * (gt[:, 3] - gt[:, 1] + 1)
+    lt = torch.max(prop[:, None, :2], gt[:, :2])
+    rb = torch.min(prop[:, None, 2:], gt[:, 2:])
+    wh = (rb - lt + 1).clamp(min=0)
+    inter = wh[:, :, 0] * wh[:, :, 1]
+    return inter / (area1[:, None] + area2 - inter)
+
+
+def proposal_cover(prop, gt):
+    """the cover of coco_eval.py:316-334: float32 [G], the min(P, G) recorded overlaps in round order, then zeros.  Each round takes the
+    largest remaining overlap (Tensor.max: the first maximal index, so ties go to the lowest ground truth, then the lowest proposal
+    rank) and retires its proposal and its ground truth.  P > 0 and G > 0."""
+    import torch
+    overlaps = proposal_iou(prop, gt)
+    out = torch.zeros(len(gt))
+    for j in range(min(len(prop), len(gt))):
+        max_overlaps, argmax_overlaps = overlaps.max(dim=0)
+        gt_ovr, gt_ind = max_overlaps.max(dim=0)
+        assert gt_ovr >= 0
+        box_ind = argmax_overlaps[gt_ind]
+        out[j] = overlaps[box_ind, gt_ind]
+        assert out[j] == gt_ovr
+        overlaps[box_ind, :] = -1
+        overlaps[:, gt_ind] = -1
+    return out
+
+
+def proposal_summary(gt_overlaps, hits, num_pos, thresholds):
+    """the reference's result dict from the sorted overlaps, the counts of overlaps >= threshold and num_pos (coco_eval.py:344-356)"""
+    import torch
+    recalls = torch.zeros_like(thresholds)
+    for i in range(len(thresholds)):
+        recalls[i] = torch.tensor(int(hits[i])).float() / float(num_pos)
+    return {"ar": recalls.mean(), "recalls": recalls, "thresholds": thresholds, "gt_overlaps": gt_overlaps, "num_pos": num_pos}
+
+
+def proposal_recall_host(images, thresholds=None, area="all", limit=None, area_range=None):
+    """evaluate_box_proposals over `images` (see above) -> {"ar", "recalls", "thresholds", "gt_overlaps", "num_pos"}.
+    area: a key of PROPOSAL_AREAS, or give area_range = (lo, hi) itself; a ground truth is in the range when lo <= area <= hi.
+    One deviation: a range without a ground truth in the whole dataset (the reference raises from torch.cat([])) gives ar = nan, nan
+    recalls and an empty gt_overlaps; with ground truths but no image that has proposals too, the recalls are 0."""
+    import torch
+    if area_range is None:
+        assert area in PROPOSAL_AREAS, "Unknown area range: {}".format(area)
+        area_range = PROPOSAL_AREA_RNG[PROPOSAL_AREAS[area]]
+    gt_overlaps = []
+    num_pos = 0
+    for im in images:
+        boxes = torch.as_tensor(im["boxes"], dtype=torch.float32).reshape(-1, 4)
+        inds = proposal_rank(im["objectness"])
+        boxes = boxes[inds]
+        gt_boxes, gt_areas = proposal_ground_truth(im["gt_boxes"], im["gt_area"], im["gt_crowd"])
+        if len(gt_boxes) == 0:
+            continue
+        valid_gt_inds = (gt_areas >= area_range[0]) & (gt_areas <= area_range[1])
+        gt_boxes = gt_boxes[valid_gt_inds]
+        num_pos += len(gt_boxes)
+        if len(gt_boxes) == 0:
+            continue
+        if len(boxes) == 0:
+            continue
+        if limit is not None and len(boxes) > limit:
+            boxes = boxes[:limit]
+        gt_overlaps.append(proposal_cover(boxes, gt_boxes))
+    gt_overlaps = torch.sort(torch.cat(gt_overlaps, dim=0))[0] if gt_overlaps else torch.zeros(0)
+    if thresholds is None:
+        thresholds = proposal_thresholds()
+    thresholds = torch.as_tensor(thresholds, dtype=torch.float32)
+    recalls = torch.zeros_like(thresholds)
+    for i, t in enumerate(thresholds):
+        recalls[i] = (gt_overlaps >= t).float().sum() / float(num_pos)
+    return {"ar": recalls.mean(), "recalls": recalls, "thresholds": thresholds, "gt_overlaps": gt_overlaps, "num_pos": num_pos}

@@ -2021,3 +2021,94 @@ def coco_match(iou, det_counts, gt_counts, det_area, gt_area, gt_crowd, area_rng
             out["dt_gt"][:, :, ds], out["dt_ig"][:, :, ds], out["gt_ig"][:, gs] = r["dt_gt"], r["dt_ig"], r["gt_ig"]
     out["n_fallback"] = len(over)
     return out
+
+
+# ----------------------------------------------------------------------------------------------- proposal recall (csrc/proposal_recall.hip)
+PROPOSAL_COVER_MAX_PROP = 1024      # ABR_PROPOSAL_COVER_MAX_PROP: the proposals per image proposal_cover's kernel holds
+
+
+def _f32_dev(a, dev, shape):
+    import numpy as np
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.float32:
+            raise RuntimeError("proposal_cover: expected float32 tensors, got {}".format(a.dtype))
+        return a.to(dev).reshape(shape).contiguous()
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise RuntimeError("proposal_cover: expected float32 arrays, got {} (the protocol's arithmetic is float32: round on purpose)".format(a.dtype))
+    return torch.from_numpy(np.ascontiguousarray(a.reshape(shape))).to(dev)
+
+
+def proposal_cover(prop, gt, gt_area, prop_counts, gt_counts, area_rng, limits, thrs, device="cuda"):
+    """evaluate_box_proposals' greedy cover for every image, proposal limit and area range of a dataset in one launch.  prop float32
+    [P_total,4] xyxy in rank order at the original image size (cut at the largest limit), gt float32 [G_total,4] xyxy (non-crowd), gt_area
+    float32 [G_total] (numpy or tensors; float32 is required, not converted to: the protocol compares the rounded areas); prop_counts /
+    gt_counts: proposals / ground truths per image; area_rng [A,2] (inclusive), limits [L], thrs [T] float32, used as given.
+    -> dict of numpy arrays:
+        overlaps  float32 [L,A,G_total]  per image segment: the cell's recorded overlaps in round order, zeros up to the number of ground
+                                         truths in range, then -1; all -1 where the cell has no proposal or no ground truth in range
+        hits      int32 [L,A,T]          how many overlaps of the cell vectors are >= thrs[t]
+        num_pos   int32 [A]              ground truths in range
+        n_fallback                       images with more than PROPOSAL_COVER_MAX_PROP proposals or COCO_MATCH_MAX_GT ground truths:
+                                         scored by the host restatement (coco_eval_host.proposal_cover), never truncated"""
+    import numpy as np
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("proposal_cover runs on the device; the host restatement is evaluation/coco/coco_eval_host.py")
+    prop_counts, gt_counts = np.asarray(prop_counts, np.int64).reshape(-1), np.asarray(gt_counts, np.int64).reshape(-1)
+    if prop_counts.shape != gt_counts.shape or (prop_counts < 0).any() or (gt_counts < 0).any():
+        raise RuntimeError("proposal_cover: one non-negative proposal count and ground-truth count per image")
+    area_rng = np.asarray(area_rng, np.float32).reshape(-1, 2)
+    limits = np.asarray(limits, np.int64).reshape(-1)
+    thrs = (thrs.detach().cpu().numpy() if isinstance(thrs, torch.Tensor) else np.asarray(thrs)).reshape(-1)
+    if thrs.dtype != np.float32:
+        raise RuntimeError("proposal_cover: the thresholds are float32 and used as given, got {}".format(thrs.dtype))
+    A, Ln, T, n = area_rng.shape[0], limits.shape[0], thrs.shape[0], len(prop_counts)
+    if not (1 <= A <= 8 and 1 <= Ln <= 4 and 1 <= T <= 16):
+        raise RuntimeError("proposal_cover: {} area ranges, {} limits, {} thresholds (1 <= A <= 8, 1 <= L <= 4, 1 <= T <= 16)".format(A, Ln, T))
+    if (limits < 1).any() or (limits >= 2 ** 31).any():
+        raise RuntimeError("proposal_cover: limits must be positive int32 values, got {}".format(limits.tolist()))
+    with torch.cuda.device(dev):
+        p_off, p_off_d = _coco_offsets(prop_counts, dev)
+        g_off, g_off_d = _coco_offsets(gt_counts, dev)
+        Pt, Gt = int(p_off[-1]), int(g_off[-1])
+        prop_d, gt_d, area_d = _f32_dev(prop, dev, (-1, 4)), _f32_dev(gt, dev, (-1, 4)), _f32_dev(gt_area, dev, (-1,))
+        if prop_d.shape[0] != Pt or gt_d.shape[0] != Gt or area_d.numel() != Gt:
+            raise RuntimeError("proposal_cover: {} proposals / {} ground truths / {} areas for counts that sum to {} / {}".format(
+                prop_d.shape[0], gt_d.shape[0], area_d.numel(), Pt, Gt))
+        overlaps = torch.empty((Ln, A, Gt), dtype=_f32, device=dev)
+        hits = torch.zeros((Ln, A, T), dtype=torch.int32, device=dev)
+        num_pos = torch.zeros((A,), dtype=torch.int32, device=dev)
+        n_over = torch.zeros((1,), dtype=torch.int32, device=dev)
+        if n and Gt:
+            rng_d, thr_d = torch.from_numpy(area_rng.copy()).to(dev), torch.from_numpy(thrs.copy()).to(dev)
+            lim_d = torch.from_numpy(limits.astype(np.int32)).to(dev)
+            L.check(L.lib().abr_proposal_cover(L.ptr(prop_d), L.ptr(gt_d), L.ptr(area_d), L.ptr(p_off_d), L.ptr(g_off_d), n, Pt, Gt, L.ptr(rng_d), A,
+                                               L.ptr(lim_d), Ln, L.ptr(thr_d), T, L.ptr(overlaps), L.ptr(hits), L.ptr(num_pos), L.ptr(n_over),
+                                               L.stream()), "proposal_cover")
+        out = {"overlaps": overlaps.cpu().numpy(), "hits": hits.cpu().numpy(), "num_pos": num_pos.cpu().numpy()}
+        skipped = int(n_over.cpu().item())
+    over = np.nonzero((gt_counts > 0) & ((gt_counts > COCO_MATCH_MAX_GT) | (prop_counts > PROPOSAL_COVER_MAX_PROP)))[0]
+    if skipped != len(over):
+        raise RuntimeError("proposal_cover: the kernel left {} images to the host, the tables say {}".format(skipped, len(over)))
+    if len(over):
+        from .data.datasets.evaluation.coco import coco_eval_host as H
+        prop_h, gt_h, area_h = prop_d.cpu(), gt_d.cpu(), area_d.cpu()
+        thr_h = torch.from_numpy(thrs.copy())
+        for k in over:
+            ps, gs = slice(p_off[k], p_off[k + 1]), slice(g_off[k], g_off[k + 1])
+            for a in range(A):
+                valid = (area_h[gs] >= float(area_rng[a, 0])) & (area_h[gs] <= float(area_rng[a, 1]))
+                Gv = int(valid.sum())
+                out["num_pos"][a] += Gv
+                for li in range(Ln):
+                    seg = out["overlaps"][li, a, gs]
+                    seg[:] = -1
+                    boxes = prop_h[ps][: int(limits[li])]
+                    if Gv == 0 or len(boxes) == 0:
+                        continue
+                    vec = H.proposal_cover(boxes, gt_h[gs][valid])
+                    seg[:Gv] = vec.numpy()
+                    out["hits"][li, a] += (vec[None, :] >= thr_h[:, None]).sum(1).to(torch.int32).numpy()
+    out["n_fallback"] = len(over)
+    return out

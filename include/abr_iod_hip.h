@@ -787,6 +787,35 @@ int abr_kp_loss(const float* x, int P, int K, int H, int W, const int64_t* tgt, 
 int abr_kp_decode(const float* maps, int64_t stride_d, int64_t stride_k, const float* boxes, int D, int K, int Hm, int Wm, float* xy,
                   float* logit, void* stream);
 
+/* =====================================================================================================
+ * 15. Proposal recall (csrc/proposal_recall.hip; evaluation/coco/coco_eval.py: evaluate_box_proposals, restated: DESIGN.md section 4).
+ *     Flat as in section 13: image k owns proposals [prop_off[k], prop_off[k+1]) and ground truths [gt_off[k], gt_off[k+1]), both tables
+ *     int64 [n_images+1].  A CELL is one (image, limit, area range).
+ * ===================================================================================================== */
+#define ABR_PROPOSAL_COVER_MAX_PROP 1024
+/* the proposals per image abr_proposal_cover holds (ABR_PROPOSAL_COVER_MAX_PROP); ground truths: ABR_COCO_MATCH_MAX_GT */
+int abr_proposal_cover_max_prop(void);
+/* The greedy cover of every cell in ONE launch.  prop float32 [p_total,4] xyxy in rank order (objectness descending, stable) at the
+ * original image size, 16-byte aligned; gt float32 [g_total,4] xyxy (non-crowd only), 16-byte aligned; gt_area float32 [g_total];
+ * area_rng float32 [A,2], both ends inclusive, A <= 8; limits int32 [L], L <= 4; thrs float32 [T], T <= 16, used as given.
+ * All of these are DEVICE pointers, so the entry cannot check their values: limits[l] < 1 makes the cells of that limit empty (all -1),
+ * and boxes must have x2 >= x1 and y2 >= y1 -- two boxes of +1-area zero have the overlap 0 / 0, which no round can select (a ground
+ * truth left with nothing else records -1, where the reference's loop fails its assertion).
+ * A cell takes the image's first min(P, limits[l]) proposals and its ground truths with lo <= gt_area <= hi (G_valid of them, file order).
+ * IoU = boxlist_iou's float32 arithmetic (area = (x2 - x1 + 1) * (y2 - y1 + 1), wh = max(min(rb) - max(lt) + 1, 0), inter / (a_p + a_g -
+ * inter)), one rounding per operation.  min(P, G_valid) rounds: the largest remaining overlap (ties: the lowest ground truth, then the
+ * lowest proposal rank) is recorded and its proposal and ground truth retire.
+ * Outputs: overlaps float32 [L,A,g_total]: of an image's segment the first G_valid slots hold the recorded values in round order, then
+ * zeros; the remaining slots -1; a cell without proposals or without a ground truth in range is all -1.  hits int32 [L,A,T]: the number of
+ * slots >= 0 with overlap >= thrs[t], added with integer atomics; num_pos int32 [A]: ground truths in range over all images that have one
+ * (with or without proposals), added likewise; hits, num_pos and *n_over are zeroed by the caller.
+ * An image with more than ABR_PROPOSAL_COVER_MAX_PROP proposals or more than ABR_COCO_MATCH_MAX_GT ground truths is NOT scored: none of
+ * its outputs is written or counted and *n_over counts it once -- the caller scores it on the host.  n_images == 0 or g_total == 0:
+ * success, nothing launched. */
+int abr_proposal_cover(const float* prop, const float* gt, const float* gt_area, const int64_t* prop_off, const int64_t* gt_off, int n_images,
+                       int64_t p_total, int64_t g_total, const float* area_rng, int A, const int32_t* limits, int L, const float* thrs, int T,
+                       float* overlaps, int32_t* hits, int32_t* num_pos, int32_t* n_over, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

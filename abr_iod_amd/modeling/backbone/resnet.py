@@ -288,28 +288,24 @@ class _FwdPlan(object):
         a3.a, a3.out, a3.stream = o2, out.data_ptr(), st
         a3.desc.residual = idt
         a3.desc.w_version = self.convs[i3].version()
-        if self.h3:
-            xw, xe = ops.amax_of(x)
-            if xw is None:
-                xw, xe = ops.amax_of(ops.amax_compute(x))
-            w1, e1 = ops.amax_new()
-            w2, e2 = ops.amax_new()
-            w3, e3 = ops.amax_new()
+        w1 = w2 = w3 = None
+        e1 = e2 = e3 = 0
+        if self.h3:   # x by the operand rule; every result here is fresh, so conv1, conv2 and conv3 emit, each word read by the next conv
+            xw, xe = ops.amax_operand(x)
+            (w1, e1), (w2, e2), (w3, e3) = ops.amax_new(), ops.amax_new(), ops.amax_new()
             d0, d2, d3 = a0.desc, a2.desc, a3.desc
             d0.x_amax, d0.x_amax_epoch, d0.out_amax, d0.out_amax_epoch = xw, xe, w1, e1
-            if self.has_ds:
+            if self.has_ds:   # (the identity branch lives in the temporaries: no tensor to tag, and conv3's epilogue reads it as fp32 -- no word)
                 d1 = arr[1].desc
                 d1.x_amax, d1.x_amax_epoch = xw, xe
             d2.x_amax, d2.x_amax_epoch, d2.out_amax, d2.out_amax_epoch = w1, e1, w2, e2
             d3.x_amax, d3.x_amax_epoch, d3.out_amax, d3.out_amax_epoch = w2, e2, w3, e3
         ops.L.check(ops.L.lib().abr_conv_run(self.ptr, n), "conv_run (bottleneck forward)")
-        if self.h3:
-            ops.amax_tag(out, w3, e3)
+        ops.conv_out_done(out, True, w3, e3)
         if not self.save:
             return out, None
-        if self.h3:
-            ops.amax_tag(t1, w1, e1)
-            ops.amax_tag(t2, w2, e2)
+        ops.conv_out_done(t1, True, w1, e1)
+        ops.conv_out_done(t2, True, w2, e2)
         return out, (x, t1, t2, out, self.s, v2)
 
 

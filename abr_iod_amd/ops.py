@@ -307,6 +307,63 @@ def amax_compute(t):
     return amax_tag(t, w, e, st)
 
 
+# ---- the conv amax-word protocol: every conv call path (conv_forward, conv_wgrad[_async], conv_backward, resnet._FwdPlan) decides its words here.
+# Where the paths differ on purpose: conv_forward(emit_amax=True) emits under any arithmetic, conv_backward's dgrad only under those that read
+# the words (it has no such argument); _FwdPlan gives the downsample branch's output no word (it lives in the table's temporaries, and nothing
+# contracts over it), the per-conv path tags that tensor like any fresh result.
+def amax_operand(t, reduce=True):
+    """(word, epoch) of a contraction operand: its tag while valid -- also with H3_TAGS off; else, with H3_TAGS on and `reduce`, a reduction
+    queued here, on the current stream, which must be the one that produced t (a side stream's wait is recorded AFTER this); else (None, 0):
+    the library reduces t inside the call.  A contiguous copy the caller had to make is a new object without a tag, so it is reduced even
+    where the original carried one."""
+    w, e = amax_of(t)
+    if w is None and reduce and H3_TAGS:
+        w, e = amax_of(amax_compute(t))
+    return w, e
+
+
+def amax_wgrad_operands(x, gy, wino_v=None):
+    """((word, epoch) of x, of gy) for a weight gradient over contiguous x, gy: x first, then gy.  With the forward pass's Winograd-domain V
+    kept (wino_v) x is never reduced -- V carries its own word inside the library -- and x's tag, when valid, is still passed on.  The pair
+    may be handed to another stream's launch (conv_wgrad(amax_refs=)) once that stream waits for this one."""
+    return amax_operand(x, reduce=wino_v is None), amax_operand(gy)
+
+
+def conv_out_emits(out, residual, sh, sw, emit_amax, math):
+    """Before the launch: may the epilogue write the amax word of the conv's result?  out = None: a fresh result.  The epilogue sees only the
+    pixels it writes, so its maximum is the tensor's when the result is fresh; when the conv adds into the very tensor it reads as residual;
+    and, scattered with strides (sh, sw) -- rows land on every sh-th / sw-th pixel of a zeroed tensor, the dgrad of a stride-2 1x1 conv --
+    only into the tensor a fresh pass of the SAME geometry zero-filled and nothing has written since (its _abr_scatter mark).  Any other
+    caller's `out` holds pixels the epilogue never sees.  emit_amax None: under the arithmetics that read the words."""
+    if emit_amax is None:
+        emit_amax = uses_amax(math)
+    if not (emit_amax and H3_TAGS):
+        return False
+    if out is None:
+        return True
+    if out is not residual:
+        return False
+    return (sh == 1 and sw == 1) or getattr(out, "_abr_scatter", None) == (out.data_ptr(), sh, sw)
+
+
+def conv_out_done(out, fresh, word, epoch, sh=1, sw=1):
+    """After the launch: tag the result with the word its epilogue wrote; a caller's `out` written without one loses whatever tag (and scatter
+    mark) it carried -- a raw kernel moves neither data_ptr nor _version; a fresh strided result is marked "zero everywhere but the pixels
+    this geometry writes"."""
+    if word is not None:
+        amax_tag(out, word, epoch)
+    elif not fresh:
+        amax_drop(out)
+    if fresh and (sh != 1 or sw != 1):
+        out._abr_scatter = (out.data_ptr(), sh, sw)
+    return out
+
+
+def _conv_result(d, scattered, device):
+    """a conv's fresh result: zeros under a scatter (out_hw given: the kernel writes only some pixels), else uninitialised"""
+    return (torch.zeros if scattered else torch.empty)((d.B, d.out_H, d.out_W, d.Cout), dtype=_f32, device=device)
+
+
 def h3_range_stats(reset=True):
     """(operand elements more than 18 binades below their tensor's amax, operand elements inspected) by the f16x3 kernels since the last
     reset (abr_h3_range_stats).  Synchronises the current stream."""
@@ -470,37 +527,14 @@ def conv_forward(x, w, stride=1, pad=0, scale=None, bias=None, residual=None, ma
     d.w_planes = L.ptr(w_planes)   # MATH_BF16X6: the caller's own pack_weights(w) planes (else the library packs (w, w_version) itself)
     d.w_version = int(w_version)   # non-zero: the library may keep data derived from (w, w_version): Winograd-domain weights, packed bf16x3 planes
     if uses_amax(math):
-        aw, ae = amax_of(x) if xc is x else (None, 0)
-        if aw is None and H3_TAGS:
-            aw, ae = amax_of(amax_compute(xc))
-        d.x_amax, d.x_amax_epoch = aw, ae
+        d.x_amax, d.x_amax_epoch = amax_operand(xc)
     fresh = out is None
-    if out is None:
-        if out_hw is not None:
-            out = torch.zeros((d.B, d.out_H, d.out_W, d.Cout), dtype=_f32, device=x.device)
-        else:
-            out = _empty((d.B, d.Ho, d.Wo, d.Cout), xc)
-    if emit_amax is None:
-        emit_amax = uses_amax(math)
-    # a strided scatter (the dgrad of a stride-2 1x1 conv: rows land on every out_sh-th pixel of a zeroed tensor) writes every non-zero element of
-    # its result, so its epilogue's amax IS the tensor's -- in the fresh pass, and in a second pass that adds into exactly that tensor
-    strided = d.out_sh != 1 or d.out_sw != 1
-    if strided:
-        covers = fresh or (out is residual and getattr(out, "_abr_scatter", None) == (out.data_ptr(), d.out_sh, d.out_sw))
-    else:
-        covers = fresh or out is residual
-    emit_amax = bool(emit_amax) and H3_TAGS and covers
-    if emit_amax:
-        ow, oe = amax_new()
-        d.out_amax, d.out_amax_epoch = ow, oe
+    ow, oe = amax_new() if conv_out_emits(out, residual, d.out_sh, d.out_sw, emit_amax, math) else (None, 0)
+    d.out_amax, d.out_amax_epoch = ow, oe
+    if fresh:
+        out = _conv_result(d, out_hw is not None, x.device)
     L.check(L.lib().abr_conv_forward(C.byref(d), L.ptr(xc), L.ptr(w), L.ptr(out), L.stream()), "conv_forward")
-    if emit_amax:
-        amax_tag(out, ow, oe)
-    elif not fresh:
-        amax_drop(out)     # a raw kernel moves neither data_ptr nor _version: whatever word `out` carried no longer bounds its values
-    if strided and fresh:
-        out._abr_scatter = (out.data_ptr(), d.out_sh, d.out_sw)   # (zero everywhere but the pixels this geometry writes)
-    return out
+    return conv_out_done(out, fresh, ow, oe, d.out_sh, d.out_sw)
 
 
 # Main-stream timeline of the UN-PROFILED step (tools/step_marks.py): with ABR_STEP_MARKS=1 `mark(name)` records an event on the current stream at
@@ -620,16 +654,8 @@ def conv_wgrad(x, gy, dw, stride=1, pad=0, scale=None, math=MATH_F32, wino_v=Non
     xc, gyc = L.f32c(x), L.f32c(gy)
     d = conv_desc(xc.shape, dw.shape, stride, pad, scale=scale, math=math)
     d.wino_v = L.ptr(wino_v)
-    if uses_amax(math):
-        if xc is x:
-            d.x_amax, d.x_amax_epoch = amax_refs[0] if amax_refs else amax_of(x)
-        if gyc is gy:
-            d.gy_amax, d.gy_amax_epoch = amax_refs[1] if amax_refs else amax_of(gy)
-        if H3_TAGS:   # (reduced here rather than inside the call so that a second consumer of the same tensor finds the tag)
-            if not d.x_amax and wino_v is None:
-                d.x_amax, d.x_amax_epoch = amax_of(amax_compute(xc))
-            if not d.gy_amax:
-                d.gy_amax, d.gy_amax_epoch = amax_of(amax_compute(gyc))
+    if uses_amax(math):   # (reduced here rather than inside the call so that a second consumer of the same tensor finds the tag)
+        (d.x_amax, d.x_amax_epoch), (d.gy_amax, d.gy_amax_epoch) = amax_refs or amax_wgrad_operands(xc, gyc, wino_v)
     L.check(L.lib().abr_conv_wgrad(C.byref(d), L.ptr(xc), L.ptr(gyc), L.ptr(dw), L.stream() if stream is None else stream), "conv_wgrad")
     return dw
 
@@ -715,6 +741,23 @@ def _wgrad_stream(dev, i):
     return side_stream(key)
 
 
+def _wgrad_owner(dw):
+    """index of the side stream that takes every gradient accumulated into the buffer dw (first-seen round-robin, see WGRAD_STREAMS)"""
+    owner = _wg_owner.get(dw.data_ptr())
+    if owner is None:
+        owner = _wg_owner[dw.data_ptr()] = len(_wg_owner) % WGRAD_STREAMS
+    return owner
+
+
+def _arm_join():
+    """the first weight gradient of a backward pass queues the join as an engine callback: from here to the join, main-stream launches share
+    the device with the side streams"""
+    if not _join_pending[0]:
+        _join_pending[0] = True
+        L.lib().abr_prof_mark_overlap(1)
+        torch.autograd.Variable._execution_engine.queue_callback(join_side_stream)
+
+
 def join_side_stream():
     """Make the current stream wait for everything queued on the side stream(s) (queued automatically as an end-of-backward
     callback by conv_wgrad_async; FusedSGD.step calls it again before touching the gradients)."""
@@ -738,27 +781,14 @@ def conv_wgrad_async(x, gy, dw, stride=1, pad=0, scale=None, math=MATH_F32, wino
     """conv_wgrad on the side stream.  Only for use inside an autograd backward (the join is an engine callback)."""
     if not WGRAD_SIDE_STREAM:
         return conv_wgrad(x, gy, dw, stride, pad, scale, math, wino_v)
-    owner = _wg_owner.get(dw.data_ptr())
-    if owner is None:
-        owner = _wg_owner[dw.data_ptr()] = len(_wg_owner) % WGRAD_STREAMS
-    side = _wgrad_stream(x.device.index, owner)
-    if not _join_pending[0]:
-        _join_pending[0] = True
-        L.lib().abr_prof_mark_overlap(1)  # from here to the join, main-stream launches share the device with the side stream
-        torch.autograd.Variable._execution_engine.queue_callback(join_side_stream)
+    side = _wgrad_stream(x.device.index, _wgrad_owner(dw))
+    _arm_join()
     # The operands are made contiguous, and their amax words reduced, HERE -- on the stream that produced them and before the side stream's wait is
     # recorded: a copy or a reduction issued after that event would not be ordered before the side stream's kernel.  The copies are what the
-    # kernel reads, so they are what is kept alive until the join.
+    # kernel reads, so they are what is kept alive until the join.  The dgrad that follows on this stream shares gy's word, and the side stream
+    # (ordered behind this point by the wait below) is handed both: a word reduced there would not be ordered before this stream's later readers.
     x, gy = L.f32c(x), L.f32c(gy)
-    refs = None
-    if uses_amax(math) and H3_TAGS:
-        # operands without an amax word get one on this stream: the dgrad that follows here shares gy's, and the side stream (ordered behind
-        # this point by the wait below) is handed both -- a word reduced on the side stream would not be ordered before this stream's later readers
-        if wino_v is None and amax_of(x)[0] is None:
-            amax_compute(x)
-        if amax_of(gy)[0] is None:
-            amax_compute(gy)
-        refs = (amax_of(x), amax_of(gy))
+    refs = amax_wgrad_operands(x, gy, wino_v) if uses_amax(math) else None
     # x, gy (and the zeroed gradient buffer) are produced on the current stream: the side stream is ordered behind it, and the launch names the
     # side stream itself (side.wait_stream(cur) + `with torch.cuda.stream(side)` cost ~30 us of Python per gradient, ~60 gradients per step)
     raw = side.cuda_stream
@@ -808,10 +838,7 @@ def conv_backward(x, gy, dw, wt, stride, pad, scale=None, math=MATH_F32, w_versi
             arr[2].kind = L.OP_FORWARD
             arr[2].desc = conv_desc(gy.shape, wt.shape, 1, dw.shape[1] - 1 - pad, out_hw=out_hw, out_stride=out_stride, math=math)
             arr[2].b = wtp
-        owner = _wg_owner.get(dw.data_ptr())
-        if owner is None:
-            owner = _wg_owner[dw.data_ptr()] = len(_wg_owner) % WGRAD_STREAMS
-        plan = _bwd_plans[key] = (arr, C.cast(arr, C.c_void_p), wtp, scp, owner, (scale, dw), threading.Lock())
+        plan = _bwd_plans[key] = (arr, C.cast(arr, C.c_void_p), wtp, scp, _wgrad_owner(dw), (scale, dw), threading.Lock())
     arr, ptr, _, _, owner, _, lock = plan
     with lock:     # (the table is shared by every host thread that runs this conv's backward pass; abr_conv_run releases the GIL)
         return _conv_backward_run(arr, ptr, owner, x, gy, dw, math, wino_v, dgrad, mask, residual, out, out_hw, w_version)
@@ -819,10 +846,7 @@ def conv_backward(x, gy, dw, wt, stride, pad, scale=None, math=MATH_F32, w_versi
 
 def _conv_backward_run(arr, ptr, owner, x, gy, dw, math, wino_v, dgrad, mask, residual, out, out_hw, w_version):
     side = _wgrad_stream(x.device.index, owner).cuda_stream
-    if not _join_pending[0]:
-        _join_pending[0] = True
-        L.lib().abr_prof_mark_overlap(1)
-        torch.autograd.Variable._execution_engine.queue_callback(join_side_stream)
+    _arm_join()
     main = L.stream()
     h3 = uses_amax(math)
     xp, gp = x.data_ptr(), gy.data_ptr()
@@ -831,58 +855,27 @@ def _conv_backward_run(arr, ptr, owner, x, gy, dw, math, wino_v, dgrad, mask, re
     a1.a, a1.b, a1.stream = xp, gp, side
     d1 = a1.desc
     d1.wino_v = wino_v.data_ptr() if wino_v is not None else None
-    if h3:
-        # operands without an amax word get one here, on the stream that produced them (see conv_wgrad_async)
-        gw, ge = amax_of(gy)
-        if gw is None:
-            gw, ge = amax_of(amax_compute(gy))
-        if wino_v is None:
-            xw, xe = amax_of(x)
-            if xw is None:
-                xw, xe = amax_of(amax_compute(x))
-        else:
-            xw, xe = amax_of(x)     # (the kept V carries its own word inside the library; x's, when there, is passed as the per-conv call does)
-        d1.x_amax, d1.x_amax_epoch, d1.gy_amax, d1.gy_amax_epoch = xw, (xe if xw is not None else 0), gw, ge
-    n_ops = 2
-    res = None
+    if h3:   # (the table is kept from call to call: every word it holds is rewritten)
+        (d1.x_amax, d1.x_amax_epoch), (gw, ge) = amax_wgrad_operands(x, gy, wino_v)
+        d1.gy_amax, d1.gy_amax_epoch = gw, ge
     if dgrad:
-        n_ops = 3
         a2 = arr[2]
         d2 = a2.desc
         fresh = out is None
+        ow, oe = amax_new() if conv_out_emits(out, residual, d2.out_sh, d2.out_sw, None, math) else (None, 0)
+        if h3:
+            d2.x_amax, d2.x_amax_epoch, d2.out_amax, d2.out_amax_epoch = gw, ge, ow, oe
         if fresh:
-            if out_hw is not None:
-                out = torch.zeros((d2.B, d2.out_H, d2.out_W, d2.Cout), dtype=_f32, device=x.device)
-            else:
-                out = torch.empty((d2.B, d2.Ho, d2.Wo, d2.Cout), dtype=_f32, device=x.device)
+            out = _conv_result(d2, out_hw is not None, x.device)
         a2.a, a2.out, a2.stream = gp, out.data_ptr(), main
         d2.residual = residual.data_ptr() if residual is not None else None
         d2.mask = mask.data_ptr() if mask is not None else None
         d2.w_version = int(w_version)
-        emit = False
-        if h3:
-            strided = d2.out_sh != 1 or d2.out_sw != 1
-            if strided:
-                emit = fresh or (out is residual and getattr(out, "_abr_scatter", None) == (out.data_ptr(), d2.out_sh, d2.out_sw))
-            else:
-                emit = fresh or out is residual
-            d2.x_amax, d2.x_amax_epoch = gw, ge
-            if emit:
-                ow, oe = amax_new()
-                d2.out_amax, d2.out_amax_epoch = ow, oe
-            else:
-                d2.out_amax, d2.out_amax_epoch = None, 0
-        res = out
-    L.check(L.lib().abr_conv_run(ptr, n_ops), "conv_run (conv backward)")
+    L.check(L.lib().abr_conv_run(ptr, 3 if dgrad else 2), "conv_run (conv backward)")
     if dgrad:
-        if emit:
-            amax_tag(out, ow, oe)
-        elif not fresh:
-            amax_drop(out)
-        if fresh and out_hw is not None and (d2.out_sh != 1 or d2.out_sw != 1):
-            out._abr_scatter = (out.data_ptr(), d2.out_sh, d2.out_sw)
+        conv_out_done(out, fresh, ow, oe, d2.out_sh, d2.out_sw)
     _wg_hold(main, (x, gy, wino_v))
-    return res
+    return out if dgrad else None
 
 
 def pack_weights(w, out=None):

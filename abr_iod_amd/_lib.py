@@ -94,6 +94,12 @@ _SIGS = {
     "abr_roi_align_backward_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "abr_roi_align_backward_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "abr_roi_align_taps": (_i, [_vp, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "abr_roi_pool_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
+    "abr_roi_pool_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "abr_roi_pool_forward_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp, _vp, _vp]),
+    "abr_roi_pool_backward_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "abr_deform_psroi_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp]),
+    "abr_deform_psroi_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "abr_nms_workspace_bytes": (_i64, [_i, _i]),
     "abr_nms_unsorted_workspace_bytes": (_i64, [_i]),
     "abr_nms": (_i, [_vp, _vp, _i, _f, _i, _vp, _vp, _vp, _i64, _vp]),

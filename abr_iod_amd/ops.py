@@ -83,6 +83,102 @@ def roi_align_taps(rois, H, W, spatial_scale, ph, pw, sampling_ratio, max_s):
     return idx, grid
 
 
+# ----------------------------------------------------------------------------------------------- ROIPool, deformable PS-RoI pooling
+def roi_pool_forward(feat, rois, spatial_scale, ph, pw, out=None):
+    """feat [B,H,W,C], rois [K,5] -> (out [K,ph,pw,C], argmax int32 [K,ph,pw,C]: flat pixel h*W+w of the bin's first maximum, -1 for none);
+    the values are written into `out`, a contiguous tensor of that shape, when given"""
+    L.require_cuda(feat, rois)
+    feat, rois = L.f32c(feat), L.f32c(rois)
+    B, H, W, Ch = feat.shape
+    K = rois.shape[0]
+    if out is None:
+        out = _empty((K, ph, pw, Ch), feat)
+    else:
+        assert tuple(out.shape) == (K, ph, pw, Ch) and out.is_contiguous() and out.dtype == _f32
+    argmax = _empty((K, ph, pw, Ch), feat, torch.int32)
+    L.check(L.lib().abr_roi_pool_forward(L.ptr(feat), L.ptr(rois), K, B, Ch, H, W, float(spatial_scale), ph, pw, L.NHWC, L.ptr(out), L.ptr(argmax),
+                                         L.stream()), "roi_pool_forward")
+    return out, argmax
+
+
+def roi_pool_backward(grad, rois, argmax, B, H, W, out=None):
+    """grad, argmax [K,ph,pw,C] -> grad_feat [B,H,W,C] (fp32 atomics); accumulates into `out` when given"""
+    L.require_cuda(grad, rois, argmax)
+    grad, rois = L.f32c(grad), L.f32c(rois)
+    K, ph, pw, Ch = grad.shape
+    if argmax.dtype != torch.int32 or tuple(argmax.shape) != tuple(grad.shape) or not argmax.is_contiguous():
+        raise RuntimeError(f"roi_pool_backward: argmax must be a contiguous int32 tensor of grad's shape {tuple(grad.shape)}")
+    acc = out is not None
+    if out is None:
+        out = _empty((B, H, W, Ch), grad)
+    else:
+        assert tuple(out.shape) == (B, H, W, Ch) and out.is_contiguous() and out.dtype == _f32
+    L.check(L.lib().abr_roi_pool_backward(L.ptr(grad), L.ptr(rois), L.ptr(argmax), K, B, Ch, H, W, ph, pw, L.NHWC, int(acc), L.ptr(out), L.stream()),
+            "roi_pool_backward")
+    amax_drop(out)
+    return out
+
+
+def _psroi_operands(rois, trans, mask_logits, K, P, part):
+    """(trans, num_classes, mask_logits) as the library takes them: trans [K, 2 num_classes, part, part] or None, mask_logits [K, P, P] or None"""
+    ncls = 1
+    if trans is not None:
+        trans = L.f32c(trans)
+        if trans.dim() != 4 or trans.shape[0] != K or trans.shape[1] % 2 or tuple(trans.shape[2:]) != (part, part):
+            raise RuntimeError(f"deform_psroi: trans {tuple(trans.shape)} is not [{K}, 2 * num_classes, {part}, {part}]")
+        ncls = trans.shape[1] // 2
+    if mask_logits is not None:
+        mask_logits = L.f32c(mask_logits)
+        if mask_logits.numel() != K * P * P:
+            raise RuntimeError(f"deform_psroi: mask_logits {tuple(mask_logits.shape)} is not [{K}, {P}, {P}]")
+    return trans, ncls, mask_logits
+
+
+def deform_psroi_forward(feat, rois, trans, spatial_scale, output_dim, group_size, pooled_size, part_size, sample_per_part, trans_std,
+                         mask_logits=None, out=None):
+    """feat [B,H,W,C], rois [K,5], trans [K, 2 num_classes, part, part] or None (no_trans), mask_logits [K,P,P] or None
+    -> (out [K,P,P,output_dim], top_count of the same shape); out is multiplied by sigmoid(mask_logits) of its bin when they are given.
+    The values are written into `out`, a contiguous tensor of that shape, when given."""
+    L.require_cuda(feat, rois, trans, mask_logits)
+    feat, rois = L.f32c(feat), L.f32c(rois)
+    B, H, W, Ch = feat.shape
+    K, P = rois.shape[0], pooled_size
+    trans, ncls, mask_logits = _psroi_operands(rois, trans, mask_logits, K, P, part_size)
+    if out is None:
+        out = _empty((K, P, P, output_dim), feat)
+    else:
+        assert tuple(out.shape) == (K, P, P, output_dim) and out.is_contiguous() and out.dtype == _f32
+    count = _empty((K, P, P, output_dim), feat)
+    L.check(L.lib().abr_deform_psroi_forward(L.ptr(feat), L.ptr(rois), L.ptr(trans), L.ptr(mask_logits), K, B, Ch, H, W, float(spatial_scale),
+                                             output_dim, group_size, P, part_size, sample_per_part, float(trans_std), ncls, L.NHWC, L.ptr(out),
+                                             L.ptr(count), L.stream()), "deform_psroi_forward")
+    return out, count
+
+
+def deform_psroi_backward(grad, feat, rois, trans, top_count, spatial_scale, output_dim, group_size, pooled_size, part_size, sample_per_part,
+                          trans_std, mask_logits=None, out=None):
+    """-> (grad_feat [B,H,W,C] by fp32 atomics, ADDED into `out` when given; grad_trans like trans or None; grad_mask_logits [K,P,P] or None).
+    The last two are bit-reproducible."""
+    L.require_cuda(grad, feat, rois, trans, top_count, mask_logits)
+    grad, feat, rois, top_count = L.f32c(grad), L.f32c(feat), L.f32c(rois), L.f32c(top_count)
+    B, H, W, Ch = feat.shape
+    K, P = rois.shape[0], pooled_size
+    if tuple(grad.shape) != (K, P, P, output_dim) or tuple(top_count.shape) != tuple(grad.shape):
+        raise RuntimeError(f"deform_psroi_backward: grad {tuple(grad.shape)} / top_count {tuple(top_count.shape)} are not {(K, P, P, output_dim)}")
+    trans, ncls, mask_logits = _psroi_operands(rois, trans, mask_logits, K, P, part_size)
+    if out is None:
+        out = torch.zeros_like(feat)
+    else:
+        assert tuple(out.shape) == (B, H, W, Ch) and out.is_contiguous() and out.dtype == _f32
+    gtrans = torch.empty_like(trans) if trans is not None else None
+    gmask = _empty((K, P, P), feat) if mask_logits is not None else None
+    L.check(L.lib().abr_deform_psroi_backward(L.ptr(grad), L.ptr(feat), L.ptr(rois), L.ptr(trans), L.ptr(mask_logits), L.ptr(top_count), K, B, Ch, H, W,
+                                              float(spatial_scale), output_dim, group_size, P, part_size, sample_per_part, float(trans_std), ncls,
+                                              L.NHWC, L.ptr(out), L.ptr(gtrans), L.ptr(gmask), L.stream()), "deform_psroi_backward")
+    amax_drop(out)
+    return out, gtrans, gmask
+
+
 # ----------------------------------------------------------------------------------------------- NMS
 _nms_ws = {}
 

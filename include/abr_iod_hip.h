@@ -132,6 +132,49 @@ int abr_roi_align_backward_gather(const float* grad, const float* rois, int K, i
 int abr_roi_align_taps(const float* rois, int K, int H, int W, float spatial_scale, int PH, int PW,
                        int sampling_ratio, int max_s, int32_t* idx, int32_t* grid, void* stream);
 
+/* _C.roi_pool_forward(input, rois, spatial_scale, pooled_h, pooled_w) -> (output, argmax)
+ *   csrc/ROIPool.h:10-24 -> csrc/cuda/ROIPool_cuda.cu:16-77,110-150 (there is no CPU implementation).
+ * feat [B,C,H,W] (NCHW) or [B,H,W,C] (NHWC); rois [K,5]; out and argmax [K,C,PH,PW] (NCHW) or [K,PH,PW,C] (NHWC).
+ * argmax is the flat pixel h*W+w of the bin's first maximum in BOTH layouts, -1 for an empty bin (value 0) and for a bin without a
+ * value above -FLT_MAX (value -FLT_MAX).  Bin borders are floor / ceil of fp32 products, as the reference computes them.
+ * Error when K*C*PH*PW or B*C*H*W does not fit int32; no launch when K == 0. */
+int abr_roi_pool_forward(const float* feat, const float* rois, int K, int B, int C, int H, int W, float spatial_scale, int PH, int PW,
+                         int layout, float* out, int32_t* argmax, void* stream);
+
+/* _C.roi_pool_backward(grad, input, rois, argmax, spatial_scale, ph, pw, B, C, H, W)   csrc/ROIPool.h:26-47 -> ROIPool_cuda.cu:79-108,153-195
+ * grad_feat[b, argmax] += grad wherever argmax != -1 (fp32 atomics: the order of the adds varies from run to run).
+ * grad_feat is zero-filled by the callee unless accumulate != 0 (reference: at::zeros, :166). */
+int abr_roi_pool_backward(const float* grad, const float* rois, const int32_t* argmax, int K, int B, int C, int H, int W, int PH, int PW,
+                          int layout, int accumulate, float* grad_feat, void* stream);
+
+/* The float64 instantiations of the reference's dispatch (AT_DISPATCH_FLOATING_TYPES, ROIPool_cuda.cu:134,177): NCHW tensors, the
+ * geometry in double.  grad_feat is zero-filled by the callee. */
+int abr_roi_pool_forward_f64(const double* feat, const double* rois, int K, int B, int C, int H, int W, double spatial_scale, int PH, int PW,
+                             double* out, int32_t* argmax, void* stream);
+int abr_roi_pool_backward_f64(const double* grad, const double* rois, const int32_t* argmax, int K, int B, int C, int H, int W, int PH, int PW,
+                              double* grad_feat, void* stream);
+
+/* _C.deform_psroi_pooling_forward(input, bbox, trans, out, top_count, no_trans, spatial_scale, output_dim, group_size, pooled_size,
+ *                                 part_size, sample_per_part, trans_std)
+ *   csrc/deform_pool.h:11-40 -> csrc/cuda/deform_pool_cuda.cu:33-82 -> deform_pool_kernel_cuda.cu:54-141; float32.
+ * feat [B,C,H,W] / [B,H,W,C] with C >= OD*G*G; rois [K,5]; trans [K,2*num_classes,part,part] in both layouts, NULL = no_trans;
+ * out and top_count [K,OD,P,P] (NCHW) or [K,P,P,OD] (NHWC).
+ * mask_logits [K,P,P] (optional, beyond the reference): out is multiplied by sigmoid(mask_logits) of its bin -- the product that
+ * ModulatedDeformRoIPoolingPack (layers/dcn/deform_pool_module.py:145-150) forms with torch ops. */
+int abr_deform_psroi_forward(const float* feat, const float* rois, const float* trans, const float* mask_logits, int K, int B, int C, int H,
+                             int W, float spatial_scale, int output_dim, int group_size, int pooled_size, int part_size, int sample_per_part,
+                             float trans_std, int num_classes, int layout, float* out, float* top_count, void* stream);
+
+/* _C.deform_psroi_pooling_backward(out_grad, input, bbox, trans, top_count, input_grad, trans_grad, no_trans, ...)
+ *   csrc/deform_pool.h:43-70 -> deform_pool_kernel_cuda.cu:143-264.
+ * grad_feat: fp32 atomics ADDED into the caller's buffer (the reference accumulates into input_grad too).
+ * grad_trans [K,2*num_classes,part,part] (NULL exactly when trans is) and grad_mask_logits [K,P,P] (NULL exactly when mask_logits is)
+ * are WRITTEN, every element by its one owner in a fixed order: no atomics, bit-reproducible. */
+int abr_deform_psroi_backward(const float* out_grad, const float* feat, const float* rois, const float* trans, const float* mask_logits,
+                              const float* top_count, int K, int B, int C, int H, int W, float spatial_scale, int output_dim, int group_size,
+                              int pooled_size, int part_size, int sample_per_part, float trans_std, int num_classes, int layout,
+                              float* grad_feat, float* grad_trans, float* grad_mask_logits, void* stream);
+
 /* _C.nms(dets, scores, threshold)   csrc/nms.h:10-27 -> csrc/cpu/nms_cpu.cpp:5-75 / csrc/cuda/nms.cu:70-131
  * Batched, boxes already sorted by descending score (the reference sorts first: nms_cpu.cpp:24, nms.cu:73).
  *   boxes   [N, n_max, 4] xyxy fp32, image i uses its first counts[i] rows

@@ -28,6 +28,9 @@ def _same(a, b):
 
 
 CASES = [(C, H, W, kind) for C in (4, 64) for (H, W) in ((13, 17), (12, 16), (13, 16), (12, 17)) for kind in ("randn", "tied", "zero", "nan")]
+# maps of one or two pixels a side: every window hangs over the border, and the quads of the last row / column are cut
+CASES += [(C, H, W, kind) for C in (4, 64) for (H, W) in ((1, 1), (1, 2), (2, 1), (2, 2), (3, 3), (1, 7), (7, 1))
+          for kind in ("randn", "tied", "zero", "nan")]
 
 
 @pytest.mark.parametrize("case", CASES, ids=["C{}-{}x{}-{}".format(*c) for c in CASES])

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "abr_iod_hip.h"
+#include "scratch.h"
 
 namespace abr {
 
@@ -87,7 +88,7 @@ __device__ __forceinline__ float block_sum(float v, float* sm) {
 // takes a ticket, and the LAST one to arrive adds all partials up in slot order (strided over its threads, then a fixed tree): the result does
 // not depend on which workgroup finishes last.  Replaces fp32 atomicAdd into the loss scalars / bias gradients, whose summation order -- and
 // with it the last bits -- changed from run to run.  det_ws: per-stream ring of scratch (launches on a stream are ordered; a slot is reused
-// thousands of launches later); .part == nullptr: no memory, the kernels fall back to atomics.
+// thousands of launches later; its memory: scratch.h); .part == nullptr: no memory, the kernels fall back to atomics.
 struct DetWs {
     float* part;
     unsigned* ticket;   // zero on entry, left zero
@@ -144,7 +145,11 @@ int wino_output_transform(const float* M, int B, int H, int W, int N, const floa
                           float* out, hipStream_t st, const AmaxRef* amax = nullptr);
 int wino_outgrad_transform(const float* gy, int B, int H, int W, int N, float* Mg, hipStream_t st, const AmaxRef* amax = nullptr);
 int wino_wgrad_inverse(const float* dU, int N, int C, const float* scale, float* dw, hipStream_t st);
-float* wino_ws(hipStream_t st, size_t floats);
+// Device memory the library owns (scratch.h has the rule; common.hip binds it to HIP): per-stream scratch by slot, nullptr = no memory
+ScratchPool& scratch_pool();
+inline void* scratch(ScratchSlot slot, hipStream_t st, size_t bytes, size_t zero_prefix = 0) { return scratch_pool().scratch(slot, st, bytes, zero_prefix); }
+inline float* wino_ws(hipStream_t st, size_t floats) { return static_cast<float*>(scratch(SCRATCH_WINO, st, floats * sizeof(float))); }
+int num_cus();   // compute units of the device, asked once (256 when it cannot be asked)
 // the cache of data derived from a weight tensor (conv_winograd.hip), keyed by (w, kind) under abr_conv_desc::w_version != 0: `fill(buf)` writes
 // `bytes` on `st` (0 = ok) when (w, version) has not been seen; nullptr = no memory or the fill failed
 enum DerivedKind { DERIVED_NONE = -1, DERIVED_WINO_U = 0, DERIVED_X6_PLANES = 1, DERIVED_WINO_U_X6_PLANES = 2, DERIVED_H3_PLANES = 3, DERIVED_WINO_U_H3_PLANES = 4 };

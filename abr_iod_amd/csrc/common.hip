@@ -202,16 +202,28 @@ extern "C" int abr_prof_event_overhead_ms(double* out_host, void* stream) {
     return ABR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------- library-owned device memory (scratch.h)
 namespace abr {
-unsigned* x6_flags_ptr() {
-    static unsigned* p = nullptr;
-    if (!p) {
-        if (hipMalloc(&p, sizeof(unsigned)) != hipSuccess) return nullptr;
-        (void)hipMemset(p, 0, sizeof(unsigned));
-    }
-    return p;
+ScratchPool& scratch_pool() {
+    static const ScratchBackend hip_backend = {
+        [](size_t bytes) -> void* { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; },
+        [](void* p) { (void)hipFree(p); },
+        [](void* st) { return hipStreamSynchronize(as_stream(st)) == hipSuccess; },
+        [](void* p, size_t bytes, void* st) { return hipMemsetAsync(p, 0, bytes, as_stream(st)) == hipSuccess; },
+    };
+    static ScratchPool* pool = new ScratchPool(hip_backend);   // never destroyed: nothing is freed behind the runtime's back at exit
+    return *pool;
 }
+int num_cus() {
+    static const int n = [] {
+        int32_t info[3];
+        return abr_device_info(info) == ABR_OK ? info[0] : 256;
+    }();
+    return n;
+}
+unsigned* x6_flags_ptr() { return static_cast<unsigned*>(scratch_pool().words(WORDS_X6_FLAGS, sizeof(unsigned))); }
 }  // namespace abr
+extern "C" int64_t abr_scratch_bytes(void) { return abr::scratch_pool().bytes(); }
 extern "C" int abr_x6_range_flags(uint32_t* out_host, int reset, void* stream) {
     ABR_REQUIRE(out_host, "x6_range_flags: null pointer");
     unsigned* p = abr::x6_flags_ptr();
@@ -251,24 +263,16 @@ extern "C" int abr_x6_range_flags_to_device(uint32_t* out_device, void* stream) 
 namespace abr {
 DetWs det_ws(hipStream_t st, size_t nfloats) {
     constexpr size_t kFloats = 1u << 16, kTickets = 4096;
-    struct Ring { float* part = nullptr; unsigned* tick = nullptr; size_t head = 0, thead = 0; };
-    static std::map<hipStream_t, Ring> rings;
-    static std::mutex mu;
-    std::lock_guard<std::mutex> g(mu);
     if (nfloats == 0 || nfloats > kFloats) return DetWs{nullptr, nullptr};
-    Ring& r = rings[st];
-    if (!r.part) {
-        if (hipMalloc(&r.part, kFloats * sizeof(float)) != hipSuccess) { r.part = nullptr; return DetWs{nullptr, nullptr}; }
-        if (hipMalloc(&r.tick, kTickets * sizeof(unsigned)) != hipSuccess) { (void)hipFree(r.part); r.part = nullptr; return DetWs{nullptr, nullptr}; }
-        // zeroed on `st` itself: a plain hipMemset goes to the null stream, which a non-blocking stream's first kernels do not wait for
-        if (hipMemsetAsync(r.tick, 0, kTickets * sizeof(unsigned), st) != hipSuccess) {
-            (void)hipFree(r.tick); (void)hipFree(r.part); r.part = nullptr; r.tick = nullptr; return DetWs{nullptr, nullptr};
-        }
-    }
-    if (r.head + nfloats > kFloats) r.head = 0;
-    DetWs w{r.part + r.head, r.tick + (r.thead++ % kTickets)};
-    r.head += nfloats;
-    return w;
+    return scratch_pool().locked(SCRATCH_DET, st, [&](ScratchPool::Ref e) {
+        char* b = static_cast<char*>(e.ensure((kTickets + kFloats) * 4, kTickets * 4));   // [tickets, zeroed][partials]
+        if (!b) return DetWs{nullptr, nullptr};
+        uint64_t &head = e.words[0], &thead = e.words[1];
+        if (head + nfloats > kFloats) head = 0;
+        DetWs w{reinterpret_cast<float*>(b + kTickets * 4) + head, reinterpret_cast<unsigned*>(b) + (thead++ % kTickets)};
+        head += nfloats;
+        return w;
+    });
 }
 }  // namespace abr
 
@@ -294,13 +298,7 @@ namespace abr {
 static std::mutex g_h3_stats_mu;
 static double g_h3_inspected = 0.0;
 unsigned long long* h3_stats_ptr() {
-    static unsigned long long* p = nullptr;
-    std::lock_guard<std::mutex> g(g_h3_stats_mu);
-    if (!p) {
-        if (hipMalloc(&p, kH3StatSlots * sizeof(unsigned long long)) != hipSuccess) return nullptr;
-        (void)hipMemset(p, 0, kH3StatSlots * sizeof(unsigned long long));
-    }
-    return p;
+    return static_cast<unsigned long long*>(scratch_pool().words(WORDS_H3_STATS, kH3StatSlots * sizeof(unsigned long long)));
 }
 void h3_stats_inspected(double n) {
     std::lock_guard<std::mutex> g(g_h3_stats_mu);
@@ -309,8 +307,8 @@ void h3_stats_inspected(double n) {
 AmaxRef h3_amax_alloc() {
     std::lock_guard<std::mutex> g(g_amax_mu);
     if (!g_amax_ring) {
-        if (hipMalloc(&g_amax_ring, (size_t)ABR_H3_AMAX_RING * 8) != hipSuccess) { g_amax_ring = nullptr; return AmaxRef{nullptr, 0}; }
-        (void)hipMemset(g_amax_ring, 0, (size_t)ABR_H3_AMAX_RING * 8);
+        g_amax_ring = static_cast<unsigned long long*>(scratch_pool().words(WORDS_AMAX_RING, (size_t)ABR_H3_AMAX_RING * 8));
+        if (!g_amax_ring) return AmaxRef{nullptr, 0};
     }
     const uint64_t c = g_amax_count++;
     // epochs grow with every allocation, so a word's later owner always outranks its earlier ones in the 64-bit max (0 is never used: a cleared

@@ -1161,15 +1161,6 @@ __global__ __launch_bounds__(256) void h3_pack_multi_kernel(Src jobs) {
     h3_pack_chunk(jb.src, jb.a, jb.b, lb / jb.gx, (lb % jb.gx) * 64, planes, reinterpret_cast<const float*>(reinterpret_cast<const char*>(planes) + abr::h3_planes_bytes_dev(jb.a, jb.b)));
 }
 
-static int num_cus() {
-    static int n = 0;
-    if (!n) {
-        int32_t info[3];
-        n = abr_device_info(info) == ABR_OK ? info[0] : 256;
-    }
-    return n;
-}
-
 template <int BM, int BN, int WM, int WN, int NP, bool F16 = false>
 int launch_x6w_np(const ConvP& p, const float* x, float* out, hipStream_t st) {
     ConvP q = p;
@@ -1224,20 +1215,8 @@ int launch_x6w(const ConvP& p, const float* x, float* out, hipStream_t st) {
 }
 
 
-// split-K scratch: partial tiles (64 KB each for 128x128) + tickets, one set per stream (streams may run convs concurrently)
-struct SplitWs { float* ws = nullptr; int* cnt = nullptr; };
-static SplitWs* split_ws(hipStream_t st) {
-    static std::map<hipStream_t, SplitWs> pool;   // node-based: the returned pointer stays valid; the mutex covers first-use insertion from
-    static std::mutex mu;                           // concurrent host threads (forward on the Python thread, backward on autograd's; ctypes drops the GIL)
-    std::lock_guard<std::mutex> g(mu);
-    SplitWs& w = pool[st];
-    if (!w.ws) {
-        if (hipMalloc(&w.ws, (size_t)kMaxSplitUnits * 128 * 128 * sizeof(float)) != hipSuccess) return nullptr;
-        if (hipMalloc(&w.cnt, kMaxSplitTiles * sizeof(int)) != hipSuccess) return nullptr;
-        if (hipMemset(w.cnt, 0, kMaxSplitTiles * sizeof(int)) != hipSuccess) return nullptr;
-    }
-    return &w;
-}
+// split-K scratch of a stream: [tickets, zeroed][partial tiles (64 KB each for 128x128)]
+constexpr size_t kSplitTicketBytes = kMaxSplitTiles * sizeof(int), kSplitBytes = kSplitTicketBytes + (size_t)kMaxSplitUnits * 128 * 128 * sizeof(float);
 
 template <int BM, int BN, int WM, int WN, bool SMALL_C, bool SB = false>
 int launch(const ConvP& p, const float* x, const float* w, float* out, hipStream_t st, int prof_id, int n_full = -1, int split = 1) {
@@ -1252,8 +1231,8 @@ int launch(const ConvP& p, const float* x, const float* w, float* out, hipStream
     q.ws = nullptr; q.cnt = nullptr;
     const int n_split = tiles - q.n_full;
     if (n_split > 0) {
-        SplitWs* sw = (n_split * q.split <= kMaxSplitUnits && n_split <= kMaxSplitTiles) ? split_ws(st) : nullptr;
-        if (sw) { q.ws = sw->ws; q.cnt = sw->cnt; }
+        char* sw = (n_split * q.split <= kMaxSplitUnits && n_split <= kMaxSplitTiles) ? static_cast<char*>(abr::scratch(abr::SCRATCH_SPLIT, st, kSplitBytes, kSplitTicketBytes)) : nullptr;
+        if (sw) { q.cnt = reinterpret_cast<int*>(sw); q.ws = reinterpret_cast<float*>(sw + kSplitTicketBytes); }
         else { q.n_full = tiles; q.split = 1; }  // no scratch: plain launch
     }
     constexpr size_t lds_op = sizeof(float) * (SB ? 1 : 2) * (BM + BN) * LDP;
@@ -1378,7 +1357,7 @@ static void dispatch_igemm(const ConvP& p, const float* x, const float* w, float
     // tile choice: biggest tile that still gives >= 2 workgroups per CU; narrow-N layers use BN=64
     const int64_t t128 = (int64_t)((p.M + 127) / 128) * ((p.Cout + 127) / 128) * nb;
     const int64_t t12864 = (int64_t)((p.M + 127) / 128) * ((p.Cout + 63) / 64) * nb;
-    const int cus = num_cus();
+    const int cus = abr::num_cus();
     // ---- split-K plan for the 128x128 tile (see ConvP::n_full).  Per-CU cost model in k-iterations: workgroups on one CU share
     // its MFMA pipe, so a grid costs ceil(tiles / CUs) tile-times; splitting the LAST tiles (or all of them when there are fewer
     // tiles than CUs) by s evens the rounds out at the price of the partial-sum round trip per unit.
@@ -1441,7 +1420,7 @@ static void dispatch_igemm(const ConvP& p, const float* x, const float* w, float
 // The split arithmetics (bf16x6, f16x3, and bf16 / f16 as their one-product forms): tile choice + launch.  p.w_planes -- the caller's, the
 // library's per-version cache, or planes packed into stream scratch for a one-off call -- is never null here: the weights-direct kernel is the only one.
 static void dispatch_igemm_x6(const ConvP& p, const float* x, const float* /*w*/, float* out, hipStream_t st) {
-    const int cus = num_cus();
+    const int cus = abr::num_cus();
     const int64_t nb = p.nbatch > 1 ? p.nbatch : 1;
     const int64_t t128 = (int64_t)((p.M + 127) / 128) * ((p.Cout + 127) / 128) * nb;
     const int64_t t12864 = (int64_t)((p.M + 127) / 128) * ((p.Cout + 63) / 64) * nb;
@@ -1498,7 +1477,7 @@ ConvRoute conv_route(const abr_conv_desc& d) {
 
 static bool wino_split_kind(int kind) { return kind == abr::DERIVED_WINO_U_X6_PLANES || kind == abr::DERIVED_WINO_U_H3_PLANES; }
 
-// Job tables of the launches with several jobs: a RING of pinned host staging + device slots per stream.  A call takes the next njobs slots; a region is
+// Job tables of the launches with several jobs: a RING of pinned host staging + device slots (SCRATCH_PREP_RING) per stream.  A call takes the next njobs slots; a region is
 // reused only after the upload that last used it has completed -- thousands of jobs (tens of optimiser steps) later, so the host never waits for
 // the stream (a single staging buffer made every call wait for the previous call's upload, which sits behind the whole backward pass).
 namespace {
@@ -1509,17 +1488,17 @@ struct PrepTables {
     size_t head = 0;                                   // next free slot
     std::vector<std::pair<size_t, hipEvent_t>> inflight;   // (end slot of a past call's region, its upload event), oldest first
     size_t inflight_begin = 0;                         // first slot still covered by `inflight`
-    float* u_scratch = nullptr;   // abr_conv_prepare_batch's fp32 Winograd-domain weights on their way to being packed
-    size_t u_floats = 0;
 };
 std::map<hipStream_t, PrepTables> g_prep_tables;
 std::mutex g_prep_mu;
 
 // slots [*first, *first + n) of the ring, free of any upload still in flight
-bool prep_ring_take(PrepTables& T, size_t n, size_t* first) {
+bool prep_ring_take(PrepTables& T, hipStream_t st, size_t n, size_t* first) {
     if (n > kPrepRing) return false;
-    if (!T.host) {
-        if (hipHostMalloc(&T.host, kPrepRing * sizeof(abr::PrepJob)) != hipSuccess || hipMalloc(&T.dev, kPrepRing * sizeof(abr::PrepJob)) != hipSuccess) return false;
+    if (!T.host) {   // both halves or neither: the pool keeps a device half whose host half failed, and hands it out again on the next try
+        void* dev = abr::scratch(abr::SCRATCH_PREP_RING, st, kPrepRing * sizeof(abr::PrepJob));
+        if (!dev || hipHostMalloc(&T.host, kPrepRing * sizeof(abr::PrepJob)) != hipSuccess) { T.host = nullptr; return false; }
+        T.dev = static_cast<abr::PrepJob*>(dev);
     }
     if (T.head + n > kPrepRing) {   // wrap: everything recorded so far must be done before slot 0 is written again
         for (auto& pr : T.inflight) { (void)hipEventSynchronize(pr.second); (void)hipEventDestroy(pr.second); }
@@ -1606,7 +1585,7 @@ const char* prep_launch(PrepPlan& p, float* u, hipStream_t st, PrepTables* T = n
     }
     if (njobs) {
         size_t first = 0;
-        if (!T || !prep_ring_take(*T, njobs, &first)) return "no memory for the job tables";
+        if (!T || !prep_ring_take(*T, st, njobs, &first)) return "no memory for the job tables";
         for (int k = 0, at = 0; k < PREP_KINDS; k++)
             if (src[k].n > 1) {
                 std::copy(p.jobs[k].begin(), p.jobs[k].end(), T->host + first + at);
@@ -1898,12 +1877,9 @@ extern "C" int abr_conv_prepare_batch(const abr_prep_item* items, int n, void* s
                         "conv_prepare_batch: no memory for the derived weights");
         }
     }
-    if (T.u_floats < plan.u_floats) {
-        if (T.u_scratch) { (void)hipStreamSynchronize(st); (void)hipFree(T.u_scratch); T.u_scratch = nullptr; T.u_floats = 0; }
-        ABR_REQUIRE(hipMalloc(&T.u_scratch, plan.u_floats * sizeof(float)) == hipSuccess, "conv_prepare_batch: no memory for the Winograd-domain scratch");
-        T.u_floats = plan.u_floats;
-    }
-    const char* err = prep_launch(plan, T.u_scratch, st, &T);
+    float* u = plan.u_floats ? static_cast<float*>(abr::scratch(abr::SCRATCH_PREP_U, st, plan.u_floats * sizeof(float))) : nullptr;
+    ABR_REQUIRE(!plan.u_floats || u, "conv_prepare_batch: no memory for the Winograd-domain scratch");
+    const char* err = prep_launch(plan, u, st, &T);
     ABR_REQUIRE(!err, "conv_prepare_batch: %s", err);
     ABR_REQUIRE(hipGetLastError() == hipSuccess, "conv_prepare_batch: launch failed");
     abr::derived_commit(tokens.data(), (int)tokens.size(), st);
@@ -1968,16 +1944,7 @@ extern "C" int abr_bias_grad(const float* gy, int64_t M, int C, float* db, void*
     dim3 grid((C + 63) / 64, (unsigned)((M + rows_per_block - 1) / rows_per_block));
     // scratch: 64 floats per workgroup + one ticket per column chunk (the ring's ticket array serves as the ticket block: column chunks <= 64 here)
     abr::DetWs ws = grid.x <= 64 ? abr::det_ws(abr::as_stream(stream), (size_t)grid.x * grid.y * 64) : abr::DetWs{nullptr, nullptr};
-    static std::map<hipStream_t, unsigned*> tick;
-    static std::mutex tick_mu;
-    unsigned* tk = nullptr;
-    if (ws.part) {
-        std::lock_guard<std::mutex> g(tick_mu);
-        unsigned*& t = tick[abr::as_stream(stream)];
-        // (zeroed on the launch stream, as det_ws does: a non-blocking stream does not wait for a null-stream hipMemset)
-        if (!t && (hipMalloc(&t, 64 * sizeof(unsigned)) != hipSuccess || hipMemsetAsync(t, 0, 64 * sizeof(unsigned), abr::as_stream(stream)) != hipSuccess)) t = nullptr;
-        tk = t;
-    }
+    unsigned* tk = ws.part ? static_cast<unsigned*>(abr::scratch(abr::SCRATCH_BIAS_TICKETS, abr::as_stream(stream), 64 * sizeof(unsigned), 64 * sizeof(unsigned))) : nullptr;
     bias_grad_kernel<<<grid, 256, 0, abr::as_stream(stream)>>>(gy, M, C, rows_per_block, db, tk ? ws.part : nullptr, tk);
     ABR_CHECK_LAUNCH("bias_grad");
     return ABR_OK;

@@ -22,9 +22,6 @@
 // conv_winograd.hip).
 #include <algorithm>
 
-#include <map>
-#include <mutex>
-
 #include "common.h"
 
 namespace {
@@ -556,26 +553,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 
 }  // namespace
 
-// scratch of the partial-sum reduction: `units` partial tiles of 64 KB, grow-only, one buffer per stream (launches on a stream are ordered)
-static float* wgrad_scratch(hipStream_t st, size_t units) {
-    struct Ws { float* ws = nullptr; size_t units = 0; };
-    static std::map<hipStream_t, Ws> pool;
-    static std::mutex mu;   // host threads may issue weight gradients for different streams concurrently
-    std::lock_guard<std::mutex> g(mu);
-    Ws& w = pool[st];
-    if (w.units < units) {
-        if (w.ws) { (void)hipStreamSynchronize(st); (void)hipFree(w.ws); w.ws = nullptr; w.units = 0; }
-        if (hipMalloc(&w.ws, units * 65536) != hipSuccess) return nullptr;
-        w.units = units;
-    }
-    return w.ws;
-}
-
 // fills p.ws for a split launch (left null -> the kernel falls back to atomics; the caller must then have zeroed a final_store dw)
 static void wgrad_plan_reduction(WgP& p, int tiles, hipStream_t st) {
     p.ws = nullptr;
     if (p.splits <= 1) { if (p.final_store) p.overwrite = 1; return; }
-    p.ws = wgrad_scratch(st, (size_t)tiles * p.splits);
+    p.ws = static_cast<float*>(abr::scratch(abr::SCRATCH_WGRAD, st, (size_t)tiles * p.splits * 65536));   // partial tiles of 64 KB
 }
 
 static void wgrad_reduce(const WgP& p, int tiles, float* dw, hipStream_t st) {
@@ -587,8 +569,7 @@ static void launch_wgrad(WgP p, const float* x, const float* gy, float* dw, void
     const int nb = p.nbatch > 1 ? p.nbatch : 1;
     p.tiles_pb = p.tiles_n * p.tiles_k;
     const int m_tiles = (p.M + MR - 1) / MR;
-    int32_t info[3];
-    const int cus = abr_device_info(info) == ABR_OK ? info[0] : 256;
+    const int cus = abr::num_cus();
     const int tiles = p.tiles_n * p.tiles_k * nb;
     // split-M so that the grid fills the chip evenly: among the candidates pick the one with the best load balance
     // (workgroups / (ceil(workgroups / CUs) * CUs)), preferring fewer splits (less atomic traffic) on ties; every
@@ -720,8 +701,7 @@ extern "C" int abr_conv_wgrad(const abr_conv_desc* d, const float* x, const floa
             // enough output tiles to fill the chip without splitting the tile axis -> each workgroup owns its dU tile and writes
             // it directly; otherwise split-M, whose partial sums go through the reduction kernel, which STORES the tile: no zero-fill
             // of dU (launch_wgrad zero-fills dU itself when it has to fall back to atomics)
-            int32_t info[3];
-            const int cus_ = abr_device_info(info) == ABR_OK ? info[0] : 256;
+            const int cus_ = abr::num_cus();
             const long out_tiles = 36L * ((d->Cout + TN_ - 1) / TN_) * ((d->Cin + TK_ - 1) / TK_);
             const int own = out_tiles >= 2L * cus_;
             if (!bad) {

@@ -592,21 +592,6 @@ int wino_wgrad_inverse(const float* dU, int N, int C, const float* scale, float*
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-// Winograd scratch, one grow-only allocation per stream (forward / dgrad run on the main stream, weight gradients on the side one)
-float* wino_ws(hipStream_t st, size_t floats) {
-    struct Ws { float* buf = nullptr; size_t floats = 0; };
-    static std::map<hipStream_t, Ws> pool;
-    static std::mutex mu;   // host threads may run Winograd convs for different streams concurrently
-    std::lock_guard<std::mutex> g(mu);
-    Ws& w = pool[st];
-    if (w.floats < floats) {
-        if (w.buf) { (void)hipStreamSynchronize(st); (void)hipFree(w.buf); w.buf = nullptr; w.floats = 0; }
-        if (hipMalloc(&w.buf, floats * sizeof(float)) != hipSuccess) return nullptr;
-        w.floats = floats;
-    }
-    return w.buf;
-}
-
 // Data DERIVED from a weight tensor, kept per (weight address, kind) under abr_conv_desc::w_version: the Winograd-domain weights U (fp32,
 // for the fp32 MFMA kernels), the fragment-packed bf16x3 planes of a weight matrix, and the packed planes of U (both for the bf16x6
 // weights-direct kernel).  One entry per (address, kind); a new version refills the same buffer.  Ordering: a hit from a stream other than

@@ -10,8 +10,6 @@
 // the result orders by descending score, equal scores by ascending index, and the first k are written out as fp32 scores + int64 indices.
 // Scores are non-negative floats, so their bit patterns order like the values.
 #include <algorithm>
-#include <map>
-#include <mutex>
 
 #include "common.h"
 
@@ -318,36 +316,29 @@ static int topk_run(const float* logits, int64_t img_stride, int N, int n, int A
     //   [level-1 histograms: cap_imgs x 4096][counters: cap_imgs][survivors: cap_imgs x CAP words][keys: cap_keys][candidates: cap_keys words]
     // The histogram and counter regions are zero on entry (allocation zero-fills them, the select phase cleans what it used); their position does not
     // depend on n or N, so a later call with a smaller feature map / another batch size never finds stale key bits where it expects zeros.
-    // Grow-only: keyed on capacity, not on N ==.
-    struct Ws { void* p = nullptr; int cap_imgs = 0; size_t cap_keys = 0; };
-    static std::mutex mu;
-    static std::map<hipStream_t, Ws> pool;
+    // Grow-only: keyed on capacity, not on N ==.  The capacities (images, keys) are the entry's two words; the bytes they ask for grow with
+    // either, so a request within both fits and touches nothing.
     hipStream_t st = abr::as_stream(stream);
     unsigned* keys;
     int* hist;
     TopkCnt* cnt;
     unsigned long long *surv, *cand;
-    {
-        std::lock_guard<std::mutex> g(mu);
-        Ws& w = pool[st];
-        const size_t need_keys = (size_t)N * n;
-        if (w.cap_imgs < N || w.cap_keys < need_keys) {
-            const int imgs = std::max(std::max(N, w.cap_imgs), 8);
-            const size_t nkeys = std::max(need_keys, w.cap_keys);
-            if (w.p) { (void)hipStreamSynchronize(st); (void)hipFree(w.p); w.p = nullptr; w.cap_imgs = 0; w.cap_keys = 0; }
-            const size_t head = (size_t)imgs * HB * 4 + (size_t)imgs * sizeof(TopkCnt);
-            ABR_REQUIRE(hipMalloc(&w.p, head + (size_t)imgs * CAP * 8 + nkeys * 4 + nkeys * 8 + 16) == hipSuccess, "topk_sigmoid: scratch allocation failed");
-            w.cap_imgs = imgs;
-            w.cap_keys = nkeys;
-            (void)hipMemsetAsync(w.p, 0, head, st);
-        }
-        char* b = static_cast<char*>(w.p);
-        hist = reinterpret_cast<int*>(b);                          b += (size_t)w.cap_imgs * HB * 4;
-        cnt = reinterpret_cast<TopkCnt*>(b);                       b += (size_t)w.cap_imgs * sizeof(TopkCnt);
-        surv = reinterpret_cast<unsigned long long*>(b);           b += (size_t)w.cap_imgs * CAP * 8;
-        cand = reinterpret_cast<unsigned long long*>(b);           b += w.cap_keys * 8;
+    const bool have = abr::scratch_pool().locked(abr::SCRATCH_TOPK, st, [&](abr::ScratchPool::Ref w) {
+        const size_t imgs = std::max<size_t>(std::max<size_t>((size_t)N, w.words[0]), 8);
+        const size_t nkeys = std::max<size_t>((size_t)N * n, w.words[1]);
+        const size_t head = imgs * HB * 4 + imgs * sizeof(TopkCnt);
+        char* b = static_cast<char*>(w.ensure(head + imgs * CAP * 8 + nkeys * 4 + nkeys * 8 + 16, head));
+        if (!b) return false;
+        w.words[0] = imgs;
+        w.words[1] = nkeys;
+        hist = reinterpret_cast<int*>(b);                          b += imgs * HB * 4;
+        cnt = reinterpret_cast<TopkCnt*>(b);                       b += imgs * sizeof(TopkCnt);
+        surv = reinterpret_cast<unsigned long long*>(b);           b += imgs * CAP * 8;
+        cand = reinterpret_cast<unsigned long long*>(b);           b += nkeys * 8;
         keys = reinterpret_cast<unsigned*>(b);
-    }
+        return true;
+    });
+    ABR_REQUIRE(have, "topk_sigmoid: scratch allocation failed");
     const unsigned slices = (unsigned)((n + per - 1) / per);
     topk_keys_kernel<<<dim3(slices, (unsigned)N), KT, 0, st>>>(logits, img_stride, n, A, ld, per, keys, hist, raw);
     topk_partition_kernel<<<dim3(slices, (unsigned)N), KT, lds_part, st>>>(keys, hist, n, k, per, surv, cand, cnt);

@@ -742,6 +742,11 @@ def conv_cache_bytes():
     return int(L.lib().abr_conv_cache_bytes())
 
 
+def scratch_bytes():
+    """Bytes of the library's own per-stream scratch and process-wide words (not the derived-weight cache)."""
+    return int(L.lib().abr_scratch_bytes())
+
+
 def conv_wgrad(x, gy, dw, stride=1, pad=0, scale=None, math=MATH_F32, wino_v=None, amax_refs=None, stream=None):
     """dw [Cout,R,S,Cin] += scale * gy^T im2col(x) (fp32 atomics; caller zeroes dw once per step).  MATH_F16X3 / MATH_F16: the amax words of x and
     gy come from their tags (else the library reduces the operand first); amax_refs = ((word, epoch) of x, of gy) taken by the caller on

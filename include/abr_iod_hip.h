@@ -417,6 +417,9 @@ int abr_conv_cache_clear(void);
  * entries whose fill is in progress on another thread. */
 int abr_conv_cache_drop_range(const void* base, int64_t bytes);
 int64_t abr_conv_cache_bytes(void);
+/* bytes of the device memory the library owns besides that cache: its per-stream scratch (grow-only, one buffer per user and stream) and its
+ * process-wide words (range flags, f16x3 statistics, the amax ring).  DESIGN.md, "Library-owned scratch". */
+int64_t abr_scratch_bytes(void);
 /* floats of the Winograd-domain input V = 36 * B*ceil(H/4)*ceil(W/4) * Cin if BOTH abr_conv_forward and abr_conv_wgrad take the
  * Winograd F(4x4,3x3) path for this descriptor (wide stride-1 pad-1 3x3, no residual / scatter; fp32 math, or bf16x6 / f16x3 with
  * Cout % 32 == 0), else 0 */

@@ -13,9 +13,22 @@ tensor layouts (NCHW fp32), return types and error behaviour — backed by libab
                                  part_size, sample_per_part, trans_std)             csrc/deform_pool.h:11-40   (writes out, top_count)
     deform_psroi_pooling_backward(out_grad, input, bbox, trans, top_count, input_grad, trans_grad, no_trans, ...)  :43-70
                                                                           (adds into input_grad, writes trans_grad)
+    deform_conv_forward(input, weight, offset, output, columns, ones, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group,
+                        deformable_group, im2col_step)                              csrc/deform_conv.h:11-42   (writes output)
+    deform_conv_backward_input(input, offset, gradOutput, gradInput, gradOffset, weight, columns, kW, ...)       :45-77
+                                                                          (writes gradInput, gradOffset)
+    deform_conv_backward_parameters(input, offset, gradOutput, gradWeight, columns, ones, kW, ..., scale, im2col_step)   :80-112
+                                                                          (adds scale * gradient into gradWeight)
+    modulated_deform_conv_forward(input, weight, bias, ones, offset, mask, output, columns, kernel_h, kernel_w, stride_h, stride_w,
+                                  pad_h, pad_w, dilation_h, dilation_w, group, deformable_group, with_bias)      :115-149  (writes output)
+    modulated_deform_conv_backward(input, weight, bias, ones, offset, mask, columns, grad_input, grad_weight, grad_bias, grad_offset,
+                                   grad_mask, grad_output, kernel_h, ...)            :152-191
+                                                      (adds into grad_weight, grad_bias; writes grad_input, grad_offset, grad_mask)
 
-The RoI poolers take float32 and float64 like the reference's dispatch, the deformable pair float32 only; anything else raises
-RuntimeError naming the dtype.  deform_conv_* / modulated_deform_conv_* are not carried (the body's DCN runs specialised kernels).
+The RoI poolers take float32 and float64 like the reference's dispatch, the deformable pooling pair and the deformable convolutions
+float32 only; anything else raises RuntimeError naming the dtype.  The deformable convolutions run the general kernels of csrc/deform.hip
+(abr_deform_im2col_general, abr_deform_col2im_coord_general) around the library's 1x1 contraction; their scratch arguments (columns, ones)
+are accepted and ignored, and the shape checks of deform_conv_cuda.cu raise with its wording.  The body's DCN keeps its specialised kernels.
 
 CPU tensors raise RuntimeError (the reference raises "Not compiled with GPU support" the other way round):
 this library is MI355X-only by design; the CPU restatement lives in oracle/ and is test infrastructure.
@@ -23,6 +36,7 @@ this library is MI355X-only by design; the CPU restatement lives in oracle/ and 
 import torch
 
 from . import _lib as L
+from . import ops
 
 # NMS comparison rule.  The reference is inconsistent: CPU suppresses at IoU >= thr (nms_cpu.cpp:60),
 # CUDA at IoU > thr (nms.cu:60).  The CPU path is the parity oracle, so '>=' is the default here.
@@ -233,3 +247,186 @@ def deform_psroi_pooling_backward(out_grad, input, bbox, trans, top_count, input
     L.check(L.lib().abr_deform_psroi_backward(L.ptr(out_grad), L.ptr(input), L.ptr(r), L.ptr(t), None, L.ptr(top_count), r.shape[0], B, Ch, H, W,
                                               float(spatial_scale), output_dim, group_size, pooled_size, part_size, sample_per_part, float(trans_std),
                                               ncls, L.NCHW, L.ptr(input_grad), L.ptr(gt), None, L.stream()), name)
+
+
+# ------------------------------------------------------------------------------------------- deformable convolutions (csrc/deform_conv.h)
+def _deform_shape_check(input, offset, grad_output, weight, kH, kW, dH, dW, padH, padW, dilationH, dilationW, group, deformable_group):
+    """shape_check of deform_conv_cuda.cu:70-159, in its order and with its wording -> (outputHeight, outputWidth)"""
+    if weight.dim() != 4:
+        raise RuntimeError(f"4D weight tensor (nOutputPlane,nInputPlane,kH,kW) expected, but got: {weight.dim()}")
+    if not weight.is_contiguous():
+        raise RuntimeError("weight tensor has to be contiguous")
+    if not (kW > 0 and kH > 0):
+        raise RuntimeError(f"kernel size should be greater than zero, but got kH: {kH} kW: {kW}")
+    if not (weight.size(2) == kH and weight.size(3) == kW):
+        raise RuntimeError("kernel size should be consistent with weight, "
+                           f"but got kH: {kH} kW: {kW} weight.size(2): {weight.size(2)}, weight.size(3): {weight.size(3)}")
+    if not (dW > 0 and dH > 0):
+        raise RuntimeError(f"stride should be greater than zero, but got dH: {dH} dW: {dW}")
+    if not (dilationW > 0 and dilationH > 0):
+        raise RuntimeError(f"dilation should be greater than 0, but got dilationH: {dilationH} dilationW: {dilationW}")
+    if input.dim() != 4:   # (the reference also takes an unbatched 3D input and adds the batch dimension; this library does not)
+        raise RuntimeError(f"3D or 4D input tensor expected but got: {input.dim()}")
+    nInputPlane = weight.size(1) * group
+    inputHeight, inputWidth = input.size(2), input.size(3)
+    nOutputPlane = weight.size(0)
+    outputHeight = (inputHeight + 2 * padH - (dilationH * (kH - 1) + 1)) // dH + 1
+    outputWidth = (inputWidth + 2 * padW - (dilationW * (kW - 1) + 1)) // dW + 1
+    if nInputPlane % deformable_group != 0:
+        raise RuntimeError("input channels must divide deformable group size")
+    if outputWidth < 1 or outputHeight < 1:
+        raise RuntimeError(f"Given input size: ({nInputPlane} x {inputHeight} x {inputWidth}). "
+                           f"Calculated output size: ({nOutputPlane} x {outputHeight} x {outputWidth}). Output size is too small")
+    if input.size(1) != nInputPlane:
+        raise RuntimeError(f"invalid number of input planes, expected: {nInputPlane}, but got: {input.size(1)}")
+    if not (inputHeight >= kH and inputWidth >= kW):
+        raise RuntimeError("input image is smaller than kernel")
+    if not (offset.size(2) == outputHeight and offset.size(3) == outputWidth):
+        raise RuntimeError(f"invalid spatial size of offset, expected height: {outputHeight} width: {outputWidth}, but "
+                           f"got height: {offset.size(2)} width: {offset.size(3)}")
+    if offset.size(1) != deformable_group * 2 * kH * kW:
+        raise RuntimeError("invalid number of channels of offset")
+    if grad_output is not None:
+        if grad_output.size(1) != nOutputPlane:
+            raise RuntimeError(f"invalid number of gradOutput planes, expected: {nOutputPlane}, but got: {grad_output.size(1)}")
+        if not (grad_output.size(2) == outputHeight and grad_output.size(3) == outputWidth):
+            raise RuntimeError(f"invalid size of gradOutput, expected height: {outputHeight} width: {outputWidth} , but "
+                               f"got height: {grad_output.size(2)} width: {grad_output.size(3)}")
+    if offset.size(0) != input.size(0):
+        raise RuntimeError("invalid batch size of offset")   # deform_conv_cuda.cu:203
+    return outputHeight, outputWidth
+
+
+def _deform_written(name, what, t, shape):
+    """a tensor one of these entry points writes: float32, on the device, contiguous NCHW of the expected shape (the reference views it)"""
+    L.require_cuda(t)
+    _f32_only(name, t)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError(f"{name}: {what} must be a contiguous {tuple(shape)} tensor, got {tuple(t.shape)}")
+
+
+def _deform_nhwc(*tensors):
+    return [None if t is None else ops.nchw_to_nhwc(t.contiguous()) for t in tensors]
+
+
+def _deform_v1_args(name, input, offset, grad_output, weight, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group,
+                    im2col_step):
+    present = [t for t in (input, offset, grad_output, weight) if t is not None]
+    L.require_cuda(*present)
+    _f32_only(name, *present)
+    _deform_shape_check(input, offset, grad_output, weight, kH, kW, dH, dW, padH, padW, dilationH, dilationW, group, deformable_group)
+    if input.size(0) % im2col_step != 0:
+        raise RuntimeError(f"{name}: im2col_step {im2col_step} does not divide the batch size {input.size(0)}")
+    return dict(kernel=(kH, kW), stride=(dH, dW), padding=(padH, padW), dilation=(dilationH, dilationW), groups=group, dg=deformable_group)
+
+
+def deform_conv_forward(input, weight, offset, output, columns, ones, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group,
+                        deformable_group, im2col_step):
+    """writes output [B, Cout, Ho, Wo]; columns and ones (the reference's scratch) are accepted and ignored; float32 only"""
+    name = "deform_conv_forward"
+    g = _deform_v1_args(name, input, offset, None, weight, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group, im2col_step)
+    Ho, Wo = offset.size(2), offset.size(3)
+    _deform_written(name, "output", output, (input.size(0), weight.size(0), Ho, Wo))
+    x, off, w = _deform_nhwc(input, offset, weight)
+    y, _ = ops.deform_conv_forward(x, off, None, w, None, **g)
+    L.check(L.lib().abr_nhwc_to_nchw(L.ptr(y), y.shape[0], y.shape[3], Ho, Wo, L.ptr(output), L.stream()), name)
+    return 1
+
+
+def deform_conv_backward_input(input, offset, gradOutput, gradInput, gradOffset, weight, columns, kW, kH, dW, dH, padW, padH, dilationW,
+                               dilationH, group, deformable_group, im2col_step):
+    """writes gradInput (like input) and gradOffset (like offset); float32 only"""
+    name = "deform_conv_backward_input"
+    g = _deform_v1_args(name, input, offset, gradOutput, weight, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group,
+                        im2col_step)
+    _deform_written(name, "gradInput", gradInput, input.shape)
+    _deform_written(name, "gradOffset", gradOffset, offset.shape)
+    x, off, gy, w = _deform_nhwc(input, offset, gradOutput, weight)
+    cols = ops.deform_im2col_general(x, off, None, **g)
+    dx, d_off, _, _, _ = ops.deform_conv_backward(gy, x, off, None, w, cols, need_input=True, need_weight=False, **g)
+    B, Ch, H, W = input.shape
+    L.check(L.lib().abr_nhwc_to_nchw(L.ptr(dx), B, Ch, H, W, L.ptr(gradInput), L.stream()), name)
+    L.check(L.lib().abr_nhwc_to_nchw(L.ptr(d_off), B, offset.size(1), offset.size(2), offset.size(3), L.ptr(gradOffset), L.stream()), name)
+    return 1
+
+
+def _deform_add_weight_grad(name, grad_weight, dw, scale):
+    """grad_weight [Cout, C/groups, kh, kw] += scale * dw (OHWI)"""
+    g = ops.nhwc_to_nchw(dw)
+    if scale != 1:
+        ops.scale_(g, float(scale))
+    ops.add_(grad_weight, g)
+
+
+def deform_conv_backward_parameters(input, offset, gradOutput, gradWeight, columns, ones, kW, kH, dW, dH, padW, padH, dilationW, dilationH,
+                                    group, deformable_group, scale, im2col_step):
+    """ADDS scale times the weight gradient into gradWeight (like weight, which it stands for in the shape check); float32 only"""
+    name = "deform_conv_backward_parameters"
+    g = _deform_v1_args(name, input, offset, gradOutput, gradWeight, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group,
+                        im2col_step)
+    x, off, gy = _deform_nhwc(input, offset, gradOutput)
+    cols = ops.deform_im2col_general(x, off, None, **g)
+    w = gradWeight.new_zeros((gradWeight.size(0), kH, kW, gradWeight.size(1)))     # (the weight's values play no part in its gradient)
+    _, _, _, dw, _ = ops.deform_conv_backward(gy, x, off, None, w, cols, need_input=False, need_weight=True, **g)
+    _deform_add_weight_grad(name, gradWeight, dw, scale)
+    return 1
+
+
+def _deform_v2_args(name, input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                    deformable_group, with_bias, more=()):
+    tensors = [input, weight, offset, mask] + ([bias] if with_bias else []) + list(more)
+    L.require_cuda(*tensors)
+    _f32_only(name, *tensors)
+    if not input.is_contiguous():
+        raise RuntimeError("input tensor has to be contiguous")    # deform_conv_cuda.cu:507
+    if not weight.is_contiguous():
+        raise RuntimeError("weight tensor has to be contiguous")   # :508
+    if weight.size(2) != kernel_h or weight.size(3) != kernel_w:   # :520-522 (its own argument order)
+        raise RuntimeError(f"Input shape and kernel shape wont match: ({weight.size(2)} x {kernel_w} vs {weight.size(2)} x {weight.size(3)}).")
+    if input.size(1) != weight.size(1) * group:                    # :523-525
+        raise RuntimeError(f"Input shape and kernel channels wont match: ({input.size(1)} vs {weight.size(1) * group}).")
+    geom = dict(kernel=(kernel_h, kernel_w), stride=(stride_h, stride_w), padding=(pad_h, pad_w), dilation=(dilation_h, dilation_w))
+    Ho, Wo = ops.deform_out_size(input.size(2), input.size(3), **geom)
+    B, K = input.size(0), kernel_h * kernel_w
+    if tuple(offset.shape) != (B, deformable_group * 2 * K, Ho, Wo):
+        raise RuntimeError(f"{name}: offset {tuple(offset.shape)} is not {(B, deformable_group * 2 * K, Ho, Wo)}")
+    if tuple(mask.shape) != (B, deformable_group * K, Ho, Wo):
+        raise RuntimeError(f"{name}: mask {tuple(mask.shape)} is not {(B, deformable_group * K, Ho, Wo)}")
+    if with_bias and tuple(bias.shape) != (weight.size(0),):
+        raise RuntimeError(f"{name}: bias {tuple(bias.shape)} is not {(weight.size(0),)}")
+    geom.update(groups=group, dg=deformable_group)
+    return geom, (B, weight.size(0), Ho, Wo)
+
+
+def modulated_deform_conv_forward(input, weight, bias, ones, offset, mask, output, columns, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                                  dilation_h, dilation_w, group, deformable_group, with_bias):
+    """writes output [B, Cout, Ho, Wo]; ones and columns are accepted and ignored, and so is bias unless with_bias; float32 only"""
+    name = "modulated_deform_conv_forward"
+    g, out_shape = _deform_v2_args(name, input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
+                                   dilation_w, group, deformable_group, with_bias)
+    _deform_written(name, "output", output, out_shape)
+    x, off, m, w = _deform_nhwc(input, offset, mask, weight)
+    y, _ = ops.deform_conv_forward(x, off, m, w, bias.contiguous() if with_bias else None, **g)
+    L.check(L.lib().abr_nhwc_to_nchw(L.ptr(y), out_shape[0], out_shape[1], out_shape[2], out_shape[3], L.ptr(output), L.stream()), name)
+
+
+def modulated_deform_conv_backward(input, weight, bias, ones, offset, mask, columns, grad_input, grad_weight, grad_bias, grad_offset, grad_mask,
+                                   grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                                   deformable_group, with_bias):
+    """ADDS into grad_weight and (with_bias) grad_bias; writes grad_input, grad_offset and grad_mask; float32 only"""
+    name = "modulated_deform_conv_backward"
+    g, out_shape = _deform_v2_args(name, input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
+                                   dilation_w, group, deformable_group, with_bias, more=(grad_output,))
+    if tuple(grad_output.shape) != out_shape:
+        raise RuntimeError(f"{name}: grad_output {tuple(grad_output.shape)} is not {out_shape}")
+    for what, t, like in (("grad_input", grad_input, input), ("grad_weight", grad_weight, weight), ("grad_offset", grad_offset, offset),
+                          ("grad_mask", grad_mask, mask)) + ((("grad_bias", grad_bias, bias),) if with_bias else ()):
+        _deform_written(name, what, t, like.shape)
+    x, off, m, w, gy = _deform_nhwc(input, offset, mask, weight, grad_output)
+    cols = ops.deform_im2col_general(x, off, m, **g)
+    dx, d_off, d_m, dw, db = ops.deform_conv_backward(gy, x, off, m, w, cols, need_input=True, need_weight=True, need_bias=bool(with_bias), **g)
+    for src, dst in ((dx, grad_input), (d_off, grad_offset), (d_m, grad_mask)):
+        L.check(L.lib().abr_nhwc_to_nchw(L.ptr(src), dst.size(0), dst.size(1), dst.size(2), dst.size(3), L.ptr(dst), L.stream()), name)
+    _deform_add_weight_grad(name, grad_weight, dw, 1)
+    if with_bias:
+        ops.add_(grad_bias, db)

@@ -144,6 +144,8 @@ _SIGS = {
     "abr_maxpool3x3s2_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "abr_deform_im2col": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "abr_deform_col2im_coord": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.c_uint32, _vp]),
+    "abr_deform_im2col_general": (_i, [_vp, _vp, _vp] + [_i] * 16 + [_vp, _vp]),
+    "abr_deform_col2im_coord_general": (_i, [_vp, _vp, _vp, _vp] + [_i] * 16 + [_vp, _vp, _vp, _vp]),
     "abr_avgpool_forward": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "abr_avgpool_backward": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "abr_avgpool_relu_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

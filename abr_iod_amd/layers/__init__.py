@@ -1,6 +1,6 @@
 """Mirror of maskrcnn_benchmark/layers/__init__.py:4-20: same public names (ROIAlign, roi_align, ROIPool, roi_pool, nms, smooth_l1_loss,
-SigmoidFocalLoss, FrozenBatchNorm2d, deform_roi_pooling, DeformRoIPooling, DeformRoIPoolingPack, ModulatedDeformRoIPoolingPack), backed
-by the HIP library."""
+SigmoidFocalLoss, FrozenBatchNorm2d, deform_roi_pooling, DeformRoIPooling, DeformRoIPoolingPack, ModulatedDeformRoIPoolingPack, and from
+layers/dcn: deform_conv, modulated_deform_conv, DeformConv, ModulatedDeformConv, ModulatedDeformConvPack), backed by the HIP library."""
 import torch
 from torch import nn
 from torch.autograd import Function
@@ -10,6 +10,7 @@ from torch.nn.modules.utils import _pair
 from .. import _C, ops
 from .._lib import require_cuda
 from ._layout import as_nhwc, from_nhwc
+from .dcn import DeformConv, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv, modulated_deform_conv  # noqa: F401  (layers/__init__.py:6-7)
 
 nms = _C.nms  # layers/nms.py:8 (amp.float_function is a no-op at O0)
 

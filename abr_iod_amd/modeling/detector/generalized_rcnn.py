@@ -32,7 +32,7 @@ from .._flat import flatten_parameters
 # amax (admitted by tests/test_gpu_f16x3_admission.py at the bounds bf16x6 was admitted with; guarded: engine/trainer.py::_x6_guard moves the
 # models to bf16x6 when a large share of the operands leaves its domain and to the fp32 MFMA kernels on inf / nan).  ABR_CONV_MATH=bf16x6 selects
 # rounds 2-4's default (exact three-term bf16 split, six products), ABR_CONV_MATH=f32 the fp32 MFMA kernels.
-DEFAULT_CONV_MATH = "f16x3"
+DEFAULT_CONV_MATH = ops.DEFAULT_CONV_MATH
 
 
 def _drop_derived_cache(base, nbytes):

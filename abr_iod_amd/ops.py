@@ -310,6 +310,19 @@ X6_FLAG_TINY, X6_FLAG_NONFINITE = 1, 2       # ABR_X6_FLAG_*
 H3_FLAG_STALE = 8                            # ABR_H3_FLAG_STALE
 
 
+CONV_MATH = {"f32": MATH_F32, "bf16x6": MATH_BF16X6, "f16x3": MATH_F16X3, "f16": MATH_F16}
+DEFAULT_CONV_MATH = "f16x3"                  # the library's default arithmetic; ABR_CONV_MATH overrides it
+
+
+def default_conv_math():
+    """abr_conv_desc::math of ABR_CONV_MATH (f32, bf16x6 or f16x3; default DEFAULT_CONV_MATH): the arithmetic of a contraction outside a model,
+    which has no GeneralizedRCNN.set_conv_math to choose it"""
+    name = os.environ.get("ABR_CONV_MATH", DEFAULT_CONV_MATH)
+    if name not in ("f32", "bf16x6", "f16x3"):
+        raise ValueError("ABR_CONV_MATH must be f32, bf16x6 or f16x3, got {!r}".format(name))
+    return CONV_MATH[name]
+
+
 def uses_amax(math):
     """the arithmetic scales its operands by their amax words (f16x3, and f16 = its one-product rounded form)"""
     return math == MATH_F16X3 or math == MATH_F16
@@ -1043,6 +1056,135 @@ def deform_col2im_coord(dcol, x, om, dg=1, modulated=False):
     if w is not None:
         amax_tag(d_om, w, e)
     return dx, d_om
+
+
+# ---- the general deformable conv (layers/dcn, _C.deform_conv_* / _C.modulated_deform_conv_*): any kernel, stride, padding, dilation, groups
+def deform_out_size(H, W, kernel, stride, padding, dilation):
+    """(Ho, Wo) of deform_conv_func.py:134-147 / :249-258; all arguments pairs"""
+    return tuple((n + 2 * p - (d * (k - 1) + 1)) // s + 1 for n, k, s, p, d in zip((H, W), kernel, stride, padding, dilation))
+
+
+def _deform_general_args(name, x, offset, mask, kernel, stride, padding, dilation, groups, dg):
+    B, H, W, Ch = x.shape
+    K = kernel[0] * kernel[1]
+    Ho, Wo = offset.shape[1], offset.shape[2]
+    if tuple(offset.shape) != (B, Ho, Wo, dg * 2 * K):
+        raise RuntimeError(f"{name}: offset {tuple(offset.shape)} is not [{B}, Ho, Wo, {dg * 2 * K}]")
+    if mask is not None and tuple(mask.shape) != (B, Ho, Wo, dg * K):
+        raise RuntimeError(f"{name}: mask {tuple(mask.shape)} is not [{B}, {Ho}, {Wo}, {dg * K}]")
+    return (B, H, W, Ch, Ho, Wo, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], int(groups), int(dg))
+
+
+def deform_im2col_general(x, offset, mask=None, kernel=(3, 3), stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1, dg=1):
+    """x [B,H,W,C], offset [B,Ho,Wo,dg*2*K], mask [B,Ho,Wo,dg*K] or None -> cols [groups, B*Ho*Wo, K*C/groups] (include/abr_iod_hip.h,
+    abr_deform_im2col_general).  Without a mask the bilinear weights sum to at most 1: x's amax word bounds cols, which inherits it.  A
+    caller's mask may exceed 1, so with one cols stays untagged and its consumer reduces it."""
+    L.require_cuda(x, offset, mask)
+    x, offset = L.f32c(x), L.f32c(offset)
+    mask = None if mask is None else L.f32c(mask)
+    a = _deform_general_args("deform_im2col_general", x, offset, mask, kernel, stride, padding, dilation, groups, dg)
+    B, Ch, Ho, Wo, K = a[0], a[3], a[4], a[5], a[6] * a[7]
+    cols = _empty((int(groups), B * Ho * Wo, K * (Ch // int(groups))), x)
+    L.check(L.lib().abr_deform_im2col_general(L.ptr(x), L.ptr(offset), L.ptr(mask), *a, L.ptr(cols), L.stream()), "deform_im2col_general")
+    return amax_carry_bound(cols, x) if mask is None else cols
+
+
+def deform_col2im_coord_general(dcol, x, offset, mask=None, kernel=(3, 3), stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1, dg=1):
+    """Backward of deform_im2col_general: (dx [B,H,W,C] from fp32 atomics into zeros -- not bit-reproducible --, d_offset like offset,
+    d_mask like mask or None: both deterministic)."""
+    L.require_cuda(dcol, x, offset, mask)
+    dcol, x, offset = L.f32c(dcol), L.f32c(x), L.f32c(offset)
+    mask = None if mask is None else L.f32c(mask)
+    a = _deform_general_args("deform_col2im_coord_general", x, offset, mask, kernel, stride, padding, dilation, groups, dg)
+    B, Ch, Ho, Wo, K = a[0], a[3], a[4], a[5], a[6] * a[7]
+    if tuple(dcol.shape) != (int(groups), B * Ho * Wo, K * (Ch // int(groups))):
+        raise RuntimeError(f"deform_col2im_coord_general: dcol {tuple(dcol.shape)} is not [{groups}, {B * Ho * Wo}, {K * (Ch // int(groups))}]")
+    dx = torch.zeros_like(x)
+    d_offset = _empty(tuple(offset.shape), offset)
+    d_mask = None if mask is None else _empty(tuple(mask.shape), mask)
+    L.check(L.lib().abr_deform_col2im_coord_general(L.ptr(dcol), L.ptr(x), L.ptr(offset), L.ptr(mask), *a, L.ptr(dx), L.ptr(d_offset),
+                                                    L.ptr(d_mask), L.stream()), "deform_col2im_coord_general")
+    return dx, d_offset, d_mask
+
+
+def _deform_group_weights(w, groups):
+    """OHWI w [Cout,kh,kw,C/groups] -> ([groups, Cop, K*C/groups], Cout/groups, Cop): group g's rows as the 1x1 conv's weight over its columns,
+    the per-group output width padded with zero rows to a multiple of 4 (the contraction kernels' unit, as Conv2d(cout_pad=) does)"""
+    Cout, kh, kw, Cg = w.shape
+    Cog = Cout // groups
+    Cop = (Cog + 3) // 4 * 4
+    wm = w.reshape(groups, Cog, kh * kw * Cg)
+    if Cop != Cog:
+        wp = w.new_zeros((groups, Cop, kh * kw * Cg))
+        wp[:, :Cog].copy_(wm)
+        wm = wp
+    return wm, Cog, Cop
+
+
+def _deform_group_cols(cols, g, B, Ho, Wo):
+    v = cols[g].view(B, Ho, Wo, cols.shape[2])
+    return amax_carry_bound(v, cols)     # (a group's columns are a subset of the tensor's: its amax word, if it has one, bounds them)
+
+
+def deform_conv_forward(x, offset, mask, w, bias, kernel, stride, padding, dilation, groups=1, dg=1, math=None):
+    """The whole general deformable conv on NHWC / OHWI tensors: columns, then one 1x1 conv per group with the bias in its epilogue.
+    x [B,H,W,C], offset [B,Ho,Wo,dg*2K], mask [B,Ho,Wo,dg*K] or None, w [Cout,kh,kw,C/groups], bias [Cout] or None
+    -> (y [B,Ho,Wo,Cout], cols): cols is what deform_conv_backward's weight gradient contracts over.  math None: default_conv_math()."""
+    math = default_conv_math() if math is None else math
+    w = L.f32c(w)
+    Cout = w.shape[0]
+    if Cout % groups or tuple(w.shape[1:3]) != tuple(kernel) or w.shape[3] * groups != x.shape[3]:
+        raise RuntimeError(f"deform_conv_forward: weight {tuple(w.shape)} does not fit x {tuple(x.shape)}, kernel {tuple(kernel)}, groups {groups}")
+    cols = deform_im2col_general(x, offset, mask, kernel, stride, padding, dilation, groups, dg)
+    B, Ho, Wo = offset.shape[:3]
+    wm, Cog, Cop = _deform_group_weights(w, groups)
+    KC = wm.shape[2]
+    if groups == 1 and Cop == Cog:
+        return conv_forward(_deform_group_cols(cols, 0, B, Ho, Wo), wm[0].view(Cop, 1, 1, KC), bias=bias, math=math), cols
+    bp = None
+    if bias is not None:
+        bp = bias.new_zeros((groups, Cop))
+        bp[:, :Cog].copy_(bias.view(groups, Cog))
+    y = _empty((B, Ho, Wo, Cout), x)
+    for g in range(groups):
+        yg = conv_forward(_deform_group_cols(cols, g, B, Ho, Wo), wm[g].view(Cop, 1, 1, KC), bias=None if bp is None else bp[g], math=math)
+        y[..., g * Cog:(g + 1) * Cog].copy_(yg[..., :Cog])
+    return y, cols
+
+
+def deform_conv_backward(gy, x, offset, mask, w, cols, kernel, stride, padding, dilation, groups=1, dg=1, math=None,
+                         need_input=True, need_weight=True, need_bias=False):
+    """Backward of deform_conv_forward from gy [B,Ho,Wo,Cout]: per group the 1x1 dgrad (the columns' gradient) and the weight gradient over
+    (cols, gy); the bias gradient; the col2im + coord kernel.  -> (dx, d_offset, d_mask, dw [Cout,kh,kw,C/groups], db [Cout]), None where
+    not asked for (need_input covers dx, d_offset and d_mask)."""
+    math = default_conv_math() if math is None else math
+    w, gy = L.f32c(w), L.f32c(gy)
+    Cout, kh, kw, Cg = w.shape
+    B, Ho, Wo = offset.shape[:3]
+    wm, Cog, Cop = _deform_group_weights(w, groups)
+    KC = wm.shape[2]
+    dcol = torch.empty_like(cols) if need_input else None
+    dw = wm.new_zeros(wm.shape) if need_weight else None
+    for g in range(groups):
+        if groups == 1 and Cop == Cog:
+            gyg = gy
+        else:
+            gyg = gy.new_zeros((B, Ho, Wo, Cop))
+            gyg[..., :Cog].copy_(gy[..., g * Cog:(g + 1) * Cog])
+        if need_input:
+            conv_forward(gyg, conv_dgrad_weights(wm[g].view(Cop, 1, 1, KC)), out=dcol[g].view(B, Ho, Wo, KC), math=math)
+        if need_weight:
+            conv_wgrad(_deform_group_cols(cols, g, B, Ho, Wo), gyg, dw[g].view(Cop, 1, 1, KC), math=math)
+    db = None
+    if need_bias:
+        db = gy.new_zeros((Cout,))
+        bias_grad(gy, db)
+    dx = d_offset = d_mask = None
+    if need_input:
+        dx, d_offset, d_mask = deform_col2im_coord_general(dcol, x, offset, mask, kernel, stride, padding, dilation, groups, dg)
+    if need_weight:
+        dw = dw[:, :Cog].reshape(Cout, kh, kw, Cg)
+    return dx, d_offset, d_mask, dw, db
 
 
 # ----------------------------------------------------------------------------------------------- pointwise

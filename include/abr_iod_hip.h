@@ -468,6 +468,28 @@ int abr_deform_im2col(const float* x, const float* om, int B, int H, int W, int 
  * C a power of two in [4, 1024]. */
 int abr_deform_col2im_coord(const float* dcol, const float* x, const float* om, int B, int H, int W, int C, int Com, int dg, int modulated,
                             float* dx, float* d_om, uint64_t* d_om_amax, uint32_t d_om_amax_epoch, void* stream);
+/* The general deformable conv (_C.deform_conv_* / _C.modulated_deform_conv_*: csrc/deform_conv.h, deform_conv_kernel_cuda.cu:198-460 and
+ * :578-780, restated) as columns: any kernel with kh * kw <= 49, stride, padding, dilation, `groups` conv groups and `dg` deformable groups.
+ * x [B,H,W,C], offset [B,Ho,Wo,dg*2*K] (K = kh*kw; for deformable group g = C/dg consecutive channels and tap k = i*kw + j: dh at
+ * g*2K + 2k, dw at g*2K + 2k + 1), mask [B,Ho,Wo,dg*K] or NULL (the factor of group g and tap k at g*K + k, used as given: no sigmoid)
+ * -> cols [groups][B*Ho*Wo][K * C/groups], group-major, tap outermost and channel innermost inside a group: each group is the operand of
+ * a 1x1 conv with the OHWI weight read as [Cout/groups][K * C/groups].
+ * Sample point in fp32: h = ho*stride_h - pad_h + i*dil_h + dh, w = wo*stride_w - pad_w + j*dil_w + dw; the value is 0 unless -1 < h < H and
+ * -1 < w < W (non-finite and huge coordinates are outside), else the bilinear interpolation of the corners floor, floor + 1, a corner outside
+ * the image contributing 0; cols = mask * value.
+ * Refused before any launch (negative status, abr_last_error names the argument): kh*kw > 49; non-positive sizes; C % groups or C % dg
+ * non-zero; C/groups or C/dg not a multiple of 4; B*Ho*Wo*K*C/4 >= 2^31; Ho or Wo other than (H + 2 pad - (dil (k - 1) + 1)) / stride + 1. */
+int abr_deform_im2col_general(const float* x, const float* offset, const float* mask, int B, int H, int W, int C, int Ho, int Wo, int kh, int kw,
+                              int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int groups, int dg, float* cols,
+                              void* stream);
+/* its backward from dcol (cols' shape).  dx [B,H,W,C] is ADDED INTO with fp32 atomics (the caller zeroes it, or passes a gradient to
+ * accumulate into; the order of the adds varies from run to run; one wave instruction adds the consecutive channels of one corner pixel,
+ * 256 contiguous bytes once C/dg >= 64).  d_offset [B,Ho,Wo,dg*2*K] (the derivative with the floors held fixed, zero outside the open box)
+ * and d_mask [B,Ho,Wo,dg*K] (sum over the group's channels of dcol * value; NULL exactly when mask is) are WRITTEN, every element by its one
+ * owner, summed over the group's channels in a fixed order: no atomics, bit-reproducible.  The same refusals. */
+int abr_deform_col2im_coord_general(const float* dcol, const float* x, const float* offset, const float* mask, int B, int H, int W, int C, int Ho,
+                                    int Wo, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int groups,
+                                    int dg, float* dx, float* d_offset, float* d_mask, void* stream);
 /* AdaptiveAvgPool2d(1)  roi_box_predictors.py:28 : x [N,HW,C] -> out [N,C] ; backward spreads g/HW */
 int abr_avgpool_forward(const float* x, int N, int HW, int C, float* out, void* stream);
 int abr_avgpool_backward(const float* g, int N, int HW, int C, float* gx, void* stream);

@@ -30,6 +30,9 @@ float32 only; anything else raises RuntimeError naming the dtype.  The deformabl
 (abr_deform_im2col_general, abr_deform_col2im_coord_general) around the library's 1x1 contraction; their scratch arguments (columns, ones)
 are accepted and ignored, and the shape checks of deform_conv_cuda.cu raise with its wording.  The body's DCN keeps its specialised kernels.
 
+The reference's multi-level Pooler (modeling/poolers.py) is Python over roi_align_forward / roi_align_backward above and works through this
+module level by level; abr_iod_amd.modeling.poolers.Pooler pools several scales in one launch each way instead (ops.roi_align_pyramid_*).
+
 CPU tensors raise RuntimeError (the reference raises "Not compiled with GPU support" the other way round):
 this library is MI355X-only by design; the CPU restatement lives in oracle/ and is test infrastructure.
 """

@@ -95,6 +95,9 @@ _SIGS = {
     "abr_roi_align_backward_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "abr_roi_align_backward_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "abr_roi_align_taps": (_i, [_vp, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "abr_fpn_levels": (_i, [_vp, _i, _f, _f, _f, _f, _f, _vp, _vp]),
+    "abr_roi_align_pyramid_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "abr_roi_align_pyramid_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "abr_roi_pool_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
     "abr_roi_pool_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "abr_roi_pool_forward_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp, _vp, _vp]),

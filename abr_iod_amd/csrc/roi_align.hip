@@ -14,7 +14,8 @@
 //     accumulation uses the reference's order too (w1*v1 + w2*v2 + w3*v3 + w4*v4, then /count);
 //   * blockIdx is remapped so each XCD (private L2) walks a contiguous range of (roi, bin) tiles:
 //     neighbouring bins/RoIs re-read the same feature rows from that XCD's L2;
-//   * bin_step=2 computes only the even bins -- the only ones layer4's stride-2 1x1 conv reads.
+//   * bin_step=2 computes only the even bins -- the only ones layer4's stride-2 1x1 conv reads;
+//   * a feature pyramid (modeling/poolers.py) is pooled by the same tile code in one launch: the level is a per-workgroup choice of map.
 // Bound: HBM (output write / grad read) with L2-resident tap re-reads; see DESIGN.md.
 #include <stdlib.h>
 
@@ -88,26 +89,17 @@ struct VecT<4> { using type = float4; };
 template <>
 struct VecT<1> { using type = float; };
 
+// One workgroup's share of the forward: `bpb` bins from bin0 of RoI n (its row of the table at `roi`), channel slice `slice` of `cslices`, on ONE
+// map.  The single-level kernel and the pyramid kernel (which picks feat, H, W, scale per RoI) both run exactly this.
 #pragma clang fp contract(off)
 template <int VEC>
-__global__ __launch_bounds__(256) void roi_align_fwd_nhwc(const float* __restrict__ feat, const float* __restrict__ rois,
-                                                           int K, int C, int H, int W, float scale, int PH, int PW,
-                                                           int sr, int step, int PHo, int PWo, int bpb, int tx,
-                                                           int blocks_per_roi, int cslices, float* __restrict__ out) {
-    __shared__ int4 s_idx[256];
-    __shared__ float4 s_w[256];
-    const unsigned nblk = gridDim.x;
-    // cslices == 8: consecutive workgroups land on consecutive XCDs, so workgroup b takes channel slice b % 8 of tile b / 8 -- every
-    // XCD then reads ONE eighth of the channels of every image (1.2 MB per image at C = 1024: resident in its 4 MiB L2, where a
-    // whole image's map, 9.7 MB, is not) and the taps that neighbouring bins / RoIs share are L2 hits instead of fabric fetches
-    const unsigned bid = cslices > 1 ? blockIdx.x / (unsigned)cslices : abr::xcd_remap(blockIdx.x, nblk);
-    const int slice = cslices > 1 ? (int)(blockIdx.x % (unsigned)cslices) : 0;
-    const int n = bid / blocks_per_roi;
-    const int bin0 = (bid % blocks_per_roi) * bpb;
+__device__ __forceinline__ void fwd_nhwc_tile(const float* __restrict__ feat, const float* __restrict__ roi, int n, int bin0, int slice,
+                                              int C, int H, int W, float scale, int PH, int PW, int sr, int step, int PHo, int PWo,
+                                              int bpb, int tx, int cslices, float* __restrict__ out, int4* s_idx, float4* s_w) {
     const int nbins = PHo * PWo;
     const int tch = 256 / bpb;  // samples per chunk per bin
 
-    const RoiGeom<float> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+    const RoiGeom<float> g = roi_geom(roi, scale, PH, PW, sr);
     const int ns = g.gh * g.gw;
     const float count = (float)ns;
 
@@ -178,24 +170,39 @@ __global__ __launch_bounds__(256) void roi_align_fwd_nhwc(const float* __restric
     }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// NHWC backward: scatter (g*w_k)/count to the 4 taps with hardware fp32 atomics (global_atomic_add_f32).
-// ---------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
 template <int VEC>
-__global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float* __restrict__ grad, const float* __restrict__ rois,
+__global__ __launch_bounds__(256) void roi_align_fwd_nhwc(const float* __restrict__ feat, const float* __restrict__ rois,
                                                            int K, int C, int H, int W, float scale, int PH, int PW,
                                                            int sr, int step, int PHo, int PWo, int bpb, int tx,
-                                                           int blocks_per_roi, float* __restrict__ gfeat) {
+                                                           int blocks_per_roi, int cslices, float* __restrict__ out) {
     __shared__ int4 s_idx[256];
     __shared__ float4 s_w[256];
-    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned nblk = gridDim.x;
+    // cslices == 8: consecutive workgroups land on consecutive XCDs, so workgroup b takes channel slice b % 8 of tile b / 8 -- every
+    // XCD then reads ONE eighth of the channels of every image (1.2 MB per image at C = 1024: resident in its 4 MiB L2, where a
+    // whole image's map, 9.7 MB, is not) and the taps that neighbouring bins / RoIs share are L2 hits instead of fabric fetches
+    const unsigned bid = cslices > 1 ? blockIdx.x / (unsigned)cslices : abr::xcd_remap(blockIdx.x, nblk);
+    const int slice = cslices > 1 ? (int)(blockIdx.x % (unsigned)cslices) : 0;
     const int n = bid / blocks_per_roi;
     const int bin0 = (bid % blocks_per_roi) * bpb;
+    fwd_nhwc_tile<VEC>(feat, rois + 5 * (size_t)n, n, bin0, slice, C, H, W, scale, PH, PW, sr, step, PHo, PWo, bpb, tx, cslices, out, s_idx, s_w);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// NHWC backward: scatter (g*w_k)/count to the 4 taps with hardware fp32 atomics (global_atomic_add_f32).
+// A = the type of the buffer the atomics add into: float (the single-level kernels: the gradient itself) or double (the pyramid kernels'
+// scratch, rounded to the gradient once at the end); the addend is computed in float either way.
+// ---------------------------------------------------------------------------------------------------
+#pragma clang fp contract(off)
+template <int VEC, typename A>
+__device__ __forceinline__ void bwd_nhwc_tile(const float* __restrict__ grad, const float* __restrict__ roi, int n, int bin0, int C, int H, int W,
+                                              float scale, int PH, int PW, int sr, int step, int PHo, int PWo, int bpb, int tx,
+                                              A* __restrict__ gfeat, int4* s_idx, float4* s_w) {
     const int nbins = PHo * PWo;
     const int tch = 256 / bpb;
 
-    const RoiGeom<float> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+    const RoiGeom<float> g = roi_geom(roi, scale, PH, PW, sr);
     const int ns = g.gh * g.gw;
     const float count = (float)ns;
 
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float* __restric
     const int bin = bin0 + bl;
     const bool bin_ok = bin < nbins;
     const int cvecs = C / VEC;
-    float* gb = gfeat + (size_t)g.b * H * W * C;
+    A* gb = gfeat + (size_t)g.b * H * W * C;
 
     const int eb = threadIdx.x / tch, es = threadIdx.x % tch;
     const int ebin = bin0 + eb;
@@ -237,21 +244,35 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float* __restric
                     const int4 p = s_idx[bl * tch + s];
                     if (p.x < 0) continue;
                     const float4 w = s_w[bl * tch + s];
-                    float* d0 = gb + (size_t)p.x * C + cv * VEC;
-                    float* d1 = gb + (size_t)p.y * C + cv * VEC;
-                    float* d2 = gb + (size_t)p.z * C + cv * VEC;
-                    float* d3 = gb + (size_t)p.w * C + cv * VEC;
+                    A* d0 = gb + (size_t)p.x * C + cv * VEC;
+                    A* d1 = gb + (size_t)p.y * C + cv * VEC;
+                    A* d2 = gb + (size_t)p.z * C + cv * VEC;
+                    A* d3 = gb + (size_t)p.w * C + cv * VEC;
 #pragma unroll
                     for (int i = 0; i < VEC; i++) {
-                        unsafeAtomicAdd(d0 + i, gp[i] * w.x / count);
-                        unsafeAtomicAdd(d1 + i, gp[i] * w.y / count);
-                        unsafeAtomicAdd(d2 + i, gp[i] * w.z / count);
-                        unsafeAtomicAdd(d3 + i, gp[i] * w.w / count);
+                        unsafeAtomicAdd(d0 + i, (A)(gp[i] * w.x / count));
+                        unsafeAtomicAdd(d1 + i, (A)(gp[i] * w.y / count));
+                        unsafeAtomicAdd(d2 + i, (A)(gp[i] * w.z / count));
+                        unsafeAtomicAdd(d3 + i, (A)(gp[i] * w.w / count));
                     }
                 }
             }
         }
     }
+}
+
+#pragma clang fp contract(off)
+template <int VEC>
+__global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float* __restrict__ grad, const float* __restrict__ rois,
+                                                           int K, int C, int H, int W, float scale, int PH, int PW,
+                                                           int sr, int step, int PHo, int PWo, int bpb, int tx,
+                                                           int blocks_per_roi, float* __restrict__ gfeat) {
+    __shared__ int4 s_idx[256];
+    __shared__ float4 s_w[256];
+    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const int n = bid / blocks_per_roi;
+    const int bin0 = (bid % blocks_per_roi) * bpb;
+    bwd_nhwc_tile<VEC, float>(grad, rois + 5 * (size_t)n, n, bin0, C, H, W, scale, PH, PW, sr, step, PHo, PWo, bpb, tx, gfeat, s_idx, s_w);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -283,18 +304,14 @@ __device__ __forceinline__ void axis_tap(float start, float bin, int grid, int p
     *lo = l; *hi = h; *wlo = 1.f - lw; *whi = lw;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void roi_align_bwd_nhwc_sep(const float* __restrict__ grad, const float* __restrict__ rois,
-                                                               int K, int C, int H, int W, float scale, int PH, int PW,
-                                                               int sr, int step, int PHo, int PWo, int tx, int cchunks,
-                                                               float* __restrict__ gfeat) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
+template <int VEC, typename A>   // A: as for bwd_nhwc_tile
+__device__ __forceinline__ void bwd_nhwc_sep_tile(const float* __restrict__ grad, const float* __restrict__ roi, int n, int chunk, int C, int H,
+                                                  int W, float scale, int PH, int PW, int sr, int step, int PHo, int PWo, int tx,
+                                                  A* __restrict__ gfeat, float* sm) {
     float* Wy = sm;                 // [PHo][H]
     float* Wx = sm + PHo * H;       // [PWo][W]
     int* rng = reinterpret_cast<int*>(Wx + PWo * W);  // ymin, ymax, xmin, xmax
-    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
-    const int n = bid / cchunks, chunk = bid % cchunks;
-    const RoiGeom<float> g = roi_geom(rois + 5 * (size_t)n, scale, PH, PW, sr);
+    const RoiGeom<float> g = roi_geom(roi, scale, PH, PW, sr);
     const float inv_count = 1.f / (float)(g.gh * g.gw);
 
     for (int i = threadIdx.x; i < PHo * H + PWo * W; i += 256) sm[i] = 0.f;
@@ -330,7 +347,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc_sep(const float* __res
     const int cv = chunk * tx + cl;
     if (cv >= cvecs) return;
     const float* gr = grad + (size_t)n * PHo * PWo * C + cv * VEC;
-    float* gb = gfeat + (size_t)g.b * H * W * C + cv * VEC;
+    A* gb = gfeat + (size_t)g.b * H * W * C + cv * VEC;
 
     for (int y = ymin + rl; y <= ymax; y += nrl) {
         float T[kMaxPo][VEC];
@@ -371,12 +388,23 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc_sep(const float* __res
                 }
             }
             if (hit) {
-                float* d = gb + ((size_t)y * W + x) * C;
+                A* d = gb + ((size_t)y * W + x) * C;
 #pragma unroll
-                for (int i = 0; i < VEC; i++) unsafeAtomicAdd(d + i, o[i]);
+                for (int i = 0; i < VEC; i++) unsafeAtomicAdd(d + i, (A)o[i]);
             }
         }
     }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void roi_align_bwd_nhwc_sep(const float* __restrict__ grad, const float* __restrict__ rois,
+                                                               int K, int C, int H, int W, float scale, int PH, int PW,
+                                                               int sr, int step, int PHo, int PWo, int tx, int cchunks,
+                                                               float* __restrict__ gfeat) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const int n = bid / cchunks, chunk = bid % cchunks;
+    bwd_nhwc_sep_tile<VEC, float>(grad, rois + 5 * (size_t)n, n, chunk, C, H, W, scale, PH, PW, sr, step, PHo, PWo, tx, gfeat, sm);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -754,7 +782,247 @@ int launch_nchw(void (*kernel)(const T*, const T*, int64_t, int, int, int, T, in
     return ABR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Pooling over a feature pyramid (modeling/poolers.py:11-42, 80-105) in one launch each way.
+//
+// The reference loops over the levels: per level a nonzero (a device-to-host sync), a row gather, one ROIAlign launch and an indexed write
+// into a zero-filled result.  A workgroup here already belongs to ONE RoI, so the level is a workgroup-uniform choice of (map, H, W, scale):
+// the workgroup computes its RoI's level with the reference's fp32 expression, reads that level's entry of a by-value table (scalar loads
+// from the kernel arguments: nothing on the device to build or keep alive) and runs the single-level tile code above on it.
+// ---------------------------------------------------------------------------------------------------
+struct LevelRule { float k_min, k_max, s0, lvl0, eps; };
+
+template <typename T>   // float: the maps (forward); double: the backward's accumulation buffers
+struct Pyramid {
+    T* feat[ABR_MAX_PYRAMID_LEVELS];   // [B, H[l], W[l], C]
+    int H[ABR_MAX_PYRAMID_LEVELS], W[ABR_MAX_PYRAMID_LEVELS];
+    float scale[ABR_MAX_PYRAMID_LEVELS];
+    LevelRule rule;
+};
+
+// LevelMapper.__call__ (poolers.py:37-42) op by op in fp32: area with TO_REMOVE = 1 (BoxList.area), IEEE sqrt and division, log2, the sum
+// rounded before the floor, clamp, then the integer difference.  -1 where the level is NaN (a negative or NaN area): the reference's row
+// then matches no level and stays zero.
+#pragma clang fp contract(off)
+__device__ __forceinline__ int fpn_level(const float* __restrict__ r, const LevelRule& m) {
+    const float area = (r[3] - r[1] + 1.f) * (r[4] - r[2] + 1.f);
+    const float s = sqrtf(area);
+    const float t = floorf(m.lvl0 + log2f(s / m.s0 + m.eps));
+    if (!(t == t)) return -1;
+    return (int)fminf(fmaxf(t, m.k_min), m.k_max) - (int)m.k_min;
+}
+
+__global__ __launch_bounds__(256) void fpn_levels_kernel(const float* __restrict__ rois, int K, LevelRule rule, int32_t* __restrict__ levels) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n < K) levels[n] = fpn_level(rois + 5 * (size_t)n, rule);
+}
+
+#pragma clang fp contract(off)
+template <int VEC>
+__global__ __launch_bounds__(256) void roi_align_pyramid_fwd(Pyramid<float> py, const float* __restrict__ rois, int C, int PH, int PW, int sr, int bpb,
+                                                              int tx, int blocks_per_roi, float* __restrict__ out,
+                                                              int32_t* __restrict__ levels_out) {
+    __shared__ int4 s_idx[256];
+    __shared__ float4 s_w[256];
+    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const int n = bid / blocks_per_roi;
+    const int bin0 = (bid % blocks_per_roi) * bpb;
+    const float* roi = rois + 5 * (size_t)n;
+    const int lv = __builtin_amdgcn_readfirstlane(fpn_level(roi, py.rule));
+    if (levels_out && bin0 == 0 && threadIdx.x == 0) levels_out[n] = lv;
+    if (lv < 0) {   // no level: the row is zero (poolers.py:99)
+        const int nbins = PH * PW;
+        const int cnt = min(bpb, nbins - bin0) * C;
+        float* o = out + ((size_t)n * nbins + bin0) * C;
+        for (int i = threadIdx.x; i < cnt; i += 256) o[i] = 0.f;
+        return;
+    }
+    fwd_nhwc_tile<VEC>(py.feat[lv], roi, n, bin0, 0, C, py.H[lv], py.W[lv], py.scale[lv], PH, PW, sr, 1, PH, PW, bpb, tx, 1, out, s_idx, s_w);
+}
+
+#pragma clang fp contract(off)
+template <int VEC>
+__global__ __launch_bounds__(256) void roi_align_pyramid_bwd(Pyramid<double> py, const float* __restrict__ grad, const float* __restrict__ rois, int C,
+                                                              int PH, int PW, int sr, int bpb, int tx, int blocks_per_roi) {
+    __shared__ int4 s_idx[256];
+    __shared__ float4 s_w[256];
+    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const int n = bid / blocks_per_roi;
+    const int bin0 = (bid % blocks_per_roi) * bpb;
+    const float* roi = rois + 5 * (size_t)n;
+    const int lv = __builtin_amdgcn_readfirstlane(fpn_level(roi, py.rule));
+    if (lv < 0) return;
+    bwd_nhwc_tile<VEC, double>(grad, roi, n, bin0, C, py.H[lv], py.W[lv], py.scale[lv], PH, PW, sr, 1, PH, PW, bpb, tx, py.feat[lv], s_idx, s_w);
+}
+
+// dynamic LDS: the largest level's tables (the host sizes it)
+#pragma clang fp contract(off)
+template <int VEC>
+__global__ __launch_bounds__(256) void roi_align_pyramid_bwd_sep(Pyramid<double> py, const float* __restrict__ grad, const float* __restrict__ rois, int C,
+                                                                  int PH, int PW, int sr, int tx, int cchunks) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const int n = bid / cchunks, chunk = bid % cchunks;
+    const float* roi = rois + 5 * (size_t)n;
+    const int lv = __builtin_amdgcn_readfirstlane(fpn_level(roi, py.rule));
+    if (lv < 0) return;
+    bwd_nhwc_sep_tile<VEC, double>(grad, roi, n, chunk, C, py.H[lv], py.W[lv], py.scale[lv], PH, PW, sr, 1, PH, PW, tx, py.feat[lv], sm);
+}
+
+// The backward's last step: every element of every level's gradient = (accumulate ? what is there : 0) + the float64 sum, rounded ONCE.
+// `acc` holds the levels back to back; end[l] = one past level l's last element.
+struct PyramidOut {
+    float* dst[ABR_MAX_PYRAMID_LEVELS];
+    int64_t end[ABR_MAX_PYRAMID_LEVELS];
+};
+
+__global__ __launch_bounds__(256) void roi_align_pyramid_round(const double* __restrict__ acc, PyramidOut po, int L, int accumulate) {
+    const int64_t total = po.end[L - 1];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        int l = 0;
+        while (i >= po.end[l]) l++;
+        float* d = po.dst[l] + (i - (l ? po.end[l - 1] : 0));
+        *d = accumulate ? (float)((double)*d + acc[i]) : (float)acc[i];
+    }
+}
+
+// the arguments the two pyramid entry points share: checked, then packed into the by-value table (the caller sets the pointers)
+template <typename T>
+int make_pyramid(const char* name, const void* feats, const int* H, const int* W, const float* scales, int L, int K, int B, int C, int PH,
+                 int PW, float k_min, float k_max, float s0, float lvl0, float eps, Pyramid<T>* py) {
+    ABR_REQUIRE(L >= 1 && L <= ABR_MAX_PYRAMID_LEVELS, "%s: L = %d levels, need 1 .. %d", name, L, ABR_MAX_PYRAMID_LEVELS);
+    ABR_REQUIRE(K >= 0 && B > 0 && C > 0 && PH > 0 && PW > 0, "%s: bad shape", name);
+    ABR_REQUIRE(feats && H && W && scales, "%s: null level table", name);
+    // every level the rule can name has an entry (L = 1: k_min == k_max, every valid row on level 0)
+    ABR_REQUIRE(k_min <= k_max && (int)k_max - (int)k_min < L, "%s: k_min %g .. k_max %g names more than L = %d levels", name, k_min, k_max, L);
+    ABR_REQUIRE((int64_t)K * PH * PW * C <= INT32_MAX, "%s: K * PH * PW * C does not fit int32", name);
+    for (int l = 0; l < L; l++) {
+        ABR_REQUIRE(H[l] >= 1 && W[l] >= 1, "%s: level %d is %d x %d", name, l, H[l], W[l]);
+        ABR_REQUIRE((int64_t)B * H[l] * W[l] * C <= INT32_MAX, "%s: level %d: B * H * W * C does not fit int32", name, l);
+        py->feat[l] = nullptr;
+        py->H[l] = H[l];
+        py->W[l] = W[l];
+        py->scale[l] = scales[l];
+    }
+    for (int l = L; l < ABR_MAX_PYRAMID_LEVELS; l++) {
+        py->feat[l] = nullptr;
+        py->H[l] = py->W[l] = 1;
+        py->scale[l] = 0.f;
+    }
+    py->rule = LevelRule{k_min, k_max, s0, lvl0, eps};
+    return ABR_OK;
+}
+
 }  // namespace
+
+extern "C" int abr_fpn_levels(const float* rois, int K, float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
+                              int32_t* levels, void* stream) {
+    ABR_REQUIRE(K >= 0, "fpn_levels: bad shape");
+    ABR_REQUIRE(k_min <= k_max, "fpn_levels: k_min %g > k_max %g", k_min, k_max);
+    if (K == 0) return ABR_OK;
+    ABR_REQUIRE(rois && levels, "fpn_levels: null pointer");
+    fpn_levels_kernel<<<(unsigned)((K + 255) / 256), 256, 0, abr::as_stream(stream)>>>(rois, K, LevelRule{k_min, k_max, canonical_scale, canonical_level, eps},
+                                                                                      levels);
+    ABR_CHECK_LAUNCH("fpn_levels");
+    return ABR_OK;
+}
+
+extern "C" int abr_roi_align_pyramid_forward(const float* const* feats, const int* H, const int* W, const float* scales, int L, const float* rois, int K,
+                                             int B, int C, int PH, int PW, int sr, float k_min, float k_max, float canonical_scale,
+                                             float canonical_level, float eps, float* out, int32_t* levels_out, void* stream) {
+    Pyramid<float> py;
+    const int rc = make_pyramid("roi_align_pyramid_forward", feats, H, W, scales, L, K, B, C, PH, PW, k_min, k_max, canonical_scale, canonical_level,
+                                eps, &py);
+    if (rc != ABR_OK) return rc;
+    if (K == 0) return ABR_OK;
+    ABR_REQUIRE(rois && out, "roi_align_pyramid_forward: null pointer");
+    for (int l = 0; l < L; l++) {
+        ABR_REQUIRE(feats[l], "roi_align_pyramid_forward: null map at level %d", l);
+        py.feat[l] = const_cast<float*>(feats[l]);
+    }
+    hipStream_t st = abr::as_stream(stream);
+    const int nbins = PH * PW;
+    int tx, bpb;
+    if (C % 4 == 0) {
+        pick_shape(C / 4, nbins, &tx, &bpb);
+        const int bpr = (nbins + bpb - 1) / bpb;
+        roi_align_pyramid_fwd<4><<<(unsigned)(K * bpr), 256, 0, st>>>(py, rois, C, PH, PW, sr, bpb, tx, bpr, out, levels_out);
+    } else {
+        pick_shape(C, nbins, &tx, &bpb);
+        const int bpr = (nbins + bpb - 1) / bpb;
+        roi_align_pyramid_fwd<1><<<(unsigned)(K * bpr), 256, 0, st>>>(py, rois, C, PH, PW, sr, bpb, tx, bpr, out, levels_out);
+    }
+    ABR_CHECK_LAUNCH("roi_align_pyramid_forward");
+    return ABR_OK;
+}
+
+extern "C" int abr_roi_align_pyramid_backward(const float* grad, const float* rois, int K, int B, int C, const int* H, const int* W, const float* scales,
+                                              int L, int PH, int PW, int sr, float k_min, float k_max, float canonical_scale, float canonical_level,
+                                              float eps, int accumulate, float* const* grad_feats, void* stream) {
+    Pyramid<double> py;
+    const int rc = make_pyramid("roi_align_pyramid_backward", grad_feats, H, W, scales, L, K, B, C, PH, PW, k_min, k_max, canonical_scale,
+                                canonical_level, eps, &py);
+    if (rc != ABR_OK) return rc;
+    for (int l = 0; l < L; l++) ABR_REQUIRE(grad_feats[l], "roi_align_pyramid_backward: null output at level %d", l);
+    hipStream_t st = abr::as_stream(stream);
+    if (K == 0) {   // nothing to add: every level, reached or not, is zero unless accumulating
+        for (int l = 0; l < L && !accumulate; l++) {
+            if (hipMemsetAsync(grad_feats[l], 0, sizeof(float) * (size_t)B * C * H[l] * W[l], st) != hipSuccess) {
+                abr::set_error("roi_align_pyramid_backward: memset failed");
+                return ABR_E_LAUNCH;
+            }
+        }
+        return ABR_OK;
+    }
+    ABR_REQUIRE(grad && rois, "roi_align_pyramid_backward: null pointer");
+    // The atomics add into zeroed float64 scratch, one buffer per level back to back, and roi_align_pyramid_round rounds each sum to the
+    // gradient once.  With float32 atomics an element that hundreds of RoIs reach is a float32 sum in arrival order: every add rounds at the
+    // ulp of the running sum, and 300 small terms behind three large ones measured 1.1e-6 of the sum of |addends| (MEASUREMENTS.md).
+    PyramidOut po;
+    int64_t total = 0;
+    for (int l = 0; l < ABR_MAX_PYRAMID_LEVELS; l++) {
+        if (l < L) total += (int64_t)B * H[l] * W[l] * C;
+        po.dst[l] = l < L ? grad_feats[l] : nullptr;
+        po.end[l] = total;
+    }
+    double* acc = static_cast<double*>(abr::scratch(abr::SCRATCH_ROI_PYRAMID, st, sizeof(double) * (size_t)total));
+    if (!acc) {
+        abr::set_error("roi_align_pyramid_backward: no memory for %lld bytes of accumulation scratch", (long long)(sizeof(double) * total));
+        return ABR_E_WORKSPACE;
+    }
+    if (hipMemsetAsync(acc, 0, sizeof(double) * (size_t)total, st) != hipSuccess) {
+        abr::set_error("roi_align_pyramid_backward: memset failed");
+        return ABR_E_LAUNCH;
+    }
+    for (int l = 0; l < L; l++) py.feat[l] = acc + (l ? po.end[l - 1] : 0);
+    const int vec = (C % 4 == 0) ? 4 : 1;
+    const int cvecs = C / vec;
+    size_t sep_lds = 0;
+    for (int l = 0; l < L; l++) sep_lds = std::max(sep_lds, sizeof(float) * ((size_t)PH * H[l] + (size_t)PW * W[l]) + 16);
+    if (PH <= kMaxPo && PW <= kMaxPo && sep_lds <= 60 * 1024) {
+        int t = 1;
+        while (t < cvecs && t < 256) t <<= 1;
+        if (t < 16) t = 16;
+        const int cchunks = (cvecs + t - 1) / t;
+        if (vec == 4)
+            roi_align_pyramid_bwd_sep<4><<<(unsigned)(K * cchunks), 256, sep_lds, st>>>(py, grad, rois, C, PH, PW, sr, t, cchunks);
+        else
+            roi_align_pyramid_bwd_sep<1><<<(unsigned)(K * cchunks), 256, sep_lds, st>>>(py, grad, rois, C, PH, PW, sr, t, cchunks);
+    } else {
+        const int nbins = PH * PW;
+        int tx, bpb;
+        pick_shape(cvecs, nbins, &tx, &bpb);
+        const int bpr = (nbins + bpb - 1) / bpb;
+        if (vec == 4)
+            roi_align_pyramid_bwd<4><<<(unsigned)(K * bpr), 256, 0, st>>>(py, grad, rois, C, PH, PW, sr, bpb, tx, bpr);
+        else
+            roi_align_pyramid_bwd<1><<<(unsigned)(K * bpr), 256, 0, st>>>(py, grad, rois, C, PH, PW, sr, bpb, tx, bpr);
+    }
+    ABR_CHECK_LAUNCH("roi_align_pyramid_backward");
+    roi_align_pyramid_round<<<(unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32), 256, 0, st>>>(acc, po, L, accumulate);
+    ABR_CHECK_LAUNCH("roi_align_pyramid_backward");
+    return ABR_OK;
+}
 
 extern "C" int abr_roi_align_forward(const float* feat, const float* rois, int K, int B, int C, int H, int W,
                                      float scale, int PH, int PW, int sr, int bin_step, int layout, float* out,

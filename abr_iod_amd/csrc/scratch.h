@@ -24,6 +24,7 @@ enum ScratchSlot {
     SCRATCH_BIAS_TICKETS,   // abr_bias_grad: one ticket per column chunk
     SCRATCH_DET,            // det_ws: tickets + ring of partial sums (words: the two ring cursors)
     SCRATCH_TOPK,           // topk.hip (words: capacity in images, capacity in keys)
+    SCRATCH_ROI_PYRAMID,    // roi_align.hip: the pyramid backward's float64 sums, every level's map back to back
 };
 // process-wide zero-initialised words
 enum WordSlot { WORDS_X6_FLAGS, WORDS_H3_STATS, WORDS_AMAX_RING, WORDS_SLOTS };

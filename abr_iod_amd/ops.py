@@ -83,6 +83,104 @@ def roi_align_taps(rois, H, W, spatial_scale, ph, pw, sampling_ratio, max_s):
     return idx, grid
 
 
+# ----------------------------------------------------------------------------------------------- ROIAlign over a feature pyramid
+MAX_PYRAMID_LEVELS = 8   # ABR_MAX_PYRAMID_LEVELS
+
+
+def fpn_levels(rois, k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6):
+    """rois [K,5] -> int32 [K]: the pyramid level of every row (modeling/poolers.py:37-42 in fp32), -1 for a row without one (NaN or negative area)"""
+    L.require_cuda(rois)
+    rois = L.f32c(rois)
+    K = rois.shape[0]
+    levels = torch.empty((K,), dtype=torch.int32, device=rois.device)
+    L.check(L.lib().abr_fpn_levels(L.ptr(rois), K, float(k_min), float(k_max), float(canonical_scale), float(canonical_level), float(eps),
+                                   L.ptr(levels), L.stream()), "fpn_levels")
+    return levels
+
+
+def _pyramid_tables(what, tensors, shapes, scales):
+    """the host arrays of the pyramid entry points: (pointers, H, W, scales) of `tensors`, a list of contiguous fp32 [B,H_l,W_l,C] device tensors"""
+    n = len(shapes)
+    if not 1 <= n <= MAX_PYRAMID_LEVELS:
+        raise RuntimeError(f"{what}: {n} levels, need 1 .. {MAX_PYRAMID_LEVELS}")
+    if len(scales) != n:
+        raise RuntimeError(f"{what}: {len(scales)} scales for {n} levels")
+    return ((C.c_void_p * n)(*[t.data_ptr() for t in tensors]), (C.c_int * n)(*[s[1] for s in shapes]), (C.c_int * n)(*[s[2] for s in shapes]),
+            (C.c_float * n)(*[float(s) for s in scales]))
+
+
+def _pyramid_check(what, feats, name="feats"):
+    """B, C, device and dtype agree across the levels -> (B, C)"""
+    if not 1 <= len(feats) <= MAX_PYRAMID_LEVELS:
+        raise RuntimeError(f"{what}: {name} has {len(feats)} levels, need 1 .. {MAX_PYRAMID_LEVELS}")
+    f0 = feats[0]
+    for l, f in enumerate(feats):
+        if not f.is_cuda:
+            raise RuntimeError(f"{what}: {name}[{l}] is a CPU tensor; abr_iod_amd ops need device tensors")
+        if f.dtype != _f32:
+            raise RuntimeError(f"{what}: {name}[{l}] has dtype {f.dtype}, expected float32")
+        if f.dim() != 4 or not f.is_contiguous():
+            raise RuntimeError(f"{what}: {name}[{l}] must be a contiguous [B,H,W,C] tensor, got shape {tuple(f.shape)}")
+        if f.device != f0.device:
+            raise RuntimeError(f"{what}: device of {name}[{l}] is {f.device}, of {name}[0] {f0.device}")
+        if f.shape[0] != f0.shape[0]:
+            raise RuntimeError(f"{what}: B of {name}[{l}] is {f.shape[0]}, of {name}[0] {f0.shape[0]}")
+        if f.shape[3] != f0.shape[3]:
+            raise RuntimeError(f"{what}: C of {name}[{l}] is {f.shape[3]}, of {name}[0] {f0.shape[3]}")
+    return f0.shape[0], f0.shape[3]
+
+
+def roi_align_pyramid_forward(feats, rois, scales, ph, pw, sampling_ratio, k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6,
+                              out=None, want_levels=False):
+    """feats: list of contiguous [B,H_l,W_l,C], rois [K,5] -> [K,ph,pw,C] in ONE launch (written into `out` when given): every row pooled on
+    the level fpn_levels gives it, all zero for a row without one.  want_levels: -> (out, int32 [K] levels).  The result carries no amax
+    tag: its rows come from maps with different amax words."""
+    feats = list(feats)
+    B, Ch = _pyramid_check("roi_align_pyramid_forward", feats)
+    L.require_cuda(rois)
+    rois = L.f32c(rois)
+    K = rois.shape[0]
+    if out is None:
+        out = _empty((K, ph, pw, Ch), rois)
+    else:
+        assert tuple(out.shape) == (K, ph, pw, Ch) and out.is_contiguous() and out.dtype == _f32
+    levels = torch.empty((K,), dtype=torch.int32, device=rois.device) if want_levels else None
+    fp, Hs, Ws, sc = _pyramid_tables("roi_align_pyramid_forward", feats, [f.shape for f in feats], scales)
+    L.check(L.lib().abr_roi_align_pyramid_forward(fp, Hs, Ws, sc, len(feats), L.ptr(rois), K, B, Ch, ph, pw, sampling_ratio, float(k_min), float(k_max),
+                                                  float(canonical_scale), float(canonical_level), float(eps), L.ptr(out), L.ptr(levels), L.stream()),
+            "roi_align_pyramid_forward")
+    amax_drop(out)
+    return (out, levels) if want_levels else out
+
+
+def roi_align_pyramid_backward(grad, rois, scales, ph, pw, sampling_ratio, shapes, k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6,
+                               out=None):
+    """grad [K,ph,pw,C], shapes: the [B,H_l,W_l,C] of every level -> list of grad_feat [B,H_l,W_l,C]: one launch over the RoIs adds into
+    float64 scratch with hardware atomics (their order varies from run to run), a second rounds every level's sums to fp32 once; every level is
+    written whole, reached or not, unless the list `out` is given: then it accumulates"""
+    L.require_cuda(grad, rois)
+    grad, rois = L.f32c(grad), L.f32c(rois)
+    K = rois.shape[0]
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    acc = out is not None
+    if out is None:
+        out = [_empty(s, grad) for s in shapes]
+    else:
+        out = list(out)
+        if [tuple(o.shape) for o in out] != shapes:
+            raise RuntimeError(f"roi_align_pyramid_backward: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
+    B, Ch = _pyramid_check("roi_align_pyramid_backward", out, "out")
+    if tuple(grad.shape) != (K, ph, pw, Ch):
+        raise RuntimeError(f"roi_align_pyramid_backward: grad {tuple(grad.shape)} is not [{K}, {ph}, {pw}, {Ch}]")
+    gp, Hs, Ws, sc = _pyramid_tables("roi_align_pyramid_backward", out, shapes, scales)
+    L.check(L.lib().abr_roi_align_pyramid_backward(L.ptr(grad), L.ptr(rois), K, B, Ch, Hs, Ws, sc, len(out), ph, pw, sampling_ratio, float(k_min),
+                                                   float(k_max), float(canonical_scale), float(canonical_level), float(eps), int(acc), gp, L.stream()),
+            "roi_align_pyramid_backward")
+    for o in out:
+        amax_drop(o)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- ROIPool, deformable PS-RoI pooling
 def roi_pool_forward(feat, rois, spatial_scale, ph, pw, out=None):
     """feat [B,H,W,C], rois [K,5] -> (out [K,ph,pw,C], argmax int32 [K,ph,pw,C]: flat pixel h*W+w of the bin's first maximum, -1 for none);

@@ -132,6 +132,45 @@ int abr_roi_align_backward_gather(const float* grad, const float* rois, int K, i
 int abr_roi_align_taps(const float* rois, int K, int H, int W, float spatial_scale, int PH, int PW,
                        int sampling_ratio, int max_s, int32_t* idx, int32_t* grid, void* stream);
 
+/* Pooling over a feature pyramid: modeling/poolers.py (LevelMapper :11-42, Pooler.forward :80-105), which is Python over _C.roi_align_* in the
+ * reference (per level a nonzero, a row gather, one ROIAlign launch, an indexed write into zeros).  Here one launch each way.
+ *
+ * Level of a row, in fp32 with the reference's operations in its order (IEEE sqrt and division, no contraction):
+ *   area = (x2 - x1 + 1) * (y2 - y1 + 1);  t = floor(canonical_level + log2(sqrt(area) / canonical_scale + eps));
+ *   level = (int)clamp(t, k_min, k_max) - (int)k_min.
+ * A negative or NaN area makes t NaN: that row has NO level, reported as -1; its output row is all zero and it adds nothing to any gradient
+ * (in the reference it matches no level and its row of the zero-filled result stays).  area == 0 is an ordinary row (it clamps to k_min).
+ * Once the level is chosen a row is pooled exactly as abr_roi_align_forward(layout = ABR_NHWC, bin_step = 1) pools it on that level's map
+ * with that level's scale: same taps, weights, association order and /count, so the same bits.
+ *
+ * 1 <= L <= ABR_MAX_PYRAMID_LEVELS; (int)k_max - (int)k_min < L; H[l], W[l] >= 1 with no relation between the levels; any C >= 1;
+ * K * PH * PW * C and every B * H[l] * W[l] * C must fit int32.  feats / grad_feats, H, W and scales are HOST arrays of L entries that the call
+ * copies into the kernel's arguments: there is no device-side table and nothing to keep alive after the call returns.
+ * NOT provided for pyramids: an atomic-free gather backward like abr_roi_align_backward_gather, bin_step = 2, NCHW memory, float64. */
+#define ABR_MAX_PYRAMID_LEVELS 8
+
+/* rois [K,5] -> levels [K] int32 in 0 .. (int)k_max - (int)k_min, or -1 for a row without a level */
+int abr_fpn_levels(const float* rois, int K, float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
+                   int32_t* levels, void* stream);
+
+/* feats_host[l] = device pointer of level l's map [B,H[l],W[l],C] (NHWC fp32); out [K,PH,PW,C]; levels_out [K] int32 or NULL.
+ * K == 0 launches nothing. */
+int abr_roi_align_pyramid_forward(const float* const* feats_host, const int* H_host, const int* W_host, const float* scales_host, int L,
+                                  const float* rois, int K, int B, int C, int PH, int PW, int sampling_ratio,
+                                  float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
+                                  float* out, int32_t* levels_out, void* stream);
+
+/* grad [K,PH,PW,C] -> grad_feats_host[l] [B,H[l],W[l],C]: every element of every level, reached by a RoI or not, is written (the sum, or
+ * 0) unless accumulate != 0, then added to (also when K == 0).  One launch over the RoIs scatters each into its level with hardware atomics;
+ * each RoI's addend is computed in fp32 as abr_roi_align_backward computes it, but the atomics add into zeroed float64 scratch that the library
+ * owns (8 bytes per gradient element of all levels, per stream) and a second launch rounds every sum to fp32 once: an element that hundreds of
+ * RoIs reach is then not a float32 sum in arrival order.  The order of the adds still varies from run to run, and with it, rarely, a last bit.
+ * ABR_E_WORKSPACE when the scratch cannot be allocated. */
+int abr_roi_align_pyramid_backward(const float* grad, const float* rois, int K, int B, int C, const int* H_host, const int* W_host,
+                                   const float* scales_host, int L, int PH, int PW, int sampling_ratio,
+                                   float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
+                                   int accumulate, float* const* grad_feats_host, void* stream);
+
 /* _C.roi_pool_forward(input, rois, spatial_scale, pooled_h, pooled_w) -> (output, argmax)
  *   csrc/ROIPool.h:10-24 -> csrc/cuda/ROIPool_cuda.cu:16-77,110-150 (there is no CPU implementation).
  * feat [B,C,H,W] (NCHW) or [B,H,W,C] (NHWC); rois [K,5]; out and argmax [K,C,PH,PW] (NCHW) or [K,PH,PW,C] (NHWC).

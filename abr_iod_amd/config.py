@@ -131,6 +131,10 @@ _C.MODEL.RPN.POST_NMS_TOP_N_TRAIN = 2000
 _C.MODEL.RPN.POST_NMS_TOP_N_TEST = 1000
 _C.MODEL.RPN.NMS_THRESH = 0.7
 _C.MODEL.RPN.MIN_SIZE = 0
+# proposals kept after the cross-level selection of a feature pyramid (rpn/inference.py:149-176); PER_BATCH: in training over the whole batch
+_C.MODEL.RPN.FPN_POST_NMS_TOP_N_TRAIN = 2000
+_C.MODEL.RPN.FPN_POST_NMS_TOP_N_TEST = 2000
+_C.MODEL.RPN.FPN_POST_NMS_PER_BATCH = True
 _C.MODEL.RPN.RPN_HEAD = "SingleConvRPNHead"
 _C.MODEL.RPN.CONV_FREEZE = False
 _C.MODEL.RPN.CLS_FREEZE = False

@@ -25,6 +25,8 @@ enum ScratchSlot {
     SCRATCH_DET,            // det_ws: tickets + ring of partial sums (words: the two ring cursors)
     SCRATCH_TOPK,           // topk.hip (words: capacity in images, capacity in keys)
     SCRATCH_ROI_PYRAMID,    // roi_align.hip: the pyramid backward's float64 sums, every level's map back to back
+    SCRATCH_RPN_PYRAMID,    // rpn_pyramid.hip: the pyramid ranking's histograms, counters, survivors, candidates and keys
+    SCRATCH_RPN_SELECT,     // rpn_pyramid.hip: the cross-level selection's candidate words and thresholds
 };
 // process-wide zero-initialised words
 enum WordSlot { WORDS_X6_FLAGS, WORDS_H3_STATS, WORDS_AMAX_RING, WORDS_SLOTS };

@@ -1,6 +1,6 @@
 """Region Proposal Network on the HIP library.
 
-Mirrors, for the single-level C4 case every configs/voc YAML uses:
+Mirrors, for the single-level C4 case every configs/voc YAML uses (anchors and proposal selection also over a feature pyramid):
     AnchorGenerator          maskrcnn_benchmark/modeling/rpn/anchor_generator.py:34-123, 215-284
     RPNHead                  modeling/rpn/rpn.py:70-121  (conv3x3+ReLU, cls_logits 1x1, bbox_pred 1x1)
     RPNPostProcessor         modeling/rpn/inference.py:14-147
@@ -91,40 +91,61 @@ class LazyProposals(object):
 class AnchorGenerator(nn.Module):
     def __init__(self, sizes=(128, 256, 512), aspect_ratios=(0.5, 1.0, 2.0), anchor_strides=(8, 16, 32), straddle_thresh=0):
         super().__init__()
-        assert len(anchor_strides) == 1, "single feature level (C4) only: FPN is out of scope (no voc config uses it)"
+        if len(anchor_strides) == 1:
+            cells = [generate_anchors(anchor_strides[0], sizes, aspect_ratios)]
+        else:                                 # a feature pyramid: one cell-anchor set per level (anchor_generator.py:49-71)
+            if len(anchor_strides) != len(sizes):
+                raise RuntimeError("FPN should have #anchor_strides == #sizes")
+            cells = [generate_anchors(st, s if isinstance(s, (tuple, list)) else (s,), aspect_ratios) for st, s in zip(anchor_strides, sizes)]
         self.strides = anchor_strides
         self.straddle_thresh = straddle_thresh
-        self.register_buffer("cell_anchors", generate_anchors(anchor_strides[0], sizes, aspect_ratios))
+        self.register_buffer("cell_anchors", cells[0])
+        for l, c in enumerate(cells[1:], 1):  # (level 0 keeps the single-level name)
+            self.register_buffer("cell_anchors_%d" % l, c)
         self._cache = {}
 
-    def num_anchors_per_location(self):
-        return [self.cell_anchors.shape[0]]
+    def level_cell_anchors(self, level):
+        return self.cell_anchors if level == 0 else getattr(self, "cell_anchors_%d" % level)
 
-    def grid(self, H, W, image_hw):
-        """([H*W*A,4] anchors, [H*W*A] uint8 visibility) for one image size; cached on device."""
-        key = (H, W, int(image_hw[0]), int(image_hw[1]), self.cell_anchors.device)
+    def num_anchors_per_location(self):
+        return [self.level_cell_anchors(l).shape[0] for l in range(len(self.strides))]
+
+    def grid(self, H, W, image_hw, level=0):
+        """([H*W*A,4] anchors, [H*W*A] uint8 visibility) of one level for one image size; cached on device."""
+        cell = self.level_cell_anchors(level)
+        lv = (level,) if level else ()
+        key = (H, W, int(image_hw[0]), int(image_hw[1]), cell.device) + lv
         hit = self._cache.get(key)
         if hit is None:
-            a, vis = ops.grid_anchors(self.cell_anchors, H, W, self.strides[0], int(image_hw[0]), int(image_hw[1]), self.straddle_thresh)
+            a, vis = ops.grid_anchors(cell, H, W, self.strides[level], int(image_hw[0]), int(image_hw[1]), self.straddle_thresh)
             # the boxes depend on (H, W) only, the visibility also on the image size: share ONE box tensor per grid
-            a = self._cache.setdefault((H, W, self.cell_anchors.device), a)
+            a = self._cache.setdefault((H, W, cell.device) + lv, a)
             hit = self._cache[key] = (a, vis, vis.bool())   # uint8 for the kernels, bool for the reference-typed BoxList field: made once
         return hit
 
     def forward(self, image_list, feature_maps):
-        H, W = feature_maps[0].shape[-2:]
+        assert len(feature_maps) == len(self.strides), "one feature map per anchor stride"
+        grids = [f.shape[-2:] for f in feature_maps]
         anchors = []
         for (ih, iw) in image_list.image_sizes:
-            a, vis, vis_bool = self.grid(H, W, (ih, iw))
-            bl = BoxList(a, (iw, ih), mode="xyxy")
-            bl.add_field("visibility", vis_bool)
-            bl._visibility_u8 = vis                   # the same mask as the kernels read it (no per-step dtype round trip)
-            anchors.append([bl])
+            per_level = []
+            for l, (H, W) in enumerate(grids):
+                a, vis, vis_bool = self.grid(H, W, (ih, iw), l)
+                bl = BoxList(a, (iw, ih), mode="xyxy")
+                bl.add_field("visibility", vis_bool)
+                bl._visibility_u8 = vis                   # the same mask as the kernels read it (no per-step dtype round trip)
+                per_level.append(bl)
+            anchors.append(per_level)
         return anchors
 
 
 def make_anchor_generator(cfg):
-    return AnchorGenerator(cfg.MODEL.RPN.ANCHOR_SIZES, cfg.MODEL.RPN.ASPECT_RATIOS, cfg.MODEL.RPN.ANCHOR_STRIDE, cfg.MODEL.RPN.STRADDLE_THRESH)
+    sizes, strides = cfg.MODEL.RPN.ANCHOR_SIZES, cfg.MODEL.RPN.ANCHOR_STRIDE
+    if cfg.MODEL.RPN.USE_FPN:
+        assert len(strides) == len(sizes), "FPN should have len(ANCHOR_STRIDE) == len(ANCHOR_SIZES)"
+    else:
+        assert len(strides) == 1, "Non-FPN should have a single ANCHOR_STRIDE"
+    return AnchorGenerator(sizes, cfg.MODEL.RPN.ASPECT_RATIOS, strides, cfg.MODEL.RPN.STRADDLE_THRESH)
 
 
 # ------------------------------------------------------------------------------------------------ head
@@ -277,6 +298,8 @@ class RPNPostProcessor(nn.Module):
         self.pre_nms_top_n, self.post_nms_top_n = pre_nms_top_n, post_nms_top_n
         self.nms_thresh, self.min_size = nms_thresh, min_size
         self.box_coder = box_coder if box_coder is not None else BoxCoder(weights=(1.0, 1.0, 1.0, 1.0))
+        self.fpn_post_nms_top_n = post_nms_top_n if fpn_post_nms_top_n is None else fpn_post_nms_top_n
+        self.fpn_post_nms_per_batch = fpn_post_nms_per_batch
 
     def add_gt_proposals(self, proposals, targets):
         out = []
@@ -290,7 +313,13 @@ class RPNPostProcessor(nn.Module):
 
     def launch(self, anchors, fused, num_anchors):
         """Device half of forward_fused: top-k -> decode -> clip -> NMS, all enqueued on the CURRENT stream, nothing read back.
-        Returns the pending state for `collect`."""
+        Returns the pending state for `collect`.  A list of several levels' outputs, or MIN_SIZE > 0, goes through `launch_pyramid`."""
+        if isinstance(fused, (list, tuple)):
+            if len(fused) > 1 or self.min_size > 0:
+                return self.launch_pyramid(anchors, fused, num_anchors)
+            fused = fused[0]
+        elif self.min_size > 0:
+            return self.launch_pyramid(anchors, [fused], num_anchors)
         y = as_nhwc(fused)
         N, H, W, Cf = y.shape
         A = num_anchors
@@ -310,31 +339,80 @@ class RPNPostProcessor(nn.Module):
             img_hw = self._hw_cache[hw_key] = ops.h2d([list(v) for v in hw_key[0]], torch.int32, y.device)
         assert same, "per-image anchor grids of one batch share (H,W): they differ only in the visibility field"
         props = ops.rpn_decode_clip(yf, A, anchors[0][0].bbox, topk_idx, img_hw, self.box_coder.weights, A=A)  # :101-112
-        counts = torch.full((N,), k, dtype=torch.int32, device=y.device)
-        if self.min_size > 0:  # remove_small_boxes (boxlist_ops.py:34-48): with MIN_SIZE=0 (every voc config) nothing is dropped
-            raise NotImplementedError("RPN.MIN_SIZE > 0 is not used by any configs/voc YAML")
+        counts = torch.full((N,), k, dtype=torch.int32, device=y.device)   # (MIN_SIZE == 0 here: remove_small_boxes drops nothing)
         keep, n_keep = ops.nms_sorted_batched(props, counts, self.nms_thresh, self.post_nms_top_n)     # :113-116
         return dict(props=props, scores=scores, keep=keep, n_keep=n_keep, sizes=[a[0].size for a in anchors], fused=yf)
+
+    def _img_hw(self, anchors, device):
+        """[N,2] int32 (h, w) on the device; image sizes repeat from step to step, so the copy is kept"""
+        hw_key = (tuple((a[0].size[1], a[0].size[0]) for a in anchors), device)
+        img_hw = self._hw_cache.get(hw_key)
+        if img_hw is None:
+            if len(self._hw_cache) > 64:
+                self._hw_cache.clear()
+            img_hw = self._hw_cache[hw_key] = ops.h2d([list(v) for v in hw_key[0]], torch.int32, device)
+        return img_hw
+
+    def launch_pyramid(self, anchors, fused, num_anchors):
+        """`launch` for L levels (inference.py:120-176) and for MIN_SIZE > 0: every (image, level) segment goes through ranking, decode + clip +
+        remove_small_boxes, NMS and the cross-level selection together, on the CURRENT stream, nothing read back (ops.rpn_pyramid_*).
+        fused: list of L logical [N,5A(+pad),H_l,W_l]; anchors: list (per image) of L BoxLists."""
+        ys = [as_nhwc(f) for f in fused]
+        nL, N, dev = len(ys), ys[0].shape[0], ys[0].device
+        yfs = [y.reshape(N, y.shape[1] * y.shape[2], y.shape[3]) for y in ys]
+        As = [num_anchors] * nL if isinstance(num_anchors, int) else list(num_anchors)
+        for l in range(nL):
+            assert all(a[l].bbox.data_ptr() == anchors[0][l].bbox.data_ptr() for a in anchors), \
+                "per-image anchor grids of one batch share (H,W): they differ only in the visibility field"
+        grids = [anchors[0][l].bbox for l in range(nL)]
+        img_hw = self._img_hw(anchors, dev)
+        ks = ops.rpn_pyramid_ks(yfs, As, self.pre_nms_top_n)
+        if max(ks) <= ops.rpn_pyramid_max_k():
+            scores, topk_idx = ops.rpn_pyramid_topk(yfs, As, self.pre_nms_top_n)                       # :87-96, all levels at once
+        else:   # beyond the pyramid ranking's in-LDS sort: the single-level operator, level by level, into the same tables
+            scores = torch.zeros((N, nL, max(ks)), dtype=torch.float32, device=dev)
+            topk_idx = torch.zeros((N, nL, max(ks)), dtype=torch.int64, device=dev)
+            for l, (yf, A, k) in enumerate(zip(yfs, As, ks)):
+                if k <= 15360 and yf.shape[1] * A <= 196608:
+                    s_l, i_l = ops.topk_sigmoid(yf, A, k)
+                else:
+                    s_l, i_l = yf[:, :, :A].reshape(N, -1).sigmoid().topk(k, dim=1, sorted=True)
+                scores[:, l, :k], topk_idx[:, l, :k] = s_l, i_l
+        props, scores, counts = ops.rpn_pyramid_decode(yfs, As, grids, topk_idx, scores, img_hw, self.pre_nms_top_n, self.box_coder.weights,
+                                                       self.min_size)                                  # :96-112 + remove_small_boxes
+        keep, n_keep = ops.nms_sorted_batched(props, counts, self.nms_thresh, self.post_nms_top_n)     # :113-116, N*L segments
+        # one level: no cross-level cut (:139-140), the selection below then only gathers the kept rows
+        fpn_post = self.fpn_post_nms_top_n if nL > 1 else self.post_nms_top_n
+        rois, out_scores, src, n_out = ops.rpn_pyramid_select(props, scores, keep, n_keep, N, fpn_post,
+                                                              self.training and self.fpn_post_nms_per_batch and nL > 1)   # :149-176
+        return dict(rois=rois, objectness=out_scores, src=src, n_out=n_out, sizes=[a[0].size for a in anchors], fused=yfs)
 
     def collect(self, pending, targets=None):
         """Host half: read the per-image keep counts (the only host sync of the proposal path; the reference syncs inside every
         nms call) and cut the BoxLists."""
+        counts = "n_out" if "n_out" in pending else "n_keep"     # (the pyramid path's pending state, or the single-level one)
         side = pending.get("stream")
         if side is not None:
             # read the counts ON THE SIDE STREAM: the copy then waits for the selection only, not for whatever the caller has queued
             # on the main stream in the meantime (a main-stream read-back would stall the host behind all of it)
             with torch.cuda.stream(side):
-                nk = pending["n_keep"].tolist()
+                nk = pending[counts].tolist()
             self.join(pending)
         else:
-            nk = pending["n_keep"].tolist()
-        props, scores, keep = pending["props"], pending["scores"], pending["keep"]
+            nk = pending[counts].tolist()
         result = []
-        for i, size in enumerate(pending["sizes"]):
-            ki = keep[i, : nk[i]].long()
-            b = BoxList(props[i].index_select(0, ki), size, mode="xyxy")
-            b.add_field("objectness", scores[i].index_select(0, ki))
-            result.append(b)
+        if counts == "n_out":
+            for i, size in enumerate(pending["sizes"]):
+                b = BoxList(pending["rois"][i, : nk[i]], size, mode="xyxy")
+                b.add_field("objectness", pending["objectness"][i, : nk[i]])
+                result.append(b)
+        else:
+            props, scores, keep = pending["props"], pending["scores"], pending["keep"]
+            for i, size in enumerate(pending["sizes"]):
+                ki = keep[i, : nk[i]].long()
+                b = BoxList(props[i].index_select(0, ki), size, mode="xyxy")
+                b.add_field("objectness", scores[i].index_select(0, ki))
+                result.append(b)
         if self.training and targets is not None:
             result = self.add_gt_proposals(result, targets)                               # :144-145
         return result
@@ -343,12 +421,14 @@ class RPNPostProcessor(nn.Module):
         """`launch` on a side stream: the selection is a chain of latency-bound kernels (a 1024-thread top-k and a one-workgroup-per-
         image NMS sweep, ~0.9 ms with a handful of CUs busy) that has no consumer until `collect`, so it runs NEXT to whatever the
         caller enqueues on the current stream meanwhile (the RPN loss; for the frozen source model, the target's whole backbone)."""
+        maps = list(fused) if isinstance(fused, (list, tuple)) else [fused]
         cur = torch.cuda.current_stream()
-        side = ops.side_stream((fused.device.index, tag))
+        side = ops.side_stream((maps[0].device.index, tag))
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             pending = self.launch(anchors, fused, num_anchors)
-        fused.record_stream(side)
+        for f in maps:
+            f.record_stream(side)
         pending["stream"] = side
         return pending
 
@@ -358,24 +438,29 @@ class RPNPostProcessor(nn.Module):
         if side is not None:
             cur = torch.cuda.current_stream()
             cur.wait_stream(side)
-            for k in ("props", "scores", "keep", "n_keep"):
-                pending[k].record_stream(cur)
+            for k in ("props", "scores", "keep", "n_keep", "rois", "objectness", "src", "n_out"):
+                if k in pending:
+                    pending[k].record_stream(cur)
         return pending
 
     def forward_fused(self, anchors, fused, num_anchors, targets=None):
-        """fused: logical [N,5A(+pad),H,W] head output.  anchors: list (per image) of [BoxList] as AnchorGenerator returns."""
+        """fused: logical [N,5A(+pad),H,W] head output, or the list of L of them.  anchors: list (per image) of the levels' BoxLists as
+        AnchorGenerator returns."""
         return self.collect(self.launch(anchors, fused, num_anchors), targets)
 
     def forward(self, anchors, objectness, box_regression, targets=None):
-        """reference signature (lists of logical [N,A,H,W] / [N,4A,H,W]); re-fuses the two tensors (compat path)."""
-        fused = torch.cat((objectness[0], box_regression[0]), 1)
-        return self.forward_fused(anchors, fused, objectness[0].shape[1], targets)
+        """reference signature (lists of L logical [N,A,H,W] / [N,4A,H,W]); re-fuses the two tensors of every level (compat path)."""
+        assert len(objectness) == len(box_regression) and all(len(a) == len(objectness) for a in anchors), "one entry per feature level"
+        fused = [torch.cat((o, b), 1) for o, b in zip(objectness, box_regression)]
+        return self.forward_fused(anchors, fused if len(fused) > 1 else fused[0], objectness[0].shape[1], targets)
 
 
 def make_rpn_postprocessor(config, rpn_box_coder, is_train):
     pre = config.MODEL.RPN.PRE_NMS_TOP_N_TRAIN if is_train else config.MODEL.RPN.PRE_NMS_TOP_N_TEST
     post = config.MODEL.RPN.POST_NMS_TOP_N_TRAIN if is_train else config.MODEL.RPN.POST_NMS_TOP_N_TEST
-    return RPNPostProcessor(pre, post, config.MODEL.RPN.NMS_THRESH, config.MODEL.RPN.MIN_SIZE, rpn_box_coder)
+    fpn_post = config.MODEL.RPN.FPN_POST_NMS_TOP_N_TRAIN if is_train else config.MODEL.RPN.FPN_POST_NMS_TOP_N_TEST
+    return RPNPostProcessor(pre, post, config.MODEL.RPN.NMS_THRESH, config.MODEL.RPN.MIN_SIZE, rpn_box_coder, fpn_post,
+                            config.MODEL.RPN.FPN_POST_NMS_PER_BATCH)
 
 
 # ------------------------------------------------------------------------------------------------ loss
@@ -496,7 +581,11 @@ class RPNModule(nn.Module):
         super().__init__()
         self.cfg = cfg.clone()
         self.anchor_generator = make_anchor_generator(cfg)
-        self.head = RPNHead(cfg, in_channels, self.anchor_generator.num_anchors_per_location()[0])
+        per_level = self.anchor_generator.num_anchors_per_location()
+        if len(set(per_level)) != 1:   # rpn.py:150-152: ONE head is shared by the levels of a pyramid
+            raise ValueError("the RPN head is shared by all feature levels, so every level needs the same number of anchors per location; "
+                             "ANCHOR_SIZES / ASPECT_RATIOS give %s" % (per_level,))
+        self.head = RPNHead(cfg, in_channels, per_level[0])
         rpn_box_coder = BoxCoder(weights=(1.0, 1.0, 1.0, 1.0))
         self.box_selector_train = make_rpn_postprocessor(cfg, rpn_box_coder, is_train=True)
         self.box_selector_test = make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False)
@@ -505,11 +594,18 @@ class RPNModule(nn.Module):
     def forward(self, images, features, targets=None, rpn_output_source=None, defer_proposals=False):
         """-> ((boxes, losses), anchors, rpn_output) exactly as rpn.py:161-183."""
         if self.training:
+            if len(features) > 1:
+                raise NotImplementedError("training the RPN on %d feature levels needs the multi-level RPN loss (rpn/loss.py over the "
+                                          "concatenated levels), which is not implemented; eval() selects proposals over a pyramid" % len(features))
             return self.forward_finish(self.forward_begin(images, features, targets, rpn_output_source))
-        fused = self.head.forward_fused(features[0])
         A = self.head.num_anchors
+        if len(features) > 1:   # a feature pyramid: the shared head per level, the multi-level selector (rpn.py:161-183, inference.py:120-176)
+            fused = [self.head.forward_fused(f) for f in features]
+            rpn_output = ([f[:, :A] for f in fused], [f[:, A:5 * A] for f in fused])
+        else:
+            fused = self.head.forward_fused(features[0])
+            rpn_output = ([fused[:, :A]], [fused[:, A:5 * A]])
         anchors = self.anchor_generator(images, features)
-        rpn_output = ([fused[:, :A]], [fused[:, A:5 * A]])
         self.box_selector_test.eval()
         if defer_proposals:   # the caller collects later (GeneralizedRCNN.soften_begin / soften_finish)
             pending = self.box_selector_test.launch_on_side_stream(anchors, fused, A, tag="source-proposals")
@@ -537,7 +633,7 @@ class RPNModule(nn.Module):
     def forward_finish(self, state):
         with torch.no_grad():
             # training: hand the box head the selector's RAW device output (LazyProposals) instead of per-image BoxLists cut on the host
-            if state["pending"]["props"].is_cuda and state["targets"] is not None:
+            if "props" in state["pending"] and state["pending"]["props"].is_cuda and state["targets"] is not None:
                 boxes = LazyProposals(self.box_selector_train, state["pending"], state["targets"])
             else:
                 boxes = self.box_selector_train.collect(state["pending"], state["targets"])

@@ -1466,6 +1466,90 @@ def rpn_decode_clip(reg, reg_col0, anchors, idx, img_hw, weights=(1.0, 1.0, 1.0,
     return out
 
 
+def rpn_pyramid_max_k():
+    """most anchors abr_rpn_pyramid_topk ranks per (image, level): its in-LDS sort (2048)"""
+    return L.lib().abr_rpn_pyramid_max_k()
+
+
+def _rpn_pyramid_tables(what, ys, As, anchors=None):
+    """the host arrays of the RPN pyramid entry points: ys = list of contiguous fp32 [N, nloc_l, ld_l] device tensors (fused head outputs)"""
+    n = len(ys)
+    if not 1 <= n <= MAX_PYRAMID_LEVELS:
+        raise RuntimeError(f"{what}: {n} levels, need 1 .. {MAX_PYRAMID_LEVELS}")
+    if len(As) != n or (anchors is not None and len(anchors) != n):
+        raise RuntimeError(f"{what}: the level lists differ in length")
+    for l, y in enumerate(ys):
+        L.require_cuda(y)
+        if y.dtype != _f32 or y.dim() != 3 or not y.is_contiguous() or y.shape[0] != ys[0].shape[0]:
+            raise RuntimeError(f"{what}: level {l} must be a contiguous float32 [N,nloc,ld] tensor with the batch of level 0, got {tuple(y.shape)} {y.dtype}")
+    if anchors is not None:
+        for l, a in enumerate(anchors):
+            L.require_cuda(a)
+            if a.dtype != _f32 or not a.is_contiguous() or tuple(a.shape) != (ys[l].shape[1] * As[l], 4):
+                raise RuntimeError(f"{what}: anchors of level {l} must be a contiguous float32 [{ys[l].shape[1] * As[l]},4] tensor, got {tuple(a.shape)}")
+    return ((C.c_void_p * n)(*[y.data_ptr() for y in ys]), (C.c_int * n)(*[y.shape[1] for y in ys]), (C.c_int * n)(*[int(a) for a in As]),
+            (C.c_int * n)(*[y.shape[2] for y in ys]), (C.c_void_p * n)(*[a.data_ptr() for a in anchors]) if anchors is not None else None)
+
+
+def rpn_pyramid_ks(ys, As, pre_nms_top_n):
+    """k_l = min(pre_nms_top_n, nloc_l * A_l) of every level"""
+    return [min(int(pre_nms_top_n), y.shape[1] * int(a)) for y, a in zip(ys, As)]
+
+
+def rpn_pyramid_topk(ys, As, pre_nms_top_n):
+    """ys: list of L fused head outputs [N, nloc_l, ld_l] -> (scores [N,L,k_max], idx [N,L,k_max] int64 level-local anchor ids): per (image, level)
+    the k_l largest sigmoid(logit) as topk_sigmoid orders them, entries past k_l zero; three launches whatever N and L are."""
+    ys = list(ys)
+    yp, nl, Ap, ld, _ = _rpn_pyramid_tables("rpn_pyramid_topk", ys, As)
+    N, k_max = ys[0].shape[0], max(rpn_pyramid_ks(ys, As, pre_nms_top_n))
+    scores = torch.empty((N, len(ys), k_max), dtype=_f32, device=ys[0].device)
+    idx = torch.empty((N, len(ys), k_max), dtype=torch.int64, device=ys[0].device)
+    L.check(L.lib().abr_rpn_pyramid_topk(yp, nl, Ap, ld, len(ys), N, int(pre_nms_top_n), k_max, L.ptr(scores), L.ptr(idx), L.stream()), "rpn_pyramid_topk")
+    return scores, idx
+
+
+def rpn_pyramid_decode(ys, As, anchors, idx, scores, img_hw, pre_nms_top_n, weights=(1.0, 1.0, 1.0, 1.0), min_size=0):
+    """idx / scores [N,L,k_max] from rpn_pyramid_topk, anchors: list of [nloc_l*A_l,4], img_hw [N,2] int32 -> (props [N*L,k_max,4],
+    scores [N*L,k_max], counts [N*L] int32): decode + clip + remove_small_boxes, survivors in rank order without holes; one launch."""
+    ys = list(ys)
+    yp, nl, Ap, ld, ap = _rpn_pyramid_tables("rpn_pyramid_decode", ys, As, list(anchors))
+    L.require_cuda(idx, scores, img_hw)
+    N, nL, k_max = idx.shape
+    assert nL == len(ys) and N == ys[0].shape[0] and idx.dtype == torch.int64 and idx.is_contiguous() and scores.is_contiguous()
+    assert img_hw.dtype == torch.int32 and tuple(img_hw.shape) == (N, 2) and img_hw.is_contiguous()
+    dev = ys[0].device
+    props = torch.empty((N * nL, k_max, 4), dtype=_f32, device=dev)
+    out_scores = torch.empty((N * nL, k_max), dtype=_f32, device=dev)
+    counts = torch.empty((N * nL,), dtype=torch.int32, device=dev)
+    L.check(L.lib().abr_rpn_pyramid_decode(yp, nl, Ap, ld, ap, nL, N, int(pre_nms_top_n), k_max, L.ptr(idx), L.ptr(scores), L.ptr(img_hw),
+                                           *[float(v) for v in weights], float(min_size), L.ptr(props), L.ptr(out_scores), L.ptr(counts), L.stream()),
+            "rpn_pyramid_decode")
+    return props, out_scores, counts
+
+
+def rpn_pyramid_select(props, scores, keep, n_keep, N, fpn_post_n, per_batch):
+    """props [N*L,k_max,4], scores [N*L,k_max], keep [N*L,post] int32, n_keep [N*L] int32 (nms_sorted_batched over the segments) ->
+    (rois [N,cap,4], scores [N,cap], src [N,cap] int32 candidate positions level*post+rank, n_out [N] int32), cap = min(fpn_post_n, L*post):
+    per image the fpn_post_n best by descending score, or (per_batch) the batch's fpn_post_n best in candidate order; three launches."""
+    L.require_cuda(props, scores, keep, n_keep)
+    S, k_max = scores.shape
+    post = keep.shape[1]
+    assert N >= 0 and (S % N == 0 if N else S == 0) and tuple(props.shape) == (S, k_max, 4) and keep.shape[0] == S and n_keep.shape[0] == S
+    assert props.dtype == _f32 and scores.dtype == _f32 and keep.dtype == torch.int32 and n_keep.dtype == torch.int32
+    assert props.is_contiguous() and scores.is_contiguous() and keep.is_contiguous() and n_keep.is_contiguous()
+    nL = S // N if N else 1
+    cap = min(int(fpn_post_n), nL * post)
+    dev = props.device
+    rois = torch.empty((N, cap, 4), dtype=_f32, device=dev)
+    out_scores = torch.empty((N, cap), dtype=_f32, device=dev)
+    src = torch.empty((N, cap), dtype=torch.int32, device=dev)
+    n_out = torch.empty((N,), dtype=torch.int32, device=dev)
+    L.check(L.lib().abr_rpn_pyramid_select(L.ptr(props), L.ptr(scores), L.ptr(keep), L.ptr(n_keep), N, nL, k_max, post, int(fpn_post_n),
+                                           1 if per_batch else 0, L.ptr(rois), L.ptr(out_scores), L.ptr(src), L.ptr(n_out), L.stream()),
+            "rpn_pyramid_select")
+    return rois, out_scores, src, n_out
+
+
 def match_encode(boxes, gt, gt_labels, vis, hi, lo, allow_low_quality, weights, rpn_labels):
     """-> matched int64 [n], labels (fp32 RPN / int64 head) [n], reg_targets [n,4]"""
     boxes, gt = L.f32c(boxes), L.f32c(gt)

@@ -25,6 +25,10 @@ def reference_state_dict(model):
             # the reference registers its cell anchors through a BufferList (rpn/anchor_generator.py:13-31, 61): one buffer per level
             out[name.replace("cell_anchors", "cell_anchors.0")] = b.detach().clone()
             continue
+        head, _, level = name.rpartition("cell_anchors_")
+        if _ and level.isdigit():   # the further levels of a feature pyramid's generator
+            out[head + "cell_anchors." + level] = b.detach().clone()
+            continue
         out[name] = b.detach().clone()
     if "mask" in getattr(model, "roi_heads", {}):
         # the reference registers the SHARED feature extractor under the mask head too (roi_heads.py:18-21): its state_dict repeats every key

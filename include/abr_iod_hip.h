@@ -588,6 +588,38 @@ int abr_det_select(const float* prob, const float* boxes, const int32_t* row_off
 int abr_rpn_decode_clip(const float* reg, int reg_stride, int reg_col0, int A, const float* anchors,
                         const int64_t* idx, int N, int n_anchor, int k, const int32_t* img_hw, float wx,
                         float wy, float ww, float wh, float* out, void* stream);
+/* RPN proposal selection over a feature pyramid (rpn/inference.py:76-118 per level, :120-176 across the levels), S = N * L (image, level)
+ * segments, segment s = i * L + l, through every stage together and nothing read back (csrc/rpn_pyramid.hip):
+ *   abr_rpn_pyramid_topk -> abr_rpn_pyramid_decode -> abr_nms_sorted_batched(props, counts, S, k_max, thr, 0, post, ...) -> abr_rpn_pyramid_select.
+ * y_host[l] = device pointer of level l's fused head output [N, nloc[l], ld[l]] (row = location; columns 0 .. A[l]-1 the logits of anchors
+ * loc * A + a, columns A[l] + 4a .. +3 their deltas, further columns never read); y_host, nloc_host, A_host, ld_host, anchors_host are HOST arrays
+ * of L entries copied into the kernels' arguments.  1 <= L <= ABR_MAX_PYRAMID_LEVELS; k_l = min(pre_nms_top_n, nloc[l] * A[l]) and k_max = max k_l,
+ * else an error; the ranking (not the decode) also needs k_l <= abr_rpn_pyramid_max_k() (2048: the in-LDS sort, 32 KB of LDS per workgroup) --
+ * beyond it a caller ranks level by level with abr_topk_sigmoid into the same tables; the keys of all levels, N * L * k_max * 4 and
+ * N * L * post must fit int32.  N == 0 launches nothing.  The number of launches does not depend on N or L. */
+int abr_rpn_pyramid_max_k(void);
+/* scores [N,L,k_max] fp32, idx [N,L,k_max] int64 level-local anchor ids: per segment the k_l largest sigmoid(logit), descending, equal scores by
+ * ascending index -- bit for bit what abr_topk_sigmoid returns for that level alone; entries k_l .. k_max-1 are 0. */
+int abr_rpn_pyramid_topk(const float* const* y_host, const int* nloc_host, const int* A_host, const int* ld_host, int L, int N, int pre_nms_top_n,
+                         int k_max, float* scores, int64_t* idx, void* stream);
+/* BoxCoder.decode + clip_to_image of the ranked anchors with abr_rpn_decode_clip's arithmetic (ld[l] >= 5 A[l]; anchors_host[l] = device [nloc*A,4]),
+ * then remove_small_boxes (boxlist_ops.py:34-48: keep iff x2-x1+1 >= min_size and y2-y1+1 >= min_size; min_size <= 0 keeps every row) and a stable
+ * compaction: props [S,k_max,4] / scores_out [S,k_max] hold each segment's survivors in rank order without holes (rows past the count: 0),
+ * counts [S] int32 (device; may be 0).  img_hw [N,2] int32 (h, w). */
+int abr_rpn_pyramid_decode(const float* const* y_host, const int* nloc_host, const int* A_host, const int* ld_host, const float* const* anchors_host,
+                           int L, int N, int pre_nms_top_n, int k_max, const int64_t* idx, const float* scores_in, const int32_t* img_hw, float wx,
+                           float wy, float ww, float wh, float min_size, float* props, float* scores_out, int32_t* counts, void* stream);
+/* select_over_all_levels (inference.py:149-176).  keep [S,post] / n_keep [S] = abr_nms_sorted_batched's output over props / scores [S,k_max,..].
+ * Candidates of image i: its levels' NMS survivors in level order, each level in keep order; candidate position p = level * post + rank.
+ *   mode 0 (test, or training per image): the min(fpn_post_n, #candidates) highest scores per image, emitted by descending score;
+ *   mode 1 (training per batch): the min(fpn_post_n, #candidates of all images) highest scores of the batch; every image emits its chosen
+ *          candidates in candidate order (the reference indexes with a mask).
+ * torch.topk leaves a tie group's members undefined; here equal scores go by ascending candidate position, image-major in mode 1.  The cut is an
+ * exact radix selection on (order-preserving score key, position), so no result depends on the order in which atomics were won.
+ * cap = min(fpn_post_n, L * post) (<= 4096 in mode 0: the in-LDS sort): rois [N,cap,4], out_scores [N,cap], src [N,cap] int32 = p (-1 past the
+ * count), n_out [N] int32.  Scores may be any non-NaN fp32. */
+int abr_rpn_pyramid_select(const float* props, const float* scores, const int32_t* keep, const int32_t* n_keep, int N, int L, int k_max, int post,
+                           int fpn_post_n, int mode, float* rois, float* out_scores, int32_t* src, int32_t* n_out, void* stream);
 /* BoxCoder.encode row-wise (box_coder.py:22-50): out[i] = encode(gt[i], ex[i]); img_hw==NULL above = decode without clip */
 int abr_box_encode(const float* gt, const float* ex, int n, float wx, float wy, float ww, float wh, float* out,
                    void* stream);

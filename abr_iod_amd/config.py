@@ -98,6 +98,14 @@ _C.DATALOADER.SIZE_DIVISIBILITY = 0
 _C.MODEL.BACKBONE = CN()
 _C.MODEL.BACKBONE.CONV_BODY = "R-50-C4"
 _C.MODEL.BACKBONE.FREEZE_CONV_BODY_AT = 2
+# the FPN bodies' freezes (defaults.py:108-111; backbone.py:46-61): every backbone parameter / every parameter with "fpn" in its name
+_C.MODEL.BACKBONE.ALL_FREEZE = False
+_C.MODEL.BACKBONE.FPN_FREEZE = False
+
+# the FPN neck's conv block (defaults.py:116-118): plain convs only, either key set raises in build_backbone
+_C.MODEL.FPN = CN()
+_C.MODEL.FPN.USE_GN = False
+_C.MODEL.FPN.USE_RELU = False
 
 _C.MODEL.RESNETS = CN()
 _C.MODEL.RESNETS.NUM_GROUPS = 1

@@ -1,4 +1,4 @@
-"""ResNet C4 bodies (R-50-C4, R-101-C4) and the C5 head on the HIP conv engine.
+"""ResNet C4 bodies (R-50-C4, R-101-C4), the FPN bodies' C2..C5 trunk (R-50/101/152-FPN) and the C5 head on the HIP conv engine.
 
 Mirror of maskrcnn_benchmark/modeling/backbone/resnet.py for the C4 bodies of the reference's backbone registry (backbone.py:12-15)
 (CONV_BODY "R-50-C4", the configs/voc default, and "R-101-C4": layer3 has 23 blocks instead of 6; BottleneckWithFixedBatchNorm,
@@ -31,19 +31,36 @@ StageSpec = namedtuple("StageSpec", ["index", "block_count", "return_features"])
 ResNet50StagesTo4 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, False), (2, 4, False), (3, 6, True)))
 ResNet50StagesTo5 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, False), (2, 4, False), (3, 6, False), (4, 3, True)))
 ResNet101StagesTo4 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, False), (2, 4, False), (3, 23, True)))
+ResNet50FPNStagesTo5 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, True), (2, 4, True), (3, 6, True), (4, 3, True)))
+ResNet101FPNStagesTo5 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, True), (2, 4, True), (3, 23, True), (4, 3, True)))
+ResNet152FPNStagesTo5 = tuple(StageSpec(index=i, block_count=c, return_features=r) for (i, c, r) in ((1, 3, True), (2, 8, True), (3, 36, True), (4, 3, True)))
 
-# CONV_BODY -> the body's stages: the C4 entries of the reference's _STAGE_SPECS (resnet.py:443-453).  The C5 bodies would feed C5 into the
-# detector's layer4 head, and the FPN bodies' forward returns a tuple FPN cannot take (resnet.py:145-155): neither makes a working detector there.
-STAGE_SPECS = {"R-50-C4": ResNet50StagesTo4, "R-101-C4": ResNet101StagesTo4}
+# CONV_BODY -> the body's stages: the C4 and FPN entries of the reference's _STAGE_SPECS (resnet.py:443-453).  The C5 bodies would feed C5 into the
+# detector's layer4 head: no working detector there.  The FPN bodies' forward returns (outputs, backbone_features), a pair the reference's
+# nn.Sequential(body, fpn) hands to FPN.forward whole (resnet.py:145-155): build_backbone here gives the FPN `outputs` (backbone.py).
+STAGE_SPECS = {"R-50-C4": ResNet50StagesTo4, "R-101-C4": ResNet101StagesTo4,
+               "R-50-FPN": ResNet50FPNStagesTo5, "R-101-FPN": ResNet101FPNStagesTo5, "R-152-FPN": ResNet152FPNStagesTo5}
+FPN_BODIES = ("R-50-FPN", "R-101-FPN", "R-152-FPN")
 
 
 def stage_specs(conv_body):
     """the StageSpecs of MODEL.BACKBONE.CONV_BODY; NotImplementedError for every body this build does not run"""
     specs = STAGE_SPECS.get(conv_body)
     if specs is None:
-        raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r}: this build runs the C4 bodies {} only (no C5, FPN or FBNet body)"
-                                  .format(conv_body, ", ".join(sorted(STAGE_SPECS))))
+        raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r}: this build runs the C4 bodies {} and the FPN bodies {} only (no C5, RetinaNet or "
+                                  "FBNet body)".format(conv_body, ", ".join(sorted(set(STAGE_SPECS) - set(FPN_BODIES))), ", ".join(sorted(FPN_BODIES))))
     return specs
+
+def check_fpn_config(cfg):
+    """An FPN body hands five maps to whatever follows it: only a multi-level RPN (MODEL.RPN.USE_FPN, one ANCHOR_STRIDE per map) can take them.
+    With the single-level RPN the reference pairs one anchor grid with five head outputs and fails at its first call, so that configuration
+    is refused when the body is built, as every FPN body was before the neck existed."""
+    body = cfg.MODEL.BACKBONE.CONV_BODY
+    if body in FPN_BODIES and not cfg.MODEL.RPN.USE_FPN:
+        raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r} with MODEL.RPN.USE_FPN False: an FPN body feeds a multi-level RPN (USE_FPN, one "
+                                  "ANCHOR_STRIDE per level); with the single-level RPN this build runs the C4 bodies {} only"
+                                  .format(body, ", ".join(sorted(set(STAGE_SPECS) - set(FPN_BODIES)))))
+
 
 # Weight versions: data derived from a weight tensor (the flipped dgrad copies; inside the library, under abr_conv_desc::w_version, the
 # Winograd-domain weights and the fragment-packed bf16x3 planes the bf16x6 weights-direct kernel reads) is rebuilt lazily when its version is stale.  _PARAM_VERSION moves with EVERY change (optimiser steps, loads, in-place
@@ -660,6 +677,7 @@ class ResNet(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         specs = stage_specs(cfg.MODEL.BACKBONE.CONV_BODY)
+        check_fpn_config(cfg)
         assert cfg.MODEL.RESNETS.STRIDE_IN_1X1 and cfg.MODEL.RESNETS.NUM_GROUPS == 1
         self.stem = StemWithFixedBatchNorm(cfg)
         width = cfg.MODEL.RESNETS.NUM_GROUPS * cfg.MODEL.RESNETS.WIDTH_PER_GROUP
@@ -667,6 +685,9 @@ class ResNet(nn.Module):
         out2 = cfg.MODEL.RESNETS.RES2_OUT_CHANNELS
         self.stages, self.return_features = [], {}
         with_dcn = tuple(cfg.MODEL.RESNETS.STAGE_WITH_DCN)
+        if any(spec.index == 4 for spec in specs) and with_dcn[3]:
+            raise NotImplementedError("MODEL.RESNETS.STAGE_WITH_DCN[3] with CONV_BODY {!r}: a deformable layer4 over the full map is not implemented "
+                                      "(the deformable conv2 runs in layer1..layer3)".format(cfg.MODEL.BACKBONE.CONV_BODY))
         for spec in specs:
             name = "layer" + str(spec.index)
             f = 2 ** (spec.index - 1)

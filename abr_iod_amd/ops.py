@@ -181,6 +181,91 @@ def roi_align_pyramid_backward(grad, rois, scales, ph, pw, sampling_ratio, shape
     return out
 
 
+# ----------------------------------------------------------------------------------------------- the FPN neck (csrc/fpn.hip)
+def _fpn_levels_check(what, maps, name):
+    """`maps`: the levels' contiguous fp32 [B,H_l,W_l,C] device tensors (None where the caller allows it) -> (B, C), C a multiple of 4"""
+    B, Ch = _pyramid_check(what, [m for m in maps if m is not None], name)
+    if Ch % 4:
+        raise ValueError(f"{what}: C = {Ch} is not a multiple of 4")
+    return B, Ch
+
+
+def _fpn_shapes_check(what, shapes):
+    """every level exactly twice the next coarser one, else ValueError before any launch (the reference's `lateral + upsampled` raises there too)"""
+    for l in range(len(shapes) - 1):
+        (_, h, w, _), (_, h1, w1, _) = shapes[l], shapes[l + 1]
+        if h != 2 * h1 or w != 2 * w1:
+            raise ValueError(f"{what}: level {l} is {h} x {w}, not twice level {l + 1}'s {h1} x {w1}")
+
+
+def fpn_topdown_forward(laterals):
+    """laterals: list of contiguous [B,H_l,W_l,C], finest first -> the list of inners, inner_l = lateral_l + nearest-upsampled inner_{l+1}, in ONE
+    launch; the top inner IS the top lateral (the same tensor).  Bit-equal to the level-by-level lateral + F.interpolate(.., scale_factor=2)."""
+    lats = list(laterals)
+    B, Ch = _fpn_levels_check("fpn_topdown_forward", lats, "laterals")
+    shapes = [tuple(t.shape) for t in lats]
+    _fpn_shapes_check("fpn_topdown_forward", shapes)
+    n = len(lats)
+    inners = [torch.empty_like(t) for t in lats[:-1]] + [lats[-1]]
+    if n > 1:
+        L.check(L.lib().abr_fpn_topdown_forward((C.c_void_p * n)(*[t.data_ptr() for t in lats]), (C.c_void_p * n)(*[t.data_ptr() for t in inners]),
+                                                (C.c_int * n)(*[s[1] for s in shapes]), (C.c_int * n)(*[s[2] for s in shapes]), n, B, Ch, L.stream()),
+                "fpn_topdown_forward")
+    return inners
+
+
+def fpn_topdown_backward(grads, inplace=False):
+    """grads: the gradients arriving at inner_0 .. inner_{L-1} (contiguous [B,H_l,W_l,C]; None past level 0 = none arrives) -> the list of
+    lateral gradients T_l, T_0 = g_0, T_l = g_l + ((T_{l-1}(2y,2x) + T_{l-1}(2y,2x+1)) + (T_{l-1}(2y+1,2x) + T_{l-1}(2y+1,2x+1))), in ONE launch
+    and this fixed order.  T_0 is g_0 itself; inplace: every T_l is written over g_l (a level without g_l still gets a new tensor)."""
+    gs = list(grads)
+    if not gs or gs[0] is None:
+        raise ValueError("fpn_topdown_backward: the finest level's gradient is missing (start the list at the finest level that has one)")
+    B, Ch = _fpn_levels_check("fpn_topdown_backward", gs, "grads")
+    g0 = gs[0]
+    shapes = [tuple(g0.shape)]
+    for l in range(1, len(gs)):
+        shapes.append(tuple(gs[l].shape) if gs[l] is not None else (B, shapes[-1][1] // 2, shapes[-1][2] // 2, Ch))
+    _fpn_shapes_check("fpn_topdown_backward", shapes)
+    n = len(gs)
+    outs = [g0] + [g if (inplace and g is not None) else _empty(s, g0) for g, s in zip(gs[1:], shapes[1:])]
+    if n > 1:
+        L.check(L.lib().abr_fpn_topdown_backward((C.c_void_p * n)(*[L.ptr(g) for g in gs]), (C.c_void_p * n)(*[t.data_ptr() for t in outs]),
+                                                 (C.c_int * n)(*[s[1] for s in shapes]), (C.c_int * n)(*[s[2] for s in shapes]), n, B, Ch, L.stream()),
+                "fpn_topdown_backward")
+        for t in outs[1:]:
+            amax_drop(t)
+    return outs
+
+
+def fpn_subsample2(x):
+    """LastLevelMaxPool, F.max_pool2d(x, 1, 2, 0): x [B,H,W,C] -> [B,(H-1)//2+1,(W-1)//2+1,C], out(y,x) = x(2y,2x)"""
+    L.require_cuda(x)
+    x = L.f32c(x)
+    B, H, W, Ch = x.shape
+    out = _empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Ch), x)
+    L.check(L.lib().abr_fpn_subsample2_forward(L.ptr(x), B, H, W, Ch, L.ptr(out), L.stream()), "fpn_subsample2_forward")
+    return out
+
+
+def fpn_subsample2_backward(g_out, shape, g_in=None, inplace=False):
+    """g_out [B,Ho,Wo,C], shape = x's [B,H,W,C] -> g_x = g_in (None: zero) + g_out scattered to the even pixels, every element written once;
+    inplace: g_x is written over g_in"""
+    L.require_cuda(g_out, g_in)
+    g_out = L.f32c(g_out)
+    B, H, W, Ch = (int(v) for v in shape)
+    if tuple(g_out.shape) != (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Ch):
+        raise ValueError(f"fpn_subsample2_backward: g_out {tuple(g_out.shape)} is not the subsampled shape of {(B, H, W, Ch)}")
+    if g_in is not None:
+        if tuple(g_in.shape) != (B, H, W, Ch):
+            raise ValueError(f"fpn_subsample2_backward: g_in {tuple(g_in.shape)} is not {(B, H, W, Ch)}")
+        g_in = L.f32c(g_in)
+    g_x = g_in if (inplace and g_in is not None) else _empty((B, H, W, Ch), g_out)
+    L.check(L.lib().abr_fpn_subsample2_backward(L.ptr(g_out), L.ptr(g_in), B, H, W, Ch, L.ptr(g_x), L.stream()), "fpn_subsample2_backward")
+    amax_drop(g_x)
+    return g_x
+
+
 # ----------------------------------------------------------------------------------------------- ROIPool, deformable PS-RoI pooling
 def roi_pool_forward(feat, rois, spatial_scale, ph, pw, out=None):
     """feat [B,H,W,C], rois [K,5] -> (out [K,ph,pw,C], argmax int32 [K,ph,pw,C]: flat pixel h*W+w of the bin's first maximum, -1 for none);

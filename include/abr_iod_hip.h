@@ -171,6 +171,31 @@ int abr_roi_align_pyramid_backward(const float* grad, const float* rois, int K, 
                                    float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
                                    int accumulate, float* const* grad_feats_host, void* stream);
 
+/* The top-down pathway of a feature pyramid network (modeling/backbone/fpn.py:47-70) and LastLevelMaxPool (:90-92), csrc/fpn.hip.
+ * All maps are NHWC fp32, contiguous, 16-byte aligned, C % 4 == 0; level 0 is the finest, H[l] == 2 H[l+1] and W[l] == 2 W[l+1];
+ * 1 <= L <= ABR_MAX_PYRAMID_LEVELS; B * H[0] * W[0] * C / 4 must fit int32.  The *_host arguments are HOST arrays of L entries copied into the
+ * kernel's arguments.  Every refusal (negative status, abr_last_error names the argument) comes before any launch.  No atomics: every output
+ * element has one owner and its additions a fixed order, so results reproduce bit for bit.
+ *
+ * Forward, one launch: inner_host[l], l < L-1, receives inner_l(y,x) = lat_l(y,x) + inner_{l+1}(y>>1, x>>1) with inner_{L-1} = lat_{L-1};
+ * each element is evaluated from the top down (t = lat_{L-1}; t = lat_{L-2} + t; ... ; t = lat_l + t), only fp32 adds: bit-equal to the
+ * level-by-level lateral + F.interpolate(last_inner, scale_factor=2, mode="nearest").  inner_host[L-1] is never read or written (the top
+ * level IS its lateral); inner_host[l] may not alias a lateral.  L == 1 launches nothing. */
+int abr_fpn_topdown_forward(const float* const* lat_host, float* const* inner_host, const int* H_host, const int* W_host, int L, int B, int C,
+                            void* stream);
+/* Its adjoint, one launch: g_host[l] = the gradient arriving at inner_l (NULL for l >= 1: none, a zero that is not added; g_host[0] is required),
+ * d_lat_host[l] receives T_l, T_0 = g_0,
+ *   T_l(y,x) = g_l(y,x) + ((T_{l-1}(2y,2x) + T_{l-1}(2y,2x+1)) + (T_{l-1}(2y+1,2x) + T_{l-1}(2y+1,2x+1)))      (without g_l: the bracket alone)
+ * in exactly this order of fp32 additions.  One thread per (image, coarsest pixel, 4 channels) folds its descendants from the finest level
+ * up: every g is read once, every d_lat written once.  d_lat_host[l] == g_host[l] is allowed (T_l written over g_l; nothing is copied for
+ * level 0 then). */
+int abr_fpn_topdown_backward(const float* const* g_host, float* const* d_lat_host, const int* H_host, const int* W_host, int L, int B, int C,
+                             void* stream);
+/* LastLevelMaxPool = F.max_pool2d(x, 1, 2, 0): out [B,Ho,Wo,C] (y,x) = x [B,H,W,C] (2y,2x), Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1 */
+int abr_fpn_subsample2_forward(const float* x, int B, int H, int W, int C, float* out, void* stream);
+/* g_x [B,H,W,C] written whole: g_in (NULL: zero) + g_out [B,Ho,Wo,C] scattered to the even pixels; g_x == g_in is allowed */
+int abr_fpn_subsample2_backward(const float* g_out, const float* g_in, int B, int H, int W, int C, float* g_x, void* stream);
+
 /* _C.roi_pool_forward(input, rois, spatial_scale, pooled_h, pooled_w) -> (output, argmax)
  *   csrc/ROIPool.h:10-24 -> csrc/cuda/ROIPool_cuda.cu:16-77,110-150 (there is no CPU implementation).
  * feat [B,C,H,W] (NCHW) or [B,H,W,C] (NHWC); rois [K,5]; out and argmax [K,C,PH,PW] (NCHW) or [K,PH,PW,C] (NHWC).

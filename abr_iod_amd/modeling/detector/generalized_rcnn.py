@@ -50,8 +50,8 @@ class GeneralizedRCNN(nn.Module):
         super().__init__()
         from ..backbone.resnet import FPN_BODIES
         if cfg.MODEL.BACKBONE.CONV_BODY in FPN_BODIES:
-            raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r} in the whole detector: build_backbone, RPNModule.eval() and the multi-level Pooler "
-                                      "run over a pyramid, the multi-level RPN loss and the FPN RoI heads are not built; the detector runs the C4 "
+            raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r} in the whole detector: build_backbone, RPNModule (train and eval) and the "
+                                      "multi-level Pooler run over a pyramid, the FPN RoI heads are not built; the detector runs the C4 "
                                       "bodies R-101-C4, R-50-C4".format(cfg.MODEL.BACKBONE.CONV_BODY))
         self.backbone = build_backbone(cfg)
         self.incremental = cfg.INCREMENTAL

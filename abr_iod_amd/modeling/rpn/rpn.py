@@ -1,6 +1,7 @@
 """Region Proposal Network on the HIP library.
 
-Mirrors, for the single-level C4 case every configs/voc YAML uses (anchors and proposal selection also over a feature pyramid):
+Mirrors, for the single-level C4 case every configs/voc YAML uses and over a feature pyramid (anchors, proposal selection, and the loss over the
+levels' concatenated anchors, so RPNModule trains on an FPN body):
     AnchorGenerator          maskrcnn_benchmark/modeling/rpn/anchor_generator.py:34-123, 215-284
     RPNHead                  modeling/rpn/rpn.py:70-121  (conv3x3+ReLU, cls_logits 1x1, bbox_pred 1x1)
     RPNPostProcessor         modeling/rpn/inference.py:14-147
@@ -14,6 +15,9 @@ MI355X-first differences (results identical):
   * proposals for all images are decoded / clipped / NMS-ed in batched launches; the greedy NMS sweep stays on device.
   * anchors are cached per (H, W, image size) instead of being rebuilt with numpy every step.
   * IoU + Matcher + labels + BoxCoder.encode for 35 910 anchors is one kernel per image.
+  * over L > 1 levels the loss never concatenates predictions: the levels' anchors are ONE cached tensor (AnchorGenerator.pyramid), matching and
+    sampling run over it as over a single level, and abr_rpn_pyramid_loss reads each sampled anchor out of its level's fused output by address
+    (one launch); the backward is one memset of the levels' gradients (one allocation) plus one scatter of the sampled entries.
 """
 import math
 
@@ -123,6 +127,26 @@ class AnchorGenerator(nn.Module):
             hit = self._cache[key] = (a, vis, vis.bool())   # uint8 for the kernels, bool for the reference-typed BoxList field: made once
         return hit
 
+    def pyramid(self, grids, image_hw):
+        """The anchors of all levels as ONE tensor, in the reference's cat_boxlist order (level-major, then location row-major, then the anchor of
+        the cell): ([n,4] anchors, [n] uint8 visibility for this image size, the L+1 level offsets).  Built once per (grids, image size, device)
+        from the levels' grid() results; the box tensor is shared by every image size (only the visibility differs)."""
+        grids = tuple((int(h), int(w)) for h, w in grids)
+        assert len(grids) == len(self.strides), "one grid per anchor stride"
+        dev = self.cell_anchors.device
+        key = ("pyramid", grids, int(image_hw[0]), int(image_hw[1]), dev)
+        hit = self._cache.get(key)
+        if hit is None:
+            per = [self.grid(H, W, image_hw, l) for l, (H, W) in enumerate(grids)]
+            boxes = self._cache.get(("pyramid", grids, dev))
+            if boxes is None:
+                boxes = self._cache[("pyramid", grids, dev)] = torch.cat([p[0] for p in per])
+            offs = [0]
+            for p in per:
+                offs.append(offs[-1] + p[0].shape[0])
+            hit = self._cache[key] = (boxes, torch.cat([p[1] for p in per]), tuple(offs))
+        return hit
+
     def forward(self, image_list, feature_maps):
         assert len(feature_maps) == len(self.strides), "one feature map per anchor stride"
         grids = [f.shape[-2:] for f in feature_maps]
@@ -135,6 +159,8 @@ class AnchorGenerator(nn.Module):
                 bl.add_field("visibility", vis_bool)
                 bl._visibility_u8 = vis                   # the same mask as the kernels read it (no per-step dtype round trip)
                 per_level.append(bl)
+            if len(grids) > 1:
+                per_level[0]._pyramid = self.pyramid(grids, (ih, iw))   # the loss matches over the concatenation (no per-step torch.cat)
             anchors.append(per_level)
         return anchors
 
@@ -502,6 +528,45 @@ class _RPNLossFn(Function):
         return from_nhwc(g_obj.view(ctx.shape)), None, None, None, None, None, None, None
 
 
+class _RPNPyramidLossFn(Function):
+    """The same two losses over L levels (rpn/loss.py:104-148): ops.rpn_pyramid_loss reads every sampled anchor out of its level's fused NHWC
+    output; backward returns the L views of one gradient allocation (ops.rpn_pyramid_loss_backward)."""
+
+    @staticmethod
+    def forward(ctx, A, labels, reg_targets, pos, neg, counts, *fused):
+        ys = [as_nhwc(f) for f in fused]
+        want = any(f.requires_grad for f in fused)
+        losses, rec = ops.rpn_pyramid_loss(ys, A, labels, reg_targets, pos, neg, counts, want_grad=want)
+        ctx.meta = ([tuple(y.shape) for y in ys], A, pos.shape[1], neg.shape[1], ys[0].device)
+        ctx.rec = rec
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, g_lo, g_lb):
+        shapes, A, max_pos, batch, dev = ctx.meta
+        grads = ops.rpn_pyramid_loss_backward(shapes, A, ctx.rec, max_pos, batch, g_lo, g_lb, dev)
+        return (None,) * 6 + tuple(from_nhwc(g) if need else None for g, need in zip(grads, ctx.needs_input_grad[6:]))
+
+
+def _padded_from_flat(pos_idx, samp_idx, N, n):
+    """injected batch-flat index lists of any length (entries < 0 ignored) -> the sampler's padded form: pos [N,max_pos], neg [N,batch] (per image
+    ascending, -1 padded) and counts [N,2] int32; the negatives are the sampled entries that are no positives"""
+    pos_idx, samp_idx = pos_idx.reshape(-1), samp_idx.reshape(-1)
+    pos_idx, samp_idx = pos_idx[pos_idx >= 0], samp_idx[samp_idx >= 0]
+    neg_idx = samp_idx[~torch.isin(samp_idx, pos_idx)]
+
+    def pad(idx):
+        idx = idx.sort().values
+        img = torch.div(idx, n, rounding_mode="floor")
+        cnt = torch.bincount(img, minlength=N)
+        out = torch.full((N, max(int(cnt.max()) if idx.numel() else 0, 1)), -1, dtype=torch.int64, device=idx.device)
+        out[img, torch.arange(idx.numel(), device=idx.device) - (cnt.cumsum(0) - cnt)[img]] = idx
+        return out, cnt
+
+    (pos, n_pos), (neg, n_neg) = pad(pos_idx), pad(neg_idx)
+    return pos, neg, torch.stack([n_pos, n_neg], 1).to(torch.int32)
+
+
 class RPNLossComputation(object):
     def __init__(self, proposal_matcher, fg_bg_sampler, box_coder, generate_labels_func=None):
         self.proposal_matcher, self.fg_bg_sampler, self.box_coder = proposal_matcher, fg_bg_sampler, box_coder
@@ -533,10 +598,20 @@ class RPNLossComputation(object):
 
     def __call__(self, anchors, objectness, box_regression, targets, rpn_output_source=None, fused=None, sampled=None):
         """Returns (objectness_loss, box_loss).  `rpn_output_source` is accepted and ignored as in the reference (:129-143).
-        `sampled=(pos_idx, samp_idx)` injects the sampler's choice (parity tests)."""
-        anchors = [a[0] if isinstance(a, (list, tuple)) else a for a in anchors]
+        `sampled=(pos_idx, samp_idx)` injects the sampler's choice (parity tests).  A list of L > 1 fused outputs (`fused=[...]`), or the
+        reference's lists of L objectness and L regression tensors, goes through `call_pyramid`; one level stays on the route below."""
         if sampled is None:
             sampled = getattr(self, "inject_sampled", None)  # parity tests pin the sampler's draw here
+        if isinstance(fused, (list, tuple)) or (fused is None and len(objectness) > 1):
+            if fused is None:   # the reference's signature: re-fuse the two tensors of every level (compat path), pad columns zero
+                assert len(objectness) == len(box_regression), "one entry per feature level"
+                A = objectness[0].shape[1]
+                fused = [torch.cat((o, b) + ((o.new_zeros((o.shape[0], -5 * A % 4) + tuple(o.shape[2:])),) if 5 * A % 4 else ()), 1)
+                         for o, b in zip(objectness, box_regression)]
+            if len(fused) > 1:
+                return self.call_pyramid(anchors, list(fused), targets, sampled)
+            fused = fused[0]
+        anchors = [a[0] if isinstance(a, (list, tuple)) else a for a in anchors]
         if fused is None:
             fused = torch.cat((objectness[0], box_regression[0]), 1)
             A = objectness[0].shape[1]
@@ -569,6 +644,38 @@ class RPNLossComputation(object):
         return _RPNLossFn.apply(fused, A, lab_flat, tgt_flat, pos_idx, samp_idx, denom, prepared)
 
 
+    def call_pyramid(self, anchors, fused, targets, sampled=None):
+        """__call__ for L > 1 fused head outputs (logical [N,Cf,H_l,W_l]); anchors: per image the list of L BoxLists AnchorGenerator returns.
+        Matching (IoU, Matcher with low-quality matches, labels, encode) runs over the levels' CONCATENATED anchors, so a ground truth's
+        low-quality match is its best anchor over all levels (rpn/loss.py:104-118 after cat_boxlist); the sampler draws per image over the same
+        concatenation; the loss reads the sampled anchors by address."""
+        nL = len(fused)
+        assert all(len(a) == nL for a in anchors), "one anchor BoxList per feature level and image"
+        A = anchors[0][0].bbox.shape[0] // (fused[0].shape[-1] * fused[0].shape[-2])
+        boxes, vis = None, []
+        for a in anchors:
+            pyr = getattr(a[0], "_pyramid", None)
+            if pyr is None:       # anchors that did not come from AnchorGenerator.forward: concatenate here
+                v = [getattr(b, "_visibility_u8", None) for b in a]
+                v = [b.get_field("visibility").to(torch.uint8) if x is None else x for b, x in zip(a, v)]
+                pyr = (torch.cat([b.bbox for b in a]), torch.cat(v))
+            if boxes is None:
+                boxes = pyr[0]
+            assert pyr[0].shape == boxes.shape, "the images of one batch share the levels' grids: they differ only in the visibility field"
+            vis.append(pyr[1])
+        lab2d, tgt3d, _keep = ops.rpn_targets_batched(boxes, vis, [t.bbox for t in targets], self.proposal_matcher.high_threshold,
+                                                      self.proposal_matcher.low_threshold, self.box_coder.weights)
+        N, n = lab2d.shape
+        if sampled is not None:
+            pos, neg, counts = _padded_from_flat(sampled[0], sampled[1], N, n)
+        else:
+            pos, neg, counts = self.fg_bg_sampler.sample_padded(lab2d, index_offset_per_image=n)
+        pos_flat = pos.reshape(-1)
+        self.last_sampled = (pos_flat, torch.cat([pos_flat, neg.reshape(-1)]))   # (-1 padded, as the single-level route's)
+        self.last_targets = (list(lab2d.unbind(0)), list(tgt3d.unbind(0)))
+        return _RPNPyramidLossFn.apply(A, lab2d, tgt3d, pos, neg, counts, *fused)
+
+
 def make_rpn_loss_evaluator(cfg, box_coder):
     matcher = Matcher(cfg.MODEL.RPN.FG_IOU_THRESHOLD, cfg.MODEL.RPN.BG_IOU_THRESHOLD, allow_low_quality_matches=True)
     sampler = BalancedPositiveNegativeSampler(cfg.MODEL.RPN.BATCH_SIZE_PER_IMAGE, cfg.MODEL.RPN.POSITIVE_FRACTION)
@@ -576,6 +683,11 @@ def make_rpn_loss_evaluator(cfg, box_coder):
 
 
 # ------------------------------------------------------------------------------------------------ module
+class MissingTargets(ValueError, NotImplementedError):
+    """RPNModule.train() over a feature pyramid was called with targets=None: a bad value for the caller.  While the multi-level RPN loss was
+    missing, exactly this call raised NotImplementedError; callers that caught it keep working (coco_eval.MissingObjectness is the precedent)."""
+
+
 class RPNModule(nn.Module):
     def __init__(self, cfg, in_channels):
         super().__init__()
@@ -594,9 +706,9 @@ class RPNModule(nn.Module):
     def forward(self, images, features, targets=None, rpn_output_source=None, defer_proposals=False):
         """-> ((boxes, losses), anchors, rpn_output) exactly as rpn.py:161-183."""
         if self.training:
-            if len(features) > 1:
-                raise NotImplementedError("training the RPN on %d feature levels needs the multi-level RPN loss (rpn/loss.py over the "
-                                          "concatenated levels), which is not implemented; eval() selects proposals over a pyramid" % len(features))
+            if len(features) > 1 and targets is None:
+                raise MissingTargets("training the RPN on %d feature levels: the multi-level RPN loss (rpn/loss.py over the concatenated "
+                                     "levels) needs targets, got targets=None; eval() selects proposals over a pyramid" % len(features))
             return self.forward_finish(self.forward_begin(images, features, targets, rpn_output_source))
         A = self.head.num_anchors
         if len(features) > 1:   # a feature pyramid: the shared head per level, the multi-level selector (rpn.py:161-183, inference.py:120-176)
@@ -616,6 +728,8 @@ class RPNModule(nn.Module):
     def forward_begin(self, images, features, targets, rpn_output_source=None):
         """Training forward up to (not including) the read-back of the proposal counts: head conv, anchors, the proposal selection
         launched on a side stream, the loss on the current stream."""
+        if len(features) > 1:   # a feature pyramid: the shared head per level, selector and loss over the list (rpn.py:161-183)
+            return self.forward_begin_pyramid(images, features, targets, rpn_output_source)
         fused = self.head.forward_fused(features[0])
         A = self.head.num_anchors
         anchors = self.anchor_generator(images, features)
@@ -626,6 +740,24 @@ class RPNModule(nn.Module):
                 pending = self.box_selector_train.launch_on_side_stream(anchors, fused.detach(), A)
             else:
                 pending = self.box_selector_train.launch(anchors, fused.detach(), A)
+        loss_objectness, loss_rpn_box_reg = self.loss_evaluator(anchors, None, None, targets, rpn_output_source, fused=fused)
+        return dict(pending=pending, targets=targets, anchors=anchors, rpn_output=rpn_output,
+                    losses={"loss_objectness": loss_objectness, "loss_rpn_box_reg": loss_rpn_box_reg})
+
+    def forward_begin_pyramid(self, images, features, targets, rpn_output_source=None):
+        """forward_begin over L > 1 maps: the head's weight and bias gradients accumulate over the L backward nodes (conv_wgrad and bias_grad add
+        into the fused gradient buffers)."""
+        A = self.head.num_anchors
+        fused = [self.head.forward_fused(f) for f in features]
+        anchors = self.anchor_generator(images, features)
+        rpn_output = ([f[:, :A] for f in fused], [f[:, A:5 * A] for f in fused])
+        with torch.no_grad():
+            self.box_selector_train.train()
+            detached = [f.detach() for f in fused]
+            if PROPOSALS_SIDE_STREAM and fused[0].is_cuda:
+                pending = self.box_selector_train.launch_on_side_stream(anchors, detached, A)
+            else:
+                pending = self.box_selector_train.launch(anchors, detached, A)
         loss_objectness, loss_rpn_box_reg = self.loss_evaluator(anchors, None, None, targets, rpn_output_source, fused=fused)
         return dict(pending=pending, targets=targets, anchors=anchors, rpn_output=rpn_output,
                     losses={"loss_objectness": loss_objectness, "loss_rpn_box_reg": loss_rpn_box_reg})

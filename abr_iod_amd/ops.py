@@ -1770,6 +1770,73 @@ def rpn_loss_indices(pos, neg, counts, A, Cf):
     return samp, obj_flat, pos_row, pos_col, denom
 
 
+def _rpn_pyramid_loss_tables(what, ys, A):
+    """host arrays of the pyramid loss's entry points; ys: the levels' contiguous fp32 [N,H_l,W_l,Cf] (or [N,nloc_l,Cf]) fused head outputs"""
+    nL = len(ys)
+    if not 1 <= nL <= MAX_PYRAMID_LEVELS:
+        raise RuntimeError(f"{what}: {nL} levels, need 1 .. {MAX_PYRAMID_LEVELS}")
+    N, Cf = ys[0].shape[0], ys[0].shape[-1]
+    for l, y in enumerate(ys):
+        L.require_cuda(y)
+        if y.dtype != _f32 or y.dim() not in (3, 4) or not y.is_contiguous() or y.shape[0] != N or y.shape[-1] != Cf:
+            raise RuntimeError(f"{what}: level {l} must be a contiguous float32 [N,H,W,Cf] tensor with the batch and width of level 0, got "
+                               f"{tuple(y.shape)} {y.dtype}")
+    nloc = [y.numel() // (N * Cf) if N else 1 for y in ys]
+    return (C.c_void_p * nL)(*[y.data_ptr() for y in ys]), (C.c_int * nL)(*nloc), nloc, N, Cf
+
+
+def rpn_pyramid_loss(ys, A, labels, reg_targets, pos, neg, counts, want_grad=False):
+    """The RPN loss over L levels in one launch (abr_rpn_pyramid_loss).  ys: list of L fused head outputs NHWC [N,H_l,W_l,Cf]; labels [N,n] fp32 and
+    reg_targets [N,n,4] over the levels' concatenated anchors (n = A * sum H_l W_l); pos [N,max_pos] / neg [N,batch] / counts [N,2] as sample_pos_neg
+    returns them with index_offset_per_image = n.  -> (losses [2] = objectness, box regression; records or None).  The records (dst int64, val fp32)
+    are what rpn_pyramid_loss_backward scatters."""
+    ys = list(ys)
+    yp, nl, nloc, N, Cf = _rpn_pyramid_loss_tables("rpn_pyramid_loss", ys, A)
+    L.require_cuda(labels, reg_targets, pos, neg, counts)
+    n = int(A) * sum(nloc)
+    if labels.dtype != _f32 or not labels.is_contiguous() or labels.numel() != N * n:
+        raise RuntimeError(f"rpn_pyramid_loss: labels must be contiguous float32 [{N},{n}], got {tuple(labels.shape)} {labels.dtype}")
+    if reg_targets.dtype != _f32 or not reg_targets.is_contiguous() or reg_targets.numel() != N * n * 4:
+        raise RuntimeError(f"rpn_pyramid_loss: reg_targets must be contiguous float32 [{N},{n},4], got {tuple(reg_targets.shape)} {reg_targets.dtype}")
+    if pos.dtype != torch.int64 or neg.dtype != torch.int64 or counts.dtype != torch.int32 or pos.dim() != 2 or neg.dim() != 2 \
+            or pos.shape[0] != N or neg.shape[0] != N or tuple(counts.shape) != (N, 2) \
+            or not (pos.is_contiguous() and neg.is_contiguous() and counts.is_contiguous()):
+        raise RuntimeError("rpn_pyramid_loss: pos [N,max_pos] / neg [N,batch] int64 and counts [N,2] int32, contiguous, as sample_pos_neg returns them")
+    max_pos, batch, dev = pos.shape[1], neg.shape[1], ys[0].device
+    losses = torch.empty((2,), dtype=_f32, device=dev)
+    rec = None
+    if want_grad:
+        S, P = N * (max_pos + batch), N * max_pos
+        rec = (torch.empty((S + P,), dtype=torch.int64, device=dev), torch.empty((S + 4 * P,), dtype=_f32, device=dev))
+    L.check(L.lib().abr_rpn_pyramid_loss(yp, nl, len(ys), N, int(A), Cf, L.ptr(labels), L.ptr(reg_targets), L.ptr(pos), max_pos, L.ptr(neg), batch,
+                                         L.ptr(counts), L.ptr(losses), L.ptr(rec[0]) if rec else None, L.ptr(rec[1]) if rec else None, L.stream()),
+            "rpn_pyramid_loss")
+    return losses, rec
+
+
+def rpn_pyramid_loss_backward(shapes, A, rec, max_pos, batch, g_obj, g_box, device):
+    """shapes: the levels' NHWC shapes (N,H_l,W_l,Cf); rec: rpn_pyramid_loss's records; g_obj / g_box: the upstream gradients of the two losses
+    (device scalars).  -> list of L [N,H_l,W_l,Cf] views of ONE zero-filled allocation (levels back to back) holding the dense gradient."""
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    nL = len(shapes)
+    if not 1 <= nL <= MAX_PYRAMID_LEVELS:
+        raise RuntimeError(f"rpn_pyramid_loss_backward: {nL} levels, need 1 .. {MAX_PYRAMID_LEVELS}")
+    N, Cf = shapes[0][0], shapes[0][-1]
+    nloc = [s[1] * s[2] for s in shapes]
+    g_obj, g_box = L.f32c(g_obj), L.f32c(g_box)
+    L.require_cuda(rec[0], rec[1], g_obj, g_box)
+    S, P = N * (max_pos + batch), N * max_pos
+    assert rec[0].numel() == S + P and rec[1].numel() == S + 4 * P and rec[0].dtype == torch.int64 and rec[1].dtype == _f32
+    grad = torch.empty((N * sum(nloc) * Cf,), dtype=_f32, device=device)
+    L.check(L.lib().abr_rpn_pyramid_loss_backward((C.c_int * nL)(*nloc), nL, N, int(A), Cf, L.ptr(rec[0]), L.ptr(rec[1]), int(max_pos), int(batch),
+                                                  L.ptr(g_obj), L.ptr(g_box), L.ptr(grad), L.stream()), "rpn_pyramid_loss_backward")
+    out, o = [], 0
+    for s, nl in zip(shapes, nloc):
+        out.append(grad[o: o + N * nl * Cf].view(s))
+        o += N * nl * Cf
+    return out
+
+
 def gather_proposals(props, scores, keep, picks, P):
     """rois [N*P,5] = (i, props[i, keep[i, picks[i*P+j]]]), obj [N*P]: P picked rows per image of the post-NMS lists"""
     N, k_pre, _ = props.shape

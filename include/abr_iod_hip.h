@@ -645,6 +645,29 @@ int abr_rpn_pyramid_decode(const float* const* y_host, const int* nloc_host, con
  * count), n_out [N] int32.  Scores may be any non-NaN fp32. */
 int abr_rpn_pyramid_select(const float* props, const float* scores, const int32_t* keep, const int32_t* n_keep, int N, int L, int k_max, int post,
                            int fpn_post_n, int mode, float* rois, float* out_scores, int32_t* src, int32_t* n_out, void* stream);
+/* The RPN loss over a feature pyramid (rpn/loss.py:104-148 with rpn/utils.py:10-45; csrc/rpn_pyramid_loss.hip).  y_host[l] = device pointer of
+ * level l's fused head output [N, nloc[l], Cf] (columns 0 .. A-1 the logits of anchors loc * A + a, A + 4a .. +3 their deltas; A, Cf and N are
+ * shared by the levels: there is one head); y_host / nloc_host are HOST arrays of L entries copied into the kernel's arguments.  An image's anchors
+ * are the levels' concatenated, n = A * sum nloc[l]: flat index g -> image g / n, j = g % n, the level l with off_l <= j < off_{l+1}
+ * (off_l = A * sum_{m<l} nloc[m]), location (j - off_l) / A, anchor (j - off_l) % A.  labels [N,n] fp32, reg_targets [N,n,4]; pos [N,max_pos],
+ * neg [N,batch] int64 and counts [N,2] int32 exactly as abr_sample_pos_neg leaves them with index_offset_per_image = n (-1 pads; an index outside
+ * 0 .. N*n-1 is skipped like padding).  losses[0] = sum of BCE-with-logits over all listed anchors / D, losses[1] = sum of smooth_l1(beta = 1/9)
+ * over the listed positives' four deltas / D, D = max(sum counts, 1), divided on the device.  One launch of one workgroup with a fixed order of
+ * additions: the values do not depend on the stream or on what else runs.
+ * rec_dst / rec_val (both or neither; NULL: no gradient wanted) receive the gradient as compact records, slot s = position in (pos, then neg),
+ * S = N * (max_pos + batch), P = N * max_pos:  rec_dst[s] = float offset of the slot's logit in the gradient storage (-1: padding), rec_val[s] =
+ * (sigmoid(x) - y) / D;  rec_dst[S + p] = offset of positive p's first delta, rec_val[S + 4p .. +3] = the smooth-L1 derivatives / D.
+ * rec_dst: S + P int64, rec_val: S + 4P floats.
+ * 1 <= L <= ABR_MAX_PYRAMID_LEVELS, Cf >= 5A, Cf % 4 == 0, non-null tables, else ABR_E_INVALID before any launch. */
+int abr_rpn_pyramid_loss(const float* const* y_host, const int* nloc_host, int L, int N, int A, int Cf, const float* labels,
+                         const float* reg_targets, const int64_t* pos, int max_pos, const int64_t* neg, int batch, const int32_t* counts,
+                         float* losses, int64_t* rec_dst, float* rec_val, void* stream);
+/* The dense gradient of all levels from abr_rpn_pyramid_loss's records.  grad = ONE allocation of Cf * N * sum nloc[l] floats, level l the
+ * [N, nloc[l], Cf] block at float offset Cf * N * sum_{m<l} nloc[m] (16-byte aligned as Cf % 4 == 0).  One hipMemsetAsync over the allocation and
+ * one scatter launch: record value * upstream gradient of its loss (g_obj, g_box: device scalars, no sync).  The sampled anchors are distinct and
+ * the logit and delta columns disjoint: plain stores, everything else (pad columns included) is exactly 0.  Same argument checks. */
+int abr_rpn_pyramid_loss_backward(const int* nloc_host, int L, int N, int A, int Cf, const int64_t* rec_dst, const float* rec_val, int max_pos,
+                                  int batch, const float* g_obj, const float* g_box, float* grad, void* stream);
 /* BoxCoder.encode row-wise (box_coder.py:22-50): out[i] = encode(gt[i], ex[i]); img_hw==NULL above = decode without clip */
 int abr_box_encode(const float* gt, const float* ex, int n, float wx, float wy, float ww, float wh, float* out,
                    void* stream);

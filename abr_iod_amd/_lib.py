@@ -76,6 +76,9 @@ _SIGS = {
     "abr_scratch_bytes": (_i64, []),
     "abr_roi_head_targets": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _i, _i, C.c_uint64,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "abr_roi_head_targets_table": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _i, _i, C.c_uint64,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "abr_h3_amax_max": (_i, [_vp, _vp, _i, _vp, C.c_uint32, _vp]),
     "abr_rpn_targets_batched": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _i64, _vp]),
     "abr_rpn_loss_indices": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "abr_loss_sum": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),

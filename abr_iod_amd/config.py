@@ -158,6 +158,13 @@ _C.MODEL.ROI_HEADS.POSITIVE_FRACTION = 0.25
 _C.MODEL.ROI_HEADS.SCORE_THRESH = 0.05
 _C.MODEL.ROI_HEADS.NMS = 0.5
 _C.MODEL.ROI_HEADS.DETECTIONS_PER_IMG = 100
+# the FPN box head (defaults.py:212-220).  Honoured by FPN2MLPFeatureExtractor / FPNPredictor: FC_FREEZE (fc6 and fc7), CLS_FREEZE, BBS_FREEZE
+# (the predictor's two layers); the offset layers CLS_OFFSET / BBS_OFFSET raise (modeling/roi_heads/box_head/fpn_box_head.py)
+_C.MODEL.ROI_HEADS.FC_FREEZE = False
+_C.MODEL.ROI_HEADS.CLS_FREEZE = False
+_C.MODEL.ROI_HEADS.BBS_FREEZE = False
+_C.MODEL.ROI_HEADS.CLS_OFFSET = False
+_C.MODEL.ROI_HEADS.BBS_OFFSET = False
 
 _C.MODEL.ROI_BOX_HEAD = CN()
 _C.MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR = "ResNet50Conv5ROIFeatureExtractor"
@@ -166,6 +173,8 @@ _C.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION = 14
 _C.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO = 0
 _C.MODEL.ROI_BOX_HEAD.POOLER_SCALES = (1.0 / 16,)
 _C.MODEL.ROI_BOX_HEAD.NUM_CLASSES = 81
+_C.MODEL.ROI_BOX_HEAD.MLP_HEAD_DIM = 1024     # hidden width of FPN2MLPFeatureExtractor's fc6 / fc7 (defaults.py:249)
+_C.MODEL.ROI_BOX_HEAD.USE_GN = False          # GroupNorm heads are not built: True raises (defaults.py:251)
 _C.MODEL.ROI_BOX_HEAD.NAME_OLD_CLASSES = []
 _C.MODEL.ROI_BOX_HEAD.NAME_NEW_CLASSES = []
 _C.MODEL.ROI_BOX_HEAD.NAME_EXCLUDED_CLASSES = []

@@ -48,12 +48,11 @@ def _drop_derived_cache(base, nbytes):
 class GeneralizedRCNN(nn.Module):
     def __init__(self, cfg):
         super().__init__()
-        from ..backbone.resnet import FPN_BODIES
-        if cfg.MODEL.BACKBONE.CONV_BODY in FPN_BODIES:
-            raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r} in the whole detector: build_backbone, RPNModule (train and eval) and the "
-                                      "multi-level Pooler run over a pyramid, the FPN RoI heads are not built; the detector runs the C4 "
-                                      "bodies R-101-C4, R-50-C4".format(cfg.MODEL.BACKBONE.CONV_BODY))
         self.backbone = build_backbone(cfg)
+        if not cfg.MODEL.RPN_ONLY:
+            # body and box head must match (C4 body + C5 head, FPN body + MLP head): said here, before the RPN is built around the body's maps
+            from ..roi_heads.box_head.box_head import check_box_head_cfg
+            check_box_head_cfg(cfg)
         self.incremental = cfg.INCREMENTAL
         self.n_old_cl = len(cfg.MODEL.ROI_BOX_HEAD.NAME_OLD_CLASSES)
         self.n_new_cl = len(cfg.MODEL.ROI_BOX_HEAD.NAME_NEW_CLASSES)
@@ -224,7 +223,7 @@ class GeneralizedRCNN(nn.Module):
         pending = state["pending"]
         if isinstance(pending, dict):   # deferred: join the side stream, read the keep counts
             sel = self.rpn.box_selector_test
-            if pending["props"].is_cuda:   # the distillation proposals gathered from the selector's raw output by one kernel
+            if pending["rois" if "n_out" in pending else "props"].is_cuda:   # the distillation proposals gathered from the selector's raw output
                 return self._soften_fused(sel, pending, state, selected_indices)
             pending = sel.collect(pending)
         return self._soften_from_proposals(pending, state["features"], state["backbone_features"], state["anchors"],
@@ -247,12 +246,14 @@ class GeneralizedRCNN(nn.Module):
         own stream (it finished long ago: the target's backbone ran in between), the picks go up in one pinned asynchronous copy and ONE
         gather kernel builds the RoI table -- instead of cutting per-image BoxLists, sorting them (the post-NMS list already is in
         descending objectness order) and indexing them field by field.  Falls back to the BoxList path for ragged pick counts."""
+        pyramid = "n_out" in pending      # the pyramid selector's pending state: a dense table, already in descending objectness order (eval)
+        counts = pending["n_out" if pyramid else "n_keep"]
         side = pending.get("stream")
         if side is not None:
             with torch.cuda.stream(side):
-                nk = pending["n_keep"].tolist()
+                nk = counts.tolist()
         else:
-            nk = pending["n_keep"].tolist()
+            nk = counts.tolist()
         picks = [self._pick_soften(n, k, selected_indices) for k, n in enumerate(nk)]
         P = len(picks[0]) if picks else 0
         if not picks or any(len(p) != P for p in picks) or P == 0:
@@ -260,8 +261,16 @@ class GeneralizedRCNN(nn.Module):
                                                state["rpn_output"], picks)
         sel.join(pending)
         self.last_soften_indices = picks
-        dev = pending["props"].device
-        rois, obj = ops.gather_proposals(pending["props"], pending["scores"], pending["keep"], ops.h2d([i for p in picks for i in p], torch.int64, dev), P)
+        if pyramid:      # no keep indirection: row pick of image k IS rois[k, pick]
+            dev = pending["rois"].device
+            idx = ops.h2d([i for p in picks for i in p], torch.int64, dev).view(len(picks), P)
+            img = torch.arange(len(picks), device=dev).view(-1, 1)
+            boxes = pending["rois"][img, idx].reshape(-1, 4)
+            rois = torch.cat((img.expand(-1, P).reshape(-1, 1).to(boxes.dtype), boxes), 1)
+            obj = pending["objectness"][img, idx].reshape(-1)
+        else:
+            dev = pending["props"].device
+            rois, obj = ops.gather_proposals(pending["props"], pending["scores"], pending["keep"], ops.h2d([i for p in picks for i in p], torch.int64, dev), P)
         ready = torch.cuda.Event()
         ready.record()          # the RoI table exists from here on: the trainer starts the target's distillation pass behind this event,
         all_selected = []       # not behind the source model's whole head pass

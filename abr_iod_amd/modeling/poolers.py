@@ -46,6 +46,9 @@ class _PyramidROIAlign(Function):
     def forward(ctx, rois, output_size, scales, sampling_ratio, rule, *feats):
         xs = [as_nhwc(f) for f in feats]
         out = ops.roi_align_pyramid_forward(xs, rois, scales, output_size[0], output_size[1], sampling_ratio, *rule)
+        # a pooled value is an average of bilinear samples of ONE level's map (or 0): the largest of the levels' amax words bounds the result
+        # (f16x3 scales; ops.amax_carry_bound for L maps).  A level without a tag leaves the result untagged: its consumer reduces it.
+        ops.amax_bound_levels(out, xs)
         ctx.save_for_backward(rois)
         ctx.geom = (tuple(output_size), tuple(scales), sampling_ratio, rule, [tuple(x.shape) for x in xs])
         return from_nhwc(out)

@@ -348,11 +348,16 @@ class FastRCNNLossComputation(object):
         the RoI table for the whole batch in three launches without a host round trip (ops.roi_head_targets).  Every image gets
         BATCH_SIZE_PER_IMAGE rows; rows past the number actually drawn (only when an image has fewer candidates than that) are
         padding with label -1, which the loss kernels skip.  Returns the dict of device tensors; `self._proposals` are BoxList VIEWS of it."""
-        props, scores, keep, n_keep, sizes = lazy.raw()
         R = self.fg_bg_sampler.batch_size_per_image
-        t = ops.roi_head_targets(props, scores, keep, n_keep, [g.bbox for g in targets], [g.get_field("labels") for g in targets],
-                                 self.proposal_matcher.high_threshold, self.proposal_matcher.low_threshold, self.box_coder.weights, R,
-                                 int(R * self.fg_bg_sampler.positive_fraction), num_classes, self.cls_agnostic_bbox_reg)
+        rest = ([g.bbox for g in targets], [g.get_field("labels") for g in targets], self.proposal_matcher.high_threshold,
+                self.proposal_matcher.low_threshold, self.box_coder.weights, R, int(R * self.fg_bg_sampler.positive_fraction), num_classes,
+                self.cls_agnostic_bbox_reg)
+        if getattr(lazy, "is_table", False):   # the pyramid selector's dense table (rpn.LazyPyramidProposals): no keep lists
+            rois, scores, n_out, sizes = lazy.raw()
+            t = ops.roi_head_targets_table(rois, scores, n_out, *rest)
+        else:
+            props, scores, keep, n_keep, sizes = lazy.raw()
+            t = ops.roi_head_targets(props, scores, keep, n_keep, *rest)
         out = []
         for i, size in enumerate(sizes):
             lo, hi = i * R, (i + 1) * R
@@ -427,11 +432,47 @@ def make_roi_box_loss_evaluator(cfg):
 from .inference import make_roi_box_post_processor  # noqa: E402
 
 
+_BOX_HEAD_PAIRS = {"ResNet50Conv5ROIFeatureExtractor": "FastRCNNPredictor", "FPN2MLPFeatureExtractor": "FPNPredictor"}
+
+
+def check_box_head_cfg(cfg):
+    """MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR / PREDICTOR (roi_box_feature_extractors.py:153-157, roi_box_predictors.py:135-137).  Built: the C4
+    pair ResNet50Conv5ROIFeatureExtractor + FastRCNNPredictor on a C4 body and the FPN pair FPN2MLPFeatureExtractor + FPNPredictor on an FPN
+    body; everything else raises, naming the key and its value.  -> whether the FPN pair is selected."""
+    from ...backbone.resnet import FPN_BODIES
+    head, body = cfg.MODEL.ROI_BOX_HEAD, cfg.MODEL.BACKBONE.CONV_BODY
+    if head.FEATURE_EXTRACTOR not in _BOX_HEAD_PAIRS:
+        raise NotImplementedError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR {!r}: this build runs {} (no FPNXconv1fcFeatureExtractor: the conv + "
+                                  "GroupNorm head is not built)".format(head.FEATURE_EXTRACTOR, ", ".join(sorted(_BOX_HEAD_PAIRS))))
+    if head.PREDICTOR not in _BOX_HEAD_PAIRS.values():
+        raise NotImplementedError("MODEL.ROI_BOX_HEAD.PREDICTOR {!r}: this build runs {}".format(head.PREDICTOR, ", ".join(sorted(_BOX_HEAD_PAIRS.values()))))
+    fpn_head, on_fpn = head.FEATURE_EXTRACTOR == "FPN2MLPFeatureExtractor", body in FPN_BODIES
+    if on_fpn != fpn_head:
+        raise NotImplementedError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR {!r} on MODEL.BACKBONE.CONV_BODY {!r}: {}".format(
+            head.FEATURE_EXTRACTOR, body,
+            "an FPN body feeds the pyramid head FPN2MLPFeatureExtractor + FPNPredictor (layer4 is part of the body, there is no C5 head to run)"
+            if on_fpn else "the multi-level pooler and MLP head need an FPN body's pyramid; a C4 body runs ResNet50Conv5ROIFeatureExtractor"))
+    if head.PREDICTOR != _BOX_HEAD_PAIRS[head.FEATURE_EXTRACTOR]:
+        raise NotImplementedError("MODEL.ROI_BOX_HEAD.PREDICTOR {!r} with MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR {!r} (MODEL.BACKBONE.CONV_BODY {!r}): "
+                                  "that extractor is built with {} only".format(head.PREDICTOR, head.FEATURE_EXTRACTOR, body,
+                                                                                _BOX_HEAD_PAIRS[head.FEATURE_EXTRACTOR]))
+    return fpn_head
+
+
+def make_box_head_parts(cfg, in_channels):
+    """(feature extractor, predictor) of a configuration check_box_head_cfg admits"""
+    if check_box_head_cfg(cfg):
+        from .fpn_box_head import FPN2MLPFeatureExtractor, FPNPredictor
+        fe = FPN2MLPFeatureExtractor(cfg, in_channels)
+        return fe, FPNPredictor(cfg, fe.out_channels)
+    fe = ResNet50Conv5ROIFeatureExtractor(cfg, in_channels)
+    return fe, FastRCNNPredictor(cfg, fe.out_channels)
+
+
 class ROIBoxHead(nn.Module):
     def __init__(self, cfg, in_channels):
         super().__init__()
-        self.feature_extractor = ResNet50Conv5ROIFeatureExtractor(cfg, in_channels)
-        self.predictor = FastRCNNPredictor(cfg, self.feature_extractor.out_channels)
+        self.feature_extractor, self.predictor = make_box_head_parts(cfg, in_channels)
         self.loss_evaluator = make_roi_box_loss_evaluator(cfg)
         self.post_processor = make_roi_box_post_processor(cfg)
         self.need_roi_features_in_training = False
@@ -472,7 +513,8 @@ class ROIBoxHead(nn.Module):
         ev = self.loss_evaluator
         # the distillation RoIs' pooling needs the features and the SOURCE's proposals only: issued before the main stream starts waiting for the
         # target's own proposal selection (inside subsample_fused), it runs in that wait instead of behind it
-        soft_early = self.feature_extractor.pool_soft_early(features, soften_proposals) if features[0].is_cuda else None
+        early = getattr(self.feature_extractor, "pool_soft_early", None)   # (the C4 extractor's; the FPN extractor pools both sets in one launch)
+        soft_early = early(features, soften_proposals) if early is not None and features[0].is_cuda else None
         with torch.no_grad():
             if hasattr(proposals, "raw") and getattr(ev, "inject_sampled_inds", None) is None:
                 rois = ev.subsample_fused(proposals, targets, K)["rois"]    # (as `forward`: everything between NMS and ROIAlign stays on the device)

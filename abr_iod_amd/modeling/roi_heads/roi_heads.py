@@ -75,6 +75,13 @@ class CombinedROIHeads(torch.nn.ModuleDict):
 def build_roi_heads(cfg, in_channels):
     if cfg.MODEL.RETINANET_ON:
         raise NotImplementedError("only the box, mask and keypoint heads are on the hot path (SURVEY.md §2 row 6b)")
+    from ..backbone.resnet import FPN_BODIES
+    if cfg.MODEL.BACKBONE.CONV_BODY in FPN_BODIES:
+        for key in ("MASK_ON", "KEYPOINT_ON"):      # the FPN mask and keypoint heads (their own poolers and conv stacks) are not built
+            if cfg.MODEL[key]:
+                raise NotImplementedError("MODEL.{} True on MODEL.BACKBONE.CONV_BODY {!r}: only the box head (FPN2MLPFeatureExtractor + "
+                                          "FPNPredictor) runs on an FPN body; the mask and keypoint heads are the C4 ones"
+                                          .format(key, cfg.MODEL.BACKBONE.CONV_BODY))
     if cfg.MODEL.MASK_ON:
         check_mask_head_cfg(cfg)
     if cfg.MODEL.KEYPOINT_ON:

@@ -92,6 +92,18 @@ class LazyProposals(object):
         return self.materialize()[i]
 
 
+class LazyPyramidProposals(LazyProposals):
+    """LazyProposals for the pyramid selector's pending state (RPNPostProcessor.launch_pyramid): the proposals already are a dense table --
+    rois [N,cap,4], objectness [N,cap], n_out [N] -- so the box head's training path feeds it to ops.roi_head_targets_table; any other use
+    materialises through `collect`, as the single-level object does."""
+    is_table = True
+
+    def raw(self):
+        """(rois [N,cap,4], objectness [N,cap], n_out [N] int32, image sizes) visible to the current stream"""
+        p = self.selector.join(self.pending)
+        return p["rois"], p["objectness"], p["n_out"], p["sizes"]
+
+
 class AnchorGenerator(nn.Module):
     def __init__(self, sizes=(128, 256, 512), aspect_ratios=(0.5, 1.0, 2.0), anchor_strides=(8, 16, 32), straddle_thresh=0):
         super().__init__()
@@ -765,8 +777,11 @@ class RPNModule(nn.Module):
     def forward_finish(self, state):
         with torch.no_grad():
             # training: hand the box head the selector's RAW device output (LazyProposals) instead of per-image BoxLists cut on the host
-            if "props" in state["pending"] and state["pending"]["props"].is_cuda and state["targets"] is not None:
-                boxes = LazyProposals(self.box_selector_train, state["pending"], state["targets"])
+            pending = state["pending"]
+            if "props" in pending and pending["props"].is_cuda and state["targets"] is not None:
+                boxes = LazyProposals(self.box_selector_train, pending, state["targets"])
+            elif "n_out" in pending and pending["rois"].is_cuda and state["targets"] is not None:    # the pyramid selector's table
+                boxes = LazyPyramidProposals(self.box_selector_train, pending, state["targets"])
             else:
                 boxes = self.box_selector_train.collect(state["pending"], state["targets"])
         return (boxes, state["losses"]), state["anchors"], state["rpn_output"]

@@ -134,7 +134,7 @@ def roi_align_pyramid_forward(feats, rois, scales, ph, pw, sampling_ratio, k_min
                               out=None, want_levels=False):
     """feats: list of contiguous [B,H_l,W_l,C], rois [K,5] -> [K,ph,pw,C] in ONE launch (written into `out` when given): every row pooled on
     the level fpn_levels gives it, all zero for a row without one.  want_levels: -> (out, int32 [K] levels).  The result carries no amax
-    tag: its rows come from maps with different amax words."""
+    tag: its rows come from maps with different amax words (modeling.poolers.Pooler tags it with their maximum: amax_bound_levels)."""
     feats = list(feats)
     B, Ch = _pyramid_check("roi_align_pyramid_forward", feats)
     L.require_cuda(rois)
@@ -597,6 +597,27 @@ def amax_compute(t):
     amax_reductions[0] += 1
     amax_reductions[1] += t.numel() * 4
     return amax_tag(t, w, e, st)
+
+
+def amax_bound_levels(dst, srcs):
+    """dst holds, in fresh memory, values each bounded by one of the tensors `srcs` (the multi-level Pooler's output: a row is an average of
+    bilinear samples of ONE level's map): tag it with a fresh word holding the largest of their amax words (abr_h3_amax_max, one tiny launch
+    on the current stream) -- amax_carry_bound for more than one source.  If any source has no valid tag, dst stays untagged."""
+    if not H3_TAGS or not 1 <= len(srcs) <= MAX_PYRAMID_LEVELS:
+        return dst
+    refs = [amax_of(s) for s in srcs]
+    if any(w is None for w, _ in refs):
+        return dst
+    streams = {s._abr_amax[5] for s in srcs} - {None}
+    st = L.stream()
+    if streams - {st}:       # (a word reduced on another stream is not ordered before this launch)
+        return dst
+    n = len(refs)
+    words = (C.c_void_p * n)(*[w for w, _ in refs])
+    epochs = (C.c_uint32 * n)(*[e for _, e in refs])
+    w, e = amax_new()
+    L.check(L.lib().abr_h3_amax_max(C.cast(words, C.c_void_p), C.cast(epochs, C.c_void_p), n, w, e, st), "h3_amax_max")
+    return amax_tag(dst, w, e, st if streams else None)
 
 
 # ---- the conv amax-word protocol: every conv call path (conv_forward, conv_wgrad[_async], conv_backward, resnet._FwdPlan) decides its words here.
@@ -1697,21 +1718,15 @@ def _pointer_table(tensors, dev):
     return tab
 
 
-def roi_head_targets(props, scores, keep, n_keep, gt_boxes, gt_labels, hi, lo, weights, batch_size, max_pos, num_classes, cls_agnostic=False,
-                     seed=None):
-    """Box-head training targets for the whole batch, on device, no host round trip (include/abr_iod_hip.h, abr_roi_head_targets).
-    props [N,k,4] / scores [N,k] / keep [N,post] int32 / n_keep [N] int32: the RPN selector's raw output; gt_boxes / gt_labels: per-image
-    tensors.  Returns a dict of fixed-size tensors (batch_size rows per image)."""
-    N, k_pre, _ = props.shape
-    post = keep.shape[1]
-    dev = props.device
+def _roi_head_targets_setup(N, n_prop, gt_boxes, gt_labels, batch_size, max_pos, dev):
+    """the GT tables and the output dict shared by roi_head_targets and roi_head_targets_table (n_prop proposal rows per image at most)"""
     gtb = [L.f32c(b) for b in gt_boxes]
     gtl = [l.to(torch.int64).contiguous() for l in gt_labels]
     n_gt = [int(b.shape[0]) for b in gtb]
     if min(n_gt) == 0:   # matcher.py:53-57
         raise ValueError("No ground-truth boxes available for one of the images during training")
     g_max = max(n_gt)
-    Pmax = post + g_max
+    Pmax = n_prop + g_max
     R = batch_size
     i64, i32 = torch.int64, torch.int32
     out = dict(
@@ -1724,16 +1739,55 @@ def roi_head_targets(props, scores, keep, n_keep, gt_boxes, gt_labels, hi, lo, w
         n_valid=torch.empty((1,), dtype=_f32, device=dev), obj=torch.empty((N * R,), dtype=_f32, device=dev),
         pos_rows=torch.empty((N * R,), dtype=i64, device=dev), col0=torch.empty((N * R,), dtype=i64, device=dev),
         n_gt=n_gt, g_max=g_max, keepalive=(gtb, gtl))
+    ngt_dev = _small_table(n_gt, i32, dev)
+    gtb_tab, gtl_tab = _pointer_table(gtb, dev), _pointer_table(gtl, dev)   # (held by the caller until the launch is enqueued: _evict_oldest)
+    return out, (gtb_tab, gtl_tab, ngt_dev)
+
+
+def roi_head_targets(props, scores, keep, n_keep, gt_boxes, gt_labels, hi, lo, weights, batch_size, max_pos, num_classes, cls_agnostic=False,
+                     seed=None):
+    """Box-head training targets for the whole batch, on device, no host round trip (include/abr_iod_hip.h, abr_roi_head_targets).
+    props [N,k,4] / scores [N,k] / keep [N,post] int32 / n_keep [N] int32: the RPN selector's raw output; gt_boxes / gt_labels: per-image
+    tensors.  Returns a dict of fixed-size tensors (batch_size rows per image)."""
+    N, k_pre, _ = props.shape
+    post = keep.shape[1]
+    R = batch_size
+    out, (gtb_tab, gtl_tab, ngt_dev) = _roi_head_targets_setup(N, post, gt_boxes, gt_labels, R, max_pos, props.device)
     if seed is None:
         seed = _draw_seed()
-    ngt_dev = _small_table(n_gt, i32, dev)
-    gtb_tab, gtl_tab = _pointer_table(gtb, dev), _pointer_table(gtl, dev)   # (held in locals until the launch is enqueued: _evict_oldest)
     L.check(L.lib().abr_roi_head_targets(
         L.ptr(props), L.ptr(keep), L.ptr(n_keep), N, k_pre, post, L.ptr(gtb_tab), L.ptr(gtl_tab), L.ptr(ngt_dev),
-        g_max, float(hi), float(lo), *[float(v) for v in weights], R, max_pos, seed, L.ptr(out["cand"]), L.ptr(out["labels_all"]),
+        out["g_max"], float(hi), float(lo), *[float(v) for v in weights], R, max_pos, seed, L.ptr(out["cand"]), L.ptr(out["labels_all"]),
         L.ptr(out["regt_all"]), L.ptr(out["n_cand"]), L.ptr(out["pos_idx"]), L.ptr(out["neg_idx"]), L.ptr(out["counts"]), L.ptr(out["rois"]),
         L.ptr(out["labels"]), L.ptr(out["reg_targets"]), L.ptr(out["sampled_idx"]), L.ptr(out["n_valid"]), L.ptr(scores), L.ptr(out["obj_all"]),
         L.ptr(out["obj"]), L.ptr(out["pos_rows"]), L.ptr(out["col0"]), int(num_classes), int(bool(cls_agnostic)), L.stream()), "roi_head_targets")
+    return out
+
+
+def roi_head_targets_table(rois, scores, n_out, gt_boxes, gt_labels, hi, lo, weights, batch_size, max_pos, num_classes, cls_agnostic=False,
+                           seed=None):
+    """roi_head_targets for the pyramid selector's output (rpn_pyramid_select): rois [N,cap,4] / scores [N,cap] / n_out [N] int32, image i's
+    proposals being rows [0, n_out[i]) -- no keep lists (include/abr_iod_hip.h, abr_roi_head_targets_table).  Same dict, same three launches,
+    no host round trip; the same bits as roi_head_targets given the same candidates and seed."""
+    L.require_cuda(rois, scores, n_out)
+    if rois.dim() != 3 or rois.shape[2] != 4 or tuple(scores.shape) != tuple(rois.shape[:2]) or n_out.numel() != rois.shape[0]:
+        raise ValueError("roi_head_targets_table: rois [N,cap,4], scores [N,cap], n_out [N]; got {}, {}, {}".format(
+            tuple(rois.shape), tuple(scores.shape), tuple(n_out.shape)))
+    if n_out.dtype != torch.int32:
+        raise ValueError("roi_head_targets_table: n_out must be int32, got {}".format(n_out.dtype))
+    rois, scores, n_out = L.f32c(rois), L.f32c(scores), n_out.contiguous()
+    N, cap, _ = rois.shape
+    R = batch_size
+    out, (gtb_tab, gtl_tab, ngt_dev) = _roi_head_targets_setup(N, cap, gt_boxes, gt_labels, R, max_pos, rois.device)
+    if seed is None:
+        seed = _draw_seed()
+    L.check(L.lib().abr_roi_head_targets_table(
+        L.ptr(rois), L.ptr(scores), L.ptr(n_out), N, cap, L.ptr(gtb_tab), L.ptr(gtl_tab), L.ptr(ngt_dev),
+        out["g_max"], float(hi), float(lo), *[float(v) for v in weights], R, max_pos, seed, L.ptr(out["cand"]), L.ptr(out["labels_all"]),
+        L.ptr(out["regt_all"]), L.ptr(out["n_cand"]), L.ptr(out["pos_idx"]), L.ptr(out["neg_idx"]), L.ptr(out["counts"]), L.ptr(out["rois"]),
+        L.ptr(out["labels"]), L.ptr(out["reg_targets"]), L.ptr(out["sampled_idx"]), L.ptr(out["n_valid"]), L.ptr(out["obj_all"]),
+        L.ptr(out["obj"]), L.ptr(out["pos_rows"]), L.ptr(out["col0"]), int(num_classes), int(bool(cls_agnostic)), L.stream()),
+        "roi_head_targets_table")
     return out
 
 

@@ -422,6 +422,13 @@ int abr_h3_range_stats(uint64_t* out_host, int reset, void* stream);
 int abr_h3_range_stats_to_device(uint64_t* out_device, int reset, void* stream);
 /* *word = (epoch << 32) | bits(max |x[i]|) for n floats on `stream` (what a producer kernel's epilogue writes for free) */
 int abr_h3_amax(const float* x, int64_t n, uint64_t* word, uint32_t epoch, void* stream);
+/* *out_word = (out_epoch << 32) | max over l < L of the amax bits in words_host[l] (each read under epochs_host[l]), one one-wave launch on
+ * `stream` (csrc/box_head_fpn.hip): an upper bound of max |x| for a tensor whose every value is bounded by one of L tagged tensors -- the
+ * multi-level Pooler's output, each row an average of bilinear samples of one of the L maps.  words_host / epochs_host are HOST arrays of L
+ * entries copied into the kernel's arguments; 1 <= L <= ABR_MAX_PYRAMID_LEVELS; out_word a fresh word (abr_h3_amax_alloc*), none of the L.
+ * The L words must have been written on `stream` or ahead of it.  If one of them no longer carries its epoch the output word is NOT written:
+ * its reader then raises ABR_H3_FLAG_STALE, as a reader of that level's own word would.  Written with the protocol's 64-bit atomic max. */
+int abr_h3_amax_max(const uint64_t* const* words_host, const uint32_t* epochs_host, int L, uint64_t* out_word, uint32_t out_epoch, void* stream);
 
 int abr_conv_forward(const abr_conv_desc* d_host, const float* x, const float* w, float* out, void* stream);
 /* The tail of a 64-wide bottleneck WITHOUT a backward pass (maskrcnn_benchmark/modeling/backbone/resnet.py:327-346 for the frozen layer1:
@@ -710,6 +717,17 @@ int abr_roi_head_targets(const float* props, const int32_t* keep, const int32_t*
                          int64_t* labels_all, float* regt_all, int32_t* n_cand, int64_t* pos_idx, int64_t* neg_idx, int32_t* counts,
                          float* rois, int64_t* labels, float* reg_targets, int64_t* sampled_idx, float* n_valid, const float* scores,
                          float* obj_all, float* obj, int64_t* pos_rows, int64_t* col0, int num_classes, int cls_agnostic, void* stream);
+/* abr_roi_head_targets for the pyramid proposal selector's output (abr_rpn_pyramid_select), csrc/box_head_fpn.hip: the proposals of image i
+ * are rows [0, min(n_out[i], cap)) of the dense table rois_in [N,cap,4] with scores [N,cap] -- no keep indirection.  Everything else is
+ * abr_roi_head_targets' contract with k_pre = post = cap (Pmax = cap + g_max candidates per image), in the same three launches and by the
+ * same device code (csrc/roi_targets.h): given the same candidates and seed the two calls write the same bits.  An image with fewer than
+ * batch_size candidates (the normal case under FPN_POST_NMS_PER_BATCH) ends in padding rows: label -1, zero box, sampled_idx -1. */
+int abr_roi_head_targets_table(const float* rois_in, const float* scores, const int32_t* n_out, int N, int cap,
+                               const float* const* gt_ptrs, const int64_t* const* gt_label_ptrs, const int32_t* n_gt, int g_max, float hi,
+                               float lo, float wx, float wy, float ww, float wh, int batch_size, int max_pos, uint64_t seed, float* cand,
+                               int64_t* labels_all, float* regt_all, int32_t* n_cand, int64_t* pos_idx, int64_t* neg_idx, int32_t* counts,
+                               float* rois, int64_t* labels, float* reg_targets, int64_t* sampled_idx, float* n_valid, float* obj_all,
+                               float* obj, int64_t* pos_rows, int64_t* col0, int num_classes, int cls_agnostic, void* stream);
 /* RPN training targets of a whole batch (rpn/loss.py:66-102 per image: boxlist_iou, Matcher with low-quality matches, labels with the
  * visibility / between-thresholds discards, BoxCoder.encode) in two launches: anchors [n,4] shared by the images, gt_ptrs / vis_ptrs [N]
  * device arrays of device pointers ([G_i,4] fp32 / [n] uint8), n_gt [N]; labels [N,n] fp32 (1 / 0 / -1), reg_targets [N,n,4];

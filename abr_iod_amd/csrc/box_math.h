@@ -1,0 +1,89 @@
+// Box coder, matcher and label arithmetic: the one definition behind every kernel that encodes, decodes, clips, matches or labels boxes
+// (rpn.hip, roi_targets.h, rpn_pyramid.hip, detect.hip), beside abr::box_iou (common.h).  Those kernels' results must agree with the reference's
+// and with each other bit for bit, so each function here rounds once per operation: the library is built with the compiler's default
+// contraction, and every body switches it off for itself (a fused dx * w + cx would change results).  Operation order is the reference's,
+// divisions included.
+#pragma once
+#include "common.h"
+
+namespace abr {
+
+constexpr float kBoxDeltaClip = 4.135166556742356f;   // log(1000/16), box_coder.py:20 bbox_xform_clip
+
+// BoxCoder.encode (box_coder.py:22-50): the regression target of ground truth `gt` against the example box `ex`
+__device__ __forceinline__ float4 box_encode(const float4 gt, const float4 ex, float wx, float wy, float ww, float wh) {
+#pragma clang fp contract(off)
+    const float ew = ex.z - ex.x + 1, eh = ex.w - ex.y + 1;
+    const float ecx = ex.x + 0.5f * ew, ecy = ex.y + 0.5f * eh;
+    const float gw = gt.z - gt.x + 1, gh = gt.w - gt.y + 1;
+    const float gcx = gt.x + 0.5f * gw, gcy = gt.y + 0.5f * gh;
+    return make_float4(wx * (gcx - ecx) / ew, wy * (gcy - ecy) / eh, ww * logf(gw / ew), wh * logf(gh / eh));
+}
+
+// BoxCoder.decode (box_coder.py:52-95): the four deltas d applied to the anchor / RoI b
+__device__ __forceinline__ float4 box_decode(const float4 b, const float* d, float wx, float wy, float ww, float wh) {
+#pragma clang fp contract(off)
+    const float w = b.z - b.x + 1, h = b.w - b.y + 1;               // :66-69
+    const float cx = b.x + 0.5f * w, cy = b.y + 0.5f * h;
+    const float dx = d[0] / wx, dy = d[1] / wy;
+    const float dw = fminf(d[2] / ww, kBoxDeltaClip), dh = fminf(d[3] / wh, kBoxDeltaClip);
+    const float pcx = dx * w + cx, pcy = dy * h + cy;
+    const float pw = expf(dw) * w, ph = expf(dh) * h;
+    return make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw - 1, pcy + 0.5f * ph - 1);
+}
+
+// BoxList.clip_to_image (bounding_box.py:214-225), TO_REMOVE = 1: W1 = width - 1, H1 = height - 1
+__device__ __forceinline__ float4 box_clip(const float4 o, float W1, float H1) {
+#pragma clang fp contract(off)
+    return make_float4(fminf(fmaxf(o.x, 0.f), W1), fminf(fmaxf(o.y, 0.f), H1), fminf(fmaxf(o.z, 0.f), W1), fminf(fmaxf(o.w, 0.f), H1));
+}
+
+// Matcher's scan of one box against G ground truths (matcher.py:64-66 max over dim 0: the FIRST maximum wins, as torch.max does).  `rowmax`
+// (per ground truth the bit pattern of its largest IoU with any box, or nullptr) switches on set_low_quality_matches_'s test (:83-112): lq =
+// the box reaches some ground truth's maximum.  The test is decided outside the loop (LQ), so the loop of a kernel that always or never
+// wants it holds no branch on the pointer.
+struct MatchScan { float best; int bi; bool lq; };
+template <bool LQ>
+__device__ __forceinline__ MatchScan match_scan_lq(const float* gt, int G, const float4 b, const unsigned* rowmax) {
+#pragma clang fp contract(off)
+    MatchScan s{-1.f, 0, false};
+    for (int g = 0; g < G; g++) {
+        const float v = box_iou(reinterpret_cast<const float4*>(gt)[g], b);
+        if (v > s.best) { s.best = v; s.bi = g; }
+        if (LQ && v == __uint_as_float(rowmax[g])) s.lq = true;
+    }
+    return s;
+}
+__device__ __forceinline__ MatchScan match_scan(const float* gt, int G, const float4 b, const unsigned* rowmax) {
+    return rowmax ? match_scan_lq<true>(gt, G, b, rowmax) : match_scan_lq<false>(gt, G, b, nullptr);
+}
+
+// Matcher's result for a scanned box (matcher.py:68-75, low-quality matches restored :108-112): the ground truth's index, -1 BELOW_LOW_THRESHOLD,
+// -2 BETWEEN_THRESHOLDS.  The ground truth a caller then reads is row max(m, 0) (clamp(min=0) of rpn/loss.py:59, box_head/loss.py:52).
+__device__ __forceinline__ int match_index(float best, int bi, bool lq, float hi, float lo) {
+#pragma clang fp contract(off)
+    int m = best < lo ? -1 : (best < hi ? -2 : bi);
+    if (lq) m = bi;
+    return m;
+}
+
+// RPN objectness label of a matched anchor (rpn/loss.py:78-92): 1 matched, 0 background, -1 ignored (between thresholds, or not visible)
+__device__ __forceinline__ float rpn_label(int m, bool visible) {
+#pragma clang fp contract(off)
+    float l = m >= 0 ? 1.f : 0.f;
+    if (!visible) l = -1.f;
+    if (m == -2) l = -1.f;
+    return l;
+}
+
+// Box-head class label of a matched proposal (box_head/loss.py:66-75): the class of ground truth gi = max(m, 0) (1 without a label table),
+// 0 background, -1 ignored
+__device__ __forceinline__ int64_t head_label(int m, const int64_t* gt_labels, int gi) {
+#pragma clang fp contract(off)
+    int64_t l = gt_labels ? gt_labels[gi] : 1;
+    if (m == -1) l = 0;
+    if (m == -2) l = -1;
+    return l;
+}
+
+}  // namespace abr

@@ -16,8 +16,17 @@ namespace abr {
 // diverged activation into a clean zero and hide it from the loss and from the range guard; the reference's run shows NaN (modeling/backbone/resnet.py:339-346).
 __device__ __forceinline__ float relu_f(const float v) { return v < 0.f ? 0.f : v; }
 
+// Smooth-L1 element (layers/smooth_l1_loss.py:6-17): the loss of the difference d, its derivative in *g.  The one definition behind losses.hip's
+// kernels and the pyramid RPN loss (rpn_pyramid_loss.hip, beta = 1/9).
+__device__ __forceinline__ float sl1(float d, float beta, float* g) {
+    const float a = fabsf(d);
+    if (a < beta) { *g = d / beta; return 0.5f * a * a / beta; }
+    *g = d > 0.f ? 1.f : -1.f;
+    return a - 0.5f * beta;
+}
+
 // IoU of two boxes (x1, y1, x2, y2) as structures/boxlist_ops.py:53-88 computes it, TO_REMOVE = 1: the one definition behind the matchers of
-// rpn.hip and mask_match.h, which must agree bit for bit (nms.hip's `suppresses` is a different formulation).  One rounding per operation.
+// box_math.h (abr::match_scan) and mask_match.h, which must agree bit for bit (nms.hip's `suppresses` is a different formulation).  One rounding per operation.
 __device__ __forceinline__ float box_iou(const float4 g, const float4 b) {
 #pragma clang fp contract(off)
     const float area1 = (g.z - g.x + 1) * (g.w - g.y + 1);

@@ -12,7 +12,8 @@
 //   abr_nms_sorted_batched      the training path's NMS (nms.hip) over the N*C sorted lists at once
 //   det_final_kernel            one workgroup per image: radix-select the detections_per_img-th largest kept score, then an
 //                               ORDER-PRESERVING compaction (class-major, proposal order inside a class) of everything >= it.
-#include "common.h"
+#include "box_math.h"
+#include "rank_select.h"
 
 extern "C" int64_t abr_nms_workspace_bytes(int N, int n_max);
 extern "C" int abr_nms_sorted_batched(const float* boxes, const int32_t* counts, int N, int n_max, float thr, int strict_gt,
@@ -28,7 +29,6 @@ __global__ void det_softmax_decode_kernel(const float* __restrict__ logits, int 
                                           int ld_deltas, int delta_col0, int agnostic_col, const float* __restrict__ rois, int K,
                                           int C, const int32_t* __restrict__ img_hw, float wx, float wy, float ww, float wh,
                                           float* __restrict__ prob, float* __restrict__ boxes) {
-    const float clip = 4.135166556742356f;  // log(1000/16), box_coder.py:20
     const int total = K * C;
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
         const int r = t / C, j = t % C;
@@ -43,19 +43,8 @@ __global__ void det_softmax_decode_kernel(const float* __restrict__ logits, int 
         const float* d = deltas + (size_t)r * ld_deltas + delta_col0 + (agnostic_col >= 0 ? agnostic_col : 4 * j);
         const float* roi = rois + (size_t)r * 5;
         const int img = (int)roi[0];
-        const float w = roi[3] - roi[1] + 1, h = roi[4] - roi[2] + 1;
-        const float cx = roi[1] + 0.5f * w, cy = roi[2] + 0.5f * h;
-        const float dx = d[0] / wx, dy = d[1] / wy;
-        const float dw = fminf(d[2] / ww, clip), dh = fminf(d[3] / wh, clip);
-        const float pcx = dx * w + cx, pcy = dy * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        const float W1 = (float)(img_hw[2 * img + 1] - 1), H1 = (float)(img_hw[2 * img] - 1);
-        float4 o;
-        o.x = fminf(fmaxf(pcx - 0.5f * pw, 0.f), W1);
-        o.y = fminf(fmaxf(pcy - 0.5f * ph, 0.f), H1);
-        o.z = fminf(fmaxf(pcx + 0.5f * pw - 1, 0.f), W1);
-        o.w = fminf(fmaxf(pcy + 0.5f * ph - 1, 0.f), H1);
-        reinterpret_cast<float4*>(boxes)[t] = o;
+        const float4 o = abr::box_decode(make_float4(roi[1], roi[2], roi[3], roi[4]), d, wx, wy, ww, wh);
+        reinterpret_cast<float4*>(boxes)[t] = abr::box_clip(o, (float)(img_hw[2 * img + 1] - 1), (float)(img_hw[2 * img] - 1));
     }
 }
 
@@ -81,7 +70,7 @@ __global__ __launch_bounds__(TT) void det_sort_kernel(const float* __restrict__ 
         if (t < n) {
             const float p = prob[(size_t)(r0 + t) * C + j];
             if (p > thresh) {  // inference.py:116 `scores > self.score_thresh`; p > thresh >= 0 so the bit pattern is non-zero
-                key = ((unsigned long long)__float_as_uint(p) << 32) | (unsigned)(~(unsigned)t);
+                key = abr::rank_word(__float_as_uint(p), (unsigned)t);
                 mine++;
             }
         }
@@ -89,24 +78,13 @@ __global__ __launch_bounds__(TT) void det_sort_kernel(const float* __restrict__ 
     }
     if (mine) atomicAdd(&s_cnt, mine);
     __syncthreads();
-    for (int size = 2; size <= m; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < (m >> 1); t += TT) {
-                const int lo = 2 * t - (t & (stride - 1));
-                const int hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long a = buf[lo], b = buf[hi];
-                if ((a < b) == desc) { buf[lo] = b; buf[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    abr::bitonic_desc<TT>(buf, m);
     const int cnt = s_cnt;
     const size_t base = ((size_t)i * C + j) * r_max;
     for (int t = threadIdx.x; t < cnt; t += TT) {
         const unsigned long long v = buf[t];
-        const int r = (int)(~(unsigned)(v & 0xFFFFFFFFu));
-        s_scores[base + t] = __uint_as_float((unsigned)(v >> 32));
+        const int r = (int)abr::rank_word_index(v);
+        s_scores[base + t] = __uint_as_float(abr::rank_word_key(v));
         s_idx[base + t] = r;
         reinterpret_cast<float4*>(s_boxes)[base + t] = reinterpret_cast<const float4*>(boxes)[(size_t)(r0 + r) * C + j];
     }

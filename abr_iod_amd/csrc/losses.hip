@@ -60,14 +60,9 @@ __device__ __forceinline__ void loss_add(float v, float* loss_out, const abr::De
 }
 
 // ------------------------------------------------------------------------------------------------
-// smooth L1 -- layers/smooth_l1_loss.py:6-17
+// smooth L1 -- layers/smooth_l1_loss.py:6-17 (the element: abr::sl1, common.h)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sl1(float d, float beta, float* g) {
-    const float a = fabsf(d);
-    if (a < beta) { *g = d / beta; return 0.5f * a * a / beta; }
-    *g = d > 0.f ? 1.f : -1.f;
-    return a - 0.5f * beta;
-}
+using abr::sl1;
 
 __global__ __launch_bounds__(256) void smooth_l1_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t n,
                                                          float beta, float scale, float* __restrict__ loss_out,

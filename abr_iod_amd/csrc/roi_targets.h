@@ -3,10 +3,10 @@
 // are rows [0, n_out[i]) of the pyramid selector's table).  One copy of the matching, encoding and gathering; the two entry points differ only
 // in how a candidate row is fetched (the `Fetch` functor below).
 //   candidate list of image i = its proposals followed by its ground-truth boxes (rpn/inference.py:53-74 add_gt_proposals); every candidate
-//   is matched against the image's GT (Matcher 0.5 / 0.5, no low-quality rule), labelled and encoded (box_head/loss.py:56-84) -- the same
-//   arithmetic, in the same order, as match_encode_kernel (rpn.hip).
+//   is matched against the image's GT (Matcher 0.5 / 0.5, no low-quality rule), labelled and encoded (box_head/loss.py:56-84) -- through the
+//   functions match_encode_kernel (rpn.hip) calls: abr::match_scan, match_index, head_label, box_encode (box_math.h).
 #pragma once
-#include "common.h"
+#include "box_math.h"
 
 extern "C" int abr_sample_pos_neg(const void* labels, int labels_are_int64, int N, int n, int64_t stride, int batch_size, int max_pos,
                                   uint64_t seed, int first_image, int64_t index_offset_per_image, int64_t* pos_idx,
@@ -64,30 +64,12 @@ __global__ void cand_match_kernel(const Fetch f, const float* const* __restrict_
     const int64_t src = j < nk ? f.row(i, j) : 0;
     const float4 b = j < nk ? reinterpret_cast<const float4*>(f.props)[src] : reinterpret_cast<const float4*>(gt)[j - nk];
     obj_all[o] = j < nk ? f.scores[src] : 1.f;                                  // GT boxes join with objectness 1 (inference.py:66-68)
-    float best = -1.f;
-    int bi = 0;
-    for (int g = 0; g < G; g++) {
-        const float v = abr::box_iou(reinterpret_cast<const float4*>(gt)[g], b);
-        if (v > best) { best = v; bi = g; }                                    // first max wins (torch.max)
-    }
-    const int64_t m = best < lo ? -1 : (best < hi ? -2 : bi);                   // matcher.py:68-75
-    const int gi = m < 0 ? 0 : (int)m;                                          // clamp(min=0)
-    int64_t l = gt_labels[gi];                                                  // box_head/loss.py:66-75
-    if (m == -1) l = 0;
-    if (m == -2) l = -1;
-    labels_all[o] = l;
-    const float4 r = reinterpret_cast<const float4*>(gt)[gi];                   // box_coder.py:22-50
-    const float ew = b.z - b.x + 1, eh = b.w - b.y + 1;
-    const float ecx = b.x + 0.5f * ew, ecy = b.y + 0.5f * eh;
-    const float gw = r.z - r.x + 1, gh = r.w - r.y + 1;
-    const float gcx = r.x + 0.5f * gw, gcy = r.y + 0.5f * gh;
-    float4 t;
-    t.x = wx * (gcx - ecx) / ew;
-    t.y = wy * (gcy - ecy) / eh;
-    t.z = ww * logf(gw / ew);
-    t.w = wh * logf(gh / eh);
+    const abr::MatchScan s = abr::match_scan(gt, G, b, nullptr);                // no low-quality rule in the box head
+    const int m = abr::match_index(s.best, s.bi, false, hi, lo);
+    const int gi = m < 0 ? 0 : m;                                               // clamp(min=0)
+    labels_all[o] = abr::head_label(m, gt_labels, gi);
     reinterpret_cast<float4*>(cand)[o] = b;
-    reinterpret_cast<float4*>(regt_all)[o] = t;
+    reinterpret_cast<float4*>(regt_all)[o] = abr::box_encode(reinterpret_cast<const float4*>(gt)[gi], b, wx, wy, ww, wh);
 }
 
 __device__ __forceinline__ int lower_bound_i64(const int64_t* a, int n, int64_t v) {

@@ -1,7 +1,7 @@
 // RPN / RoI-head glue kernels: anchors, proposal decode+clip, IoU+Matcher+labels+BoxCoder.encode.
 // In the reference these are dozens of small ATen index kernels per image (and several nonzero() host syncs);
 // here each is one launch and nothing leaves the device.
-#include "common.h"
+#include "box_math.h"
 #include "roi_targets.h"
 
 namespace {
@@ -25,28 +25,14 @@ __global__ void decode_clip_kernel(const float* __restrict__ reg, int reg_stride
                                    const float* __restrict__ anchors, const int64_t* __restrict__ idx, int N, int n_anchor,
                                    int k, const int32_t* __restrict__ img_hw, float wx, float wy, float ww, float wh,
                                    float* __restrict__ out) {
-    const float clip = 4.135166556742356f;  // log(1000/16), box_coder.py:20
     const int total = N * k;
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
         const int i = t / k;
         const int64_t a = idx[t];
         // anchor a = location*A + a': its 4 deltas sit in row `location` of reg at columns reg_col0 + 4a' (NHWC head output)
         const float* d = reg + ((size_t)i * (n_anchor / A) + a / A) * reg_stride + reg_col0 + 4 * (a % A);
-        const float4 b = reinterpret_cast<const float4*>(anchors)[a];
-        const float w = b.z - b.x + 1, h = b.w - b.y + 1;               // box_coder.py:66-69
-        const float cx = b.x + 0.5f * w, cy = b.y + 0.5f * h;
-        const float dx = d[0] / wx, dy = d[1] / wy;
-        const float dw = fminf(d[2] / ww, clip), dh = fminf(d[3] / wh, clip);
-        const float pcx = dx * w + cx, pcy = dy * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        float4 o = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw - 1, pcy + 0.5f * ph - 1);
-        if (img_hw) {                                                   // bounding_box.py:214-225 clip_to_image
-            const float W1 = (float)(img_hw[2 * i + 1] - 1), H1 = (float)(img_hw[2 * i] - 1);
-            o.x = fminf(fmaxf(o.x, 0.f), W1);
-            o.y = fminf(fmaxf(o.y, 0.f), H1);
-            o.z = fminf(fmaxf(o.z, 0.f), W1);
-            o.w = fminf(fmaxf(o.w, 0.f), H1);
-        }
+        float4 o = abr::box_decode(reinterpret_cast<const float4*>(anchors)[a], d, wx, wy, ww, wh);
+        if (img_hw) o = abr::box_clip(o, (float)(img_hw[2 * i + 1] - 1), (float)(img_hw[2 * i] - 1));
         reinterpret_cast<float4*>(out)[t] = o;
     }
 }
@@ -62,64 +48,41 @@ __device__ __forceinline__ float block_max_256(float m, float* s_m) {
     return fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
 }
 
-__global__ __launch_bounds__(256) void gt_max_iou_kernel(const float* __restrict__ boxes, int n, const float* __restrict__ gt, int G,
-                                  unsigned* __restrict__ rowmax) {
+// the pass itself, for one image's G ground truths: all 256 threads of every workgroup along x call, each with its first box j0 and the
+// grid's stride along x (read off blockDim in the kernel, where the compiler knows the launch is uniform)
+__device__ __forceinline__ void gt_row_max(const float* boxes, int n, unsigned j0, unsigned stride, const float* gt, int G, unsigned* rowmax) {
     __shared__ float s_m[4];
     for (int g = 0; g < G; g++) {
         const float4 gb = reinterpret_cast<const float4*>(gt)[g];
         float m = 0.f;
-        for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
+        for (int j = j0; j < n; j += stride)
             m = fmaxf(m, abr::box_iou(gb, reinterpret_cast<const float4*>(boxes)[j]));
         m = block_max_256(m, s_m);
         if (threadIdx.x == 0) atomicMax(rowmax + g, __float_as_uint(m));  // IoU >= 0: bit pattern is monotone
     }
 }
 
+__global__ __launch_bounds__(256) void gt_max_iou_kernel(const float* __restrict__ boxes, int n, const float* __restrict__ gt, int G,
+                                  unsigned* __restrict__ rowmax) {
+    gt_row_max(boxes, n, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, gt, G, rowmax);
+}
+
 #pragma clang fp contract(off)
 __global__ void match_encode_kernel(const float* __restrict__ boxes, int n, const float* __restrict__ gt,
                                     const int64_t* __restrict__ gt_labels, int G, const uint8_t* __restrict__ vis, float hi,
-                                    float lo, int allow_lq, const unsigned* __restrict__ rowmax, float wx, float wy, float ww,
+                                    float lo, const unsigned* __restrict__ rowmax, float wx, float wy, float ww,
                                     float wh, int64_t* __restrict__ matched, float* __restrict__ labels_f32,
                                     int64_t* __restrict__ labels_i64, float* __restrict__ reg_targets) {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
         const float4 b = reinterpret_cast<const float4*>(boxes)[j];
-        float best = -1.f;
-        int bi = 0;
-        bool lq = false;
-        for (int g = 0; g < G; g++) {
-            const float v = abr::box_iou(reinterpret_cast<const float4*>(gt)[g], b);
-            if (v > best) { best = v; bi = g; }                                    // first max wins (torch.max)
-            if (allow_lq && v == __uint_as_float(rowmax[g])) lq = true;
-        }
-        int64_t m = best < lo ? -1 : (best < hi ? -2 : bi);                         // matcher.py:68-75
-        if (lq) m = bi;                                                             // :108-112
+        const abr::MatchScan s = abr::match_scan(gt, G, b, rowmax);                 // rowmax: only with allow_low_quality_matches
+        const int m = abr::match_index(s.best, s.bi, s.lq, hi, lo);
         if (matched) matched[j] = m;
-        const int gi = m < 0 ? 0 : (int)m;                                          // clamp(min=0)
-        if (labels_f32) {                                                           // rpn/loss.py:78-92
-            float l = m >= 0 ? 1.f : 0.f;
-            if (vis && !vis[j]) l = -1.f;
-            if (m == -2) l = -1.f;
-            labels_f32[j] = l;
-        }
-        if (labels_i64) {                                                           // box_head/loss.py:66-75
-            int64_t l = gt_labels ? gt_labels[gi] : 1;
-            if (m == -1) l = 0;
-            if (m == -2) l = -1;
-            labels_i64[j] = l;
-        }
-        if (reg_targets) {                                                          // box_coder.py:22-50
-            const float4 r = reinterpret_cast<const float4*>(gt)[gi];
-            const float ew = b.z - b.x + 1, eh = b.w - b.y + 1;
-            const float ecx = b.x + 0.5f * ew, ecy = b.y + 0.5f * eh;
-            const float gw = r.z - r.x + 1, gh = r.w - r.y + 1;
-            const float gcx = r.x + 0.5f * gw, gcy = r.y + 0.5f * gh;
-            float4 o;
-            o.x = wx * (gcx - ecx) / ew;
-            o.y = wy * (gcy - ecy) / eh;
-            o.z = ww * logf(gw / ew);
-            o.w = wh * logf(gh / eh);
-            reinterpret_cast<float4*>(reg_targets)[j] = o;
-        }
+        const int gi = m < 0 ? 0 : m;                                               // clamp(min=0)
+        if (labels_f32) labels_f32[j] = abr::rpn_label(m, !vis || vis[j]);
+        if (labels_i64) labels_i64[j] = abr::head_label(m, gt_labels, gi);
+        if (reg_targets)
+            reinterpret_cast<float4*>(reg_targets)[j] = abr::box_encode(reinterpret_cast<const float4*>(gt)[gi], b, wx, wy, ww, wh);
     }
 }
 
@@ -143,21 +106,12 @@ __global__ void gather_proposals_kernel(const float* __restrict__ props, const f
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // RPN training targets for the whole batch (abr_rpn_targets_batched): the anchors are shared by the images (same feature-map size), the
-// GT boxes and the visibility masks are per image.  Same arithmetic as gt_max_iou_kernel / match_encode_kernel, blockIdx.y = image.
+// GT boxes and the visibility masks are per image.  gt_max_iou_kernel's pass (gt_row_max) and match_encode_kernel's functions (abr::match_scan,
+// match_index, rpn_label, box_encode: box_math.h), blockIdx.y = image.
 __global__ __launch_bounds__(256) void gt_max_iou_batched_kernel(const float* __restrict__ boxes, int n, const float* const* __restrict__ gt_ptrs,
                                           const int32_t* __restrict__ n_gt, int g_max, unsigned* __restrict__ rowmax) {
-    __shared__ float s_m[4];
     const int i = blockIdx.y;
-    const float* gt = gt_ptrs[i];
-    const int G = n_gt[i];
-    for (int g = 0; g < G; g++) {
-        const float4 gb = reinterpret_cast<const float4*>(gt)[g];
-        float m = 0.f;
-        for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
-            m = fmaxf(m, abr::box_iou(gb, reinterpret_cast<const float4*>(boxes)[j]));
-        m = block_max_256(m, s_m);
-        if (threadIdx.x == 0) atomicMax(rowmax + (size_t)i * g_max + g, __float_as_uint(m));
-    }
+    gt_row_max(boxes, n, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, gt_ptrs[i], n_gt[i], rowmax + (size_t)i * g_max);
 }
 
 #pragma clang fp contract(off)
@@ -172,32 +126,11 @@ __global__ void rpn_match_batched_kernel(const float* __restrict__ boxes, int n,
     const unsigned* rm = rowmax + (size_t)i * g_max;
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
         const float4 b = reinterpret_cast<const float4*>(boxes)[j];
-        float best = -1.f;
-        int bi = 0;
-        bool lq = false;
-        for (int g = 0; g < G; g++) {
-            const float v = abr::box_iou(reinterpret_cast<const float4*>(gt)[g], b);
-            if (v > best) { best = v; bi = g; }
-            if (v == __uint_as_float(rm[g])) lq = true;                            // allow_low_quality_matches (matcher.py:83-112)
-        }
-        int64_t m = best < lo ? -1 : (best < hi ? -2 : bi);
-        if (lq) m = bi;
-        const int gi = m < 0 ? 0 : (int)m;
-        float l = m >= 0 ? 1.f : 0.f;                                               // rpn/loss.py:78-92
-        if (vis && !vis[j]) l = -1.f;
-        if (m == -2) l = -1.f;
-        labels[(size_t)i * n + j] = l;
-        const float4 r = reinterpret_cast<const float4*>(gt)[gi];
-        const float ew = b.z - b.x + 1, eh = b.w - b.y + 1;
-        const float ecx = b.x + 0.5f * ew, ecy = b.y + 0.5f * eh;
-        const float gw = r.z - r.x + 1, gh = r.w - r.y + 1;
-        const float gcx = r.x + 0.5f * gw, gcy = r.y + 0.5f * gh;
-        float4 o;
-        o.x = wx * (gcx - ecx) / ew;
-        o.y = wy * (gcy - ecy) / eh;
-        o.z = ww * logf(gw / ew);
-        o.w = wh * logf(gh / eh);
-        reinterpret_cast<float4*>(reg_targets)[(size_t)i * n + j] = o;
+        const abr::MatchScan s = abr::match_scan_lq<true>(gt, G, b, rm);           // always with allow_low_quality_matches
+        const int m = abr::match_index(s.best, s.bi, s.lq, hi, lo);
+        const int gi = m < 0 ? 0 : m;                                               // clamp(min=0)
+        labels[(size_t)i * n + j] = abr::rpn_label(m, !vis || vis[j]);
+        reinterpret_cast<float4*>(reg_targets)[(size_t)i * n + j] = abr::box_encode(reinterpret_cast<const float4*>(gt)[gi], b, wx, wy, ww, wh);
     }
 }
 
@@ -231,12 +164,7 @@ __global__ void rpn_loss_indices_kernel(const int64_t* __restrict__ pos, int n_p
 __global__ void box_encode_kernel(const float* __restrict__ gt, const float* __restrict__ ex, int n, float wx, float wy,
                                   float ww, float wh, float* __restrict__ out) {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
-        const float4 r = reinterpret_cast<const float4*>(gt)[j], b = reinterpret_cast<const float4*>(ex)[j];
-        const float ew = b.z - b.x + 1, eh = b.w - b.y + 1;
-        const float ecx = b.x + 0.5f * ew, ecy = b.y + 0.5f * eh;
-        const float gw = r.z - r.x + 1, gh = r.w - r.y + 1;
-        const float gcx = r.x + 0.5f * gw, gcy = r.y + 0.5f * gh;
-        reinterpret_cast<float4*>(out)[j] = make_float4(wx * (gcx - ecx) / ew, wy * (gcy - ecy) / eh, ww * logf(gw / ew), wh * logf(gh / eh));
+        reinterpret_cast<float4*>(out)[j] = abr::box_encode(reinterpret_cast<const float4*>(gt)[j], reinterpret_cast<const float4*>(ex)[j], wx, wy, ww, wh);
     }
 }
 
@@ -292,7 +220,7 @@ extern "C" int abr_match_encode(const float* boxes, int n, const float* gt, cons
         if (hipMemsetAsync(rowmax, 0, 4 * (size_t)G, st) != hipSuccess) return ABR_E_LAUNCH;
         gt_max_iou_kernel<<<std::min(abr::cdiv(n, 1024), 64u), 256, 0, st>>>(boxes, n, gt, G, rowmax);
     }
-    match_encode_kernel<<<abr::cdiv(n, 256), 256, 0, st>>>(boxes, n, gt, gt_labels, G, vis, hi, lo, allow_low_quality, rowmax,
+    match_encode_kernel<<<abr::cdiv(n, 256), 256, 0, st>>>(boxes, n, gt, gt_labels, G, vis, hi, lo, rowmax,
                                                            wx, wy, ww, wh, matched, labels_f32, labels_i64, reg_targets);
     ABR_CHECK_LAUNCH("match_encode");
     return ABR_OK;

@@ -6,8 +6,8 @@
 //
 //   abr_rpn_pyramid_topk    1 memset + 3 launches, whatever N and L are
 //     1. keys (grid: slices x S): the sigmoid key of every anchor of every level, once, into scratch + a histogram of the keys' top 12 bits per
-//        segment (LDS per workgroup, flushed with integer atomics).  The key is topk.hip's: the bit pattern of 1 / (1 + expf(-x)).
-//     2. partition (grid: slices x S): the bin b1 holding the k-th key is read off the histogram by every workgroup; words (key << 32 | ~index)
+//        segment (LDS per workgroup, flushed with integer atomics).  The key is abr_topk_sigmoid's: abr::sigmoid_key (rank_select.h).
+//     2. partition (grid: slices x S): the bin b1 holding the k-th key is read off the histogram by every workgroup; words (abr::rank_word: key << 32 | ~index)
 //        of keys above the bin are SURVIVORS (fewer than k of them), words inside it CANDIDATES; both are appended per segment (a counting pass,
 //        one reservation per workgroup with two global integer atomics, a writing pass: no staging in LDS, so no limit on the slice).
 //     3. select + sort + emit (one 1024-thread workgroup per segment): the words are unique, so the (k - #survivors)-th largest candidate WORD
@@ -19,8 +19,8 @@
 //     Scratch (per stream, from the pool): [histograms S x 4096][counters S][survivors S x 2048 words][candidates: a word per key][keys].
 //     Histograms and counters are zeroed by the call itself, everything else is written before it is read: no call depends on what an earlier
 //     one (a larger pyramid, another batch size) left behind.
-//   abr_rpn_pyramid_decode  1 launch (one workgroup per segment): BoxCoder.decode + clip_to_image with decode_clip_kernel's arithmetic
-//     (rpn.hip), remove_small_boxes, and a stable compaction (wave ballots + a prefix over the 16 waves) so that survivors keep rank order.
+//   abr_rpn_pyramid_decode  1 launch (one workgroup per segment): BoxCoder.decode + clip_to_image through the functions decode_clip_kernel
+//     (rpn.hip) calls (abr::box_decode, box_clip: box_math.h), remove_small_boxes, and a stable compaction (wave ballots + a prefix over the 16 waves) so that survivors keep rank order.
 //   abr_nms_sorted_batched  (nms.hip, unchanged) with the S segments as its "images"
 //   abr_rpn_pyramid_select  3 launches: candidate words (order-preserving score key << 32 | ~position), the exact k-th largest word by a
 //     six-level radix selection (one workgroup per image, or one for the batch in mode 1), emission (one workgroup per image: mode 0 sorts the
@@ -28,9 +28,12 @@
 //     no result depends on the order in which atomics were won.
 #include <algorithm>
 
-#include "common.h"
+#include "box_math.h"
+#include "rank_select.h"
 
 namespace {
+
+using abr::find_bin_from_top;
 
 constexpr int MAXL = ABR_MAX_PYRAMID_LEVELS;
 constexpr int KT = 256;       // threads of the chip-wide kernels
@@ -48,48 +51,6 @@ struct PyrLevels {            // by value in the kernel arguments: no device-sid
 };
 struct PyrCnt { int surv, cand; };
 struct SelThr { unsigned long long word; int want, total; };
-
-// wave 0: the bin holding the s_krem-th largest element of histogram h (nbins a multiple of 64), counted from the TOP bin -> s_bin, s_krem -= what
-// lies above it (topk.hip's)
-__device__ __forceinline__ void find_bin_from_top(const int* h, int nbins, int* s_bin, int* s_krem) {
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x, per = nbins / 64;
-        const int base_bin = (63 - lane) * per;
-        int s = 0;
-        for (int i = 0; i < per; i++) s += h[base_bin + i];
-        int inc = s;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int v = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += v;
-        }
-        const int exc = inc - s, krem = *s_krem;
-        if (exc < krem && krem <= inc) {
-            int cum = exc, b = base_bin + per - 1;
-            for (; b > base_bin; b--) {
-                if (cum + h[b] >= krem) break;
-                cum += h[b];
-            }
-            *s_bin = b;
-            *s_krem = krem - cum;
-        }
-    }
-}
-
-// descending bitonic sort of buf[0 .. p2), p2 a power of two >= 2, by the whole workgroup
-__device__ __forceinline__ void bitonic_desc(unsigned long long* buf, int p2) {
-    for (int size = 2; size <= p2; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < p2 / 2; t += blockDim.x) {
-                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long x = buf[lo], y = buf[hi];
-                if ((x < y) == desc) { buf[lo] = y; buf[hi] = x; }
-            }
-            __syncthreads();
-        }
-    }
-}
 
 // the want-th largest of the nonzero words a[0 .. m): six radix levels over all 64 bits (12, 12, 8 | 12, 12, 8); with first_level = 1 the top
 // 12 bits are known to be `pre` already.  All threads call; h: HB ints of LDS.  Returns the word (valid when 1 <= want <= #nonzero words).
@@ -128,7 +89,7 @@ __global__ __launch_bounds__(KT) void pyr_keys_kernel(PyrLevels lv, int L, unsig
     unsigned* kout = keys + lv.key0[l] + (size_t)img * n;
     for (int j = j0 + threadIdx.x; j < j1; j += KT) {
         const float x = base[(size_t)(j / A) * ld + (j % A)];
-        const unsigned key = __float_as_uint(1.f / (1.f + expf(-x)));
+        const unsigned key = abr::sigmoid_key(x);
         kout[j] = key;
         atomicAdd(&lh[key >> 20], 1);
     }
@@ -179,7 +140,7 @@ __global__ __launch_bounds__(KT) void pyr_partition_kernel(PyrLevels lv, int L, 
     for (int j = j0 + threadIdx.x; j < j1; j += KT) {
         const unsigned key = keys[j];
         const int bin = (int)(key >> 20);
-        const unsigned long long w = ((unsigned long long)key << 32) | (unsigned)(~(unsigned)j);
+        const unsigned long long w = abr::rank_word(key, (unsigned)j);
         if (bin > b1) {
             const int pos = base_s + atomicAdd(&n_s, 1);
             if (pos < KCAP) surv[pos] = w;
@@ -217,13 +178,13 @@ __global__ __launch_bounds__(TT) void pyr_select_sort_kernel(PyrLevels lv, int L
         }
         __syncthreads();
     }
-    bitonic_desc(buf, p2);
+    abr::bitonic_desc<TT>(buf, p2);
     float* so = scores + (size_t)seg * k_max;
     int64_t* io = idx + (size_t)seg * k_max;
     for (int r = threadIdx.x; r < k_max; r += TT) {
         const unsigned long long x = r < k ? buf[r] : 0ull;
-        so[r] = r < k ? __uint_as_float((unsigned)(x >> 32)) : 0.f;
-        io[r] = r < k ? (int64_t)(~(unsigned)(x & 0xFFFFFFFFu)) : 0;
+        so[r] = r < k ? __uint_as_float(abr::rank_word_key(x)) : 0.f;
+        io[r] = r < k ? (int64_t)abr::rank_word_index(x) : 0;
     }
 }
 
@@ -253,7 +214,6 @@ __global__ __launch_bounds__(TT) void pyr_decode_kernel(PyrLevels lv, int L, int
                                                         float* __restrict__ props, float* __restrict__ scores_out, int32_t* __restrict__ counts) {
     __shared__ int s_wave[TT / 64];
     __shared__ int s_base;
-    const float clip = 4.135166556742356f;  // log(1000/16), box_coder.py:20
     const int seg = blockIdx.x, i = seg / L, l = seg % L;
     const int k = lv.k[l], A = lv.A[l], ld = lv.ld[l], nloc = lv.n[l] / A;
     const float* reg = lv.y[l];
@@ -271,19 +231,8 @@ __global__ __launch_bounds__(TT) void pyr_decode_kernel(PyrLevels lv, int L, int
             const int64_t a = idx[(size_t)seg * k_max + t];
             sc = scores_in[(size_t)seg * k_max + t];
             const float* d = reg + ((size_t)i * nloc + a / A) * ld + A + 4 * (a % A);
-            const float4 b = reinterpret_cast<const float4*>(anchors)[a];
-            const float w = b.z - b.x + 1, h = b.w - b.y + 1;               // box_coder.py:66-69
-            const float cx = b.x + 0.5f * w, cy = b.y + 0.5f * h;
-            const float dx = d[0] / wx, dy = d[1] / wy;
-            const float dw = fminf(d[2] / ww, clip), dh = fminf(d[3] / wh, clip);
-            const float pcx = dx * w + cx, pcy = dy * h + cy;
-            const float pw = expf(dw) * w, ph = expf(dh) * h;
-            o = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw - 1, pcy + 0.5f * ph - 1);
-            const float W1 = (float)(img_hw[2 * i + 1] - 1), H1 = (float)(img_hw[2 * i] - 1);   // bounding_box.py:214-225 clip_to_image
-            o.x = fminf(fmaxf(o.x, 0.f), W1);
-            o.y = fminf(fmaxf(o.y, 0.f), H1);
-            o.z = fminf(fmaxf(o.z, 0.f), W1);
-            o.w = fminf(fmaxf(o.w, 0.f), H1);
+            o = abr::box_decode(reinterpret_cast<const float4*>(anchors)[a], d, wx, wy, ww, wh);
+            o = abr::box_clip(o, (float)(img_hw[2 * i + 1] - 1), (float)(img_hw[2 * i] - 1));
             // boxlist_ops.py:34-48 remove_small_boxes; min_size <= 0 keeps every row, as the single-level path does
             keep = min_size <= 0.f || ((o.z - o.x + 1 >= min_size) && (o.w - o.y + 1 >= min_size));
         }
@@ -302,12 +251,6 @@ __global__ __launch_bounds__(TT) void pyr_decode_kernel(PyrLevels lv, int L, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------- selection
-// orders like the float for any finite value (topk.hip's raw key)
-__device__ __forceinline__ unsigned order_key(float x) {
-    const unsigned b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // candidate position g = (image * L + level) * post + rank -> its word, 0 where the level kept fewer than rank + 1 boxes
 __global__ void sel_words_kernel(const float* __restrict__ scores, const int32_t* __restrict__ keep, const int32_t* __restrict__ n_keep, int total, int k_max,
                                  int post, unsigned long long* __restrict__ words) {
@@ -317,7 +260,7 @@ __global__ void sel_words_kernel(const float* __restrict__ scores, const int32_t
     unsigned long long w = 0ull;
     if (r < min(n_keep[seg], post)) {
         const int row = keep[(size_t)seg * post + r];
-        w = ((unsigned long long)order_key(scores[(size_t)seg * k_max + row]) << 32) | (unsigned)(~(unsigned)g);
+        w = abr::rank_word(abr::order_key(scores[(size_t)seg * k_max + row]), (unsigned)g);
     }
     words[g] = w;
 }
@@ -376,9 +319,9 @@ __global__ __launch_bounds__(TT) void sel_emit_kernel(const unsigned long long* 
                 }
             }
             __syncthreads();
-            bitonic_desc(buf, p2);
+            abr::bitonic_desc<TT>(buf, p2);
             for (int r = threadIdx.x; r < count; r += TT) {
-                const int p = (int)(~(unsigned)(buf[r] & 0xFFFFFFFFu)) - i * per_img;
+                const int p = (int)abr::rank_word_index(buf[r]) - i * per_img;
                 const int seg = i * L + p / post;
                 const int row = keep[(size_t)seg * post + p % post];
                 ro[r] = reinterpret_cast<const float4*>(props)[(size_t)seg * k_max + row];

@@ -35,12 +35,7 @@ struct LossLevels {          // by value in the kernel arguments: no device-side
     long long goff[MAXL];    // first float of the level's block in the gradient storage
 };
 
-__device__ __forceinline__ float sl1_ninth(float d, float* g) {   // layers/smooth_l1_loss.py:6-17 (losses.hip's sl1)
-    const float beta = 1.0f / 9, a = fabsf(d);
-    if (a < beta) { *g = d / beta; return 0.5f * a * a / beta; }
-    *g = d > 0.f ? 1.f : -1.f;
-    return a - 0.5f * beta;
-}
+__device__ __forceinline__ float sl1_ninth(float d, float* g) { return abr::sl1(d, 1.0f / 9, g); }   // the RPN's beta (rpn/loss.py:136)
 
 // sum over the workgroup in a fixed order; valid in every thread
 __device__ __forceinline__ float tree_sum(float v, float* sm) {

@@ -11,22 +11,19 @@
 // Scores are non-negative floats, so their bit patterns order like the values.
 #include <algorithm>
 
-#include "common.h"
+#include "rank_select.h"
 
 namespace {
+
+using abr::find_bin_from_top;
 
 constexpr int TT = 1024;
 constexpr int CAP = 16384;  // LDS sort capacity (64-bit words)
 
-// raw = 0: the key is the bit pattern of sigmoid(x) (non-negative: orders like the value).  raw = 1 (abr_sort_scores_desc: the score sort of
-// _C.nms): the key orders like x itself for ANY finite float -- sign bit flipped for x >= 0, all bits for x < 0 (-0 sorts below +0, NaNs at the ends)
+// raw = 0: abr::sigmoid_key of the logit.  raw = 1 (abr_sort_scores_desc: the score sort of _C.nms): abr::order_key, the order of x itself
 __device__ __forceinline__ unsigned score_bits(const float* __restrict__ base, int j, int A, int ld, int raw) {
     const float x = base[(size_t)(j / A) * ld + (j % A)];
-    if (raw) {
-        const unsigned b = __float_as_uint(x);
-        return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    return __float_as_uint(1.f / (1.f + expf(-x)));
+    return raw ? abr::order_key(x) : abr::sigmoid_key(x);
 }
 
 // Phase 1, chip-wide (grid = G slices x N images): the sigmoid key of every anchor, once, into a scratch + a histogram of the keys' top 12 bits
@@ -51,32 +48,6 @@ __global__ __launch_bounds__(KT) void topk_keys_kernel(const float* __restrict__
     __syncthreads();
     for (int i = threadIdx.x; i < HB; i += KT)
         if (lh[i]) atomicAdd(&hist[img * HB + i], lh[i]);
-}
-
-// wave 0: the bin holding the s_krem-th largest element of histogram h (nbins a multiple of 64), counted from the TOP bin -> s_bin, s_krem -= what lies above it
-__device__ __forceinline__ void find_bin_from_top(const int* h, int nbins, int* s_bin, int* s_krem) {
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x, per = nbins / 64;
-        const int base_bin = (63 - lane) * per;          // lane 0 owns the top bins: a prefix scan over lanes is a suffix sum over bins
-        int s = 0;
-        for (int i = 0; i < per; i++) s += h[base_bin + i];
-        int inc = s;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int v = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += v;
-        }
-        const int exc = inc - s, krem = *s_krem;
-        if (exc < krem && krem <= inc) {
-            int cum = exc, b = base_bin + per - 1;
-            for (; b > base_bin; b--) {
-                if (cum + h[b] >= krem) break;
-                cum += h[b];
-            }
-            *s_bin = b;
-            *s_krem = krem - cum;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -122,7 +93,7 @@ __global__ __launch_bounds__(KT) void topk_partition_kernel(const unsigned* __re
     for (int j = j0 + threadIdx.x; j < j1; j += KT) {
         const unsigned key = keys[j];
         const int bin = (int)(key >> 20);
-        const unsigned long long w = ((unsigned long long)key << 32) | (unsigned)(~(unsigned)j);
+        const unsigned long long w = abr::rank_word(key, (unsigned)j);
         if (bin > b1) st_s[atomicAdd(&n_s, 1)] = w;
         else if (bin == b1) st_c[atomicAdd(&n_c, 1)] = w;
     }
@@ -226,18 +197,7 @@ __global__ __launch_bounds__(256) void topk_chunk_sort_kernel(unsigned long long
     unsigned long long* a = surv_all + (size_t)img * CAP + (size_t)c * CH;
     for (int i = threadIdx.x; i < CH; i += 256) buf[i] = a[i];
     __syncthreads();
-    for (int size = 2; size <= CH; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-#pragma unroll
-            for (int t = threadIdx.x; t < CH / 2; t += 256) {
-                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long x = buf[lo], y = buf[hi];
-                if ((x < y) == desc) { buf[lo] = y; buf[hi] = x; }
-            }
-            __syncthreads();
-        }
-    }
+    abr::bitonic_desc<256>(buf, CH);
     for (int i = threadIdx.x; i < CH; i += 256) a[i] = buf[i];
 }
 
@@ -271,8 +231,8 @@ __global__ __launch_bounds__(TT) void topk_merge_emit_kernel(const unsigned long
         rank += lo;
     }
     if (rank < k) {
-        if (scores) scores[(size_t)img * k + rank] = __uint_as_float((unsigned)(x >> 32));
-        idx[(size_t)img * k + rank] = (int64_t)(~(unsigned)(x & 0xFFFFFFFFu));
+        if (scores) scores[(size_t)img * k + rank] = __uint_as_float(abr::rank_word_key(x));
+        idx[(size_t)img * k + rank] = (int64_t)abr::rank_word_index(x);
     }
 }
 

@@ -369,12 +369,7 @@ class RPNPostProcessor(nn.Module):
         else:            # beyond the in-LDS sort capacity (no voc config gets here: PRE_NMS_TOP_N is 12000 / 6000)
             scores, topk_idx = yf[:, :, :A].reshape(N, n_anchor).sigmoid().topk(k, dim=1, sorted=True)
         same = all(a[0].bbox.data_ptr() == anchors[0][0].bbox.data_ptr() for a in anchors)
-        hw_key = (tuple((a[0].size[1], a[0].size[0]) for a in anchors), y.device)
-        img_hw = self._hw_cache.get(hw_key)   # image sizes repeat from step to step: keep the device copy
-        if img_hw is None:
-            if len(self._hw_cache) > 64:
-                self._hw_cache.clear()
-            img_hw = self._hw_cache[hw_key] = ops.h2d([list(v) for v in hw_key[0]], torch.int32, y.device)
+        img_hw = self._img_hw(anchors, y.device)
         assert same, "per-image anchor grids of one batch share (H,W): they differ only in the visibility field"
         props = ops.rpn_decode_clip(yf, A, anchors[0][0].bbox, topk_idx, img_hw, self.box_coder.weights, A=A)  # :101-112
         counts = torch.full((N,), k, dtype=torch.int32, device=y.device)   # (MIN_SIZE == 0 here: remove_small_boxes drops nothing)
@@ -739,38 +734,23 @@ class RPNModule(nn.Module):
 
     def forward_begin(self, images, features, targets, rpn_output_source=None):
         """Training forward up to (not including) the read-back of the proposal counts: head conv, anchors, the proposal selection
-        launched on a side stream, the loss on the current stream."""
-        if len(features) > 1:   # a feature pyramid: the shared head per level, selector and loss over the list (rpn.py:161-183)
-            return self.forward_begin_pyramid(images, features, targets, rpn_output_source)
-        fused = self.head.forward_fused(features[0])
-        A = self.head.num_anchors
-        anchors = self.anchor_generator(images, features)
-        rpn_output = ([fused[:, :A]], [fused[:, A:5 * A]])
-        with torch.no_grad():
-            self.box_selector_train.train()
-            if PROPOSALS_SIDE_STREAM and fused.is_cuda:   # selection runs next to the loss kernels below
-                pending = self.box_selector_train.launch_on_side_stream(anchors, fused.detach(), A)
-            else:
-                pending = self.box_selector_train.launch(anchors, fused.detach(), A)
-        loss_objectness, loss_rpn_box_reg = self.loss_evaluator(anchors, None, None, targets, rpn_output_source, fused=fused)
-        return dict(pending=pending, targets=targets, anchors=anchors, rpn_output=rpn_output,
-                    losses={"loss_objectness": loss_objectness, "loss_rpn_box_reg": loss_rpn_box_reg})
-
-    def forward_begin_pyramid(self, images, features, targets, rpn_output_source=None):
-        """forward_begin over L > 1 maps: the head's weight and bias gradients accumulate over the L backward nodes (conv_wgrad and bias_grad add
-        into the fused gradient buffers)."""
+        launched on a side stream, the loss on the current stream.  One feature map or a pyramid (rpn.py:161-183): the shared head runs per
+        level, and over L > 1 maps its weight and bias gradients accumulate over the L backward nodes (conv_wgrad and bias_grad add into the
+        fused gradient buffers)."""
         A = self.head.num_anchors
         fused = [self.head.forward_fused(f) for f in features]
         anchors = self.anchor_generator(images, features)
         rpn_output = ([f[:, :A] for f in fused], [f[:, A:5 * A] for f in fused])
+        # one level: the selector and the loss get the tensor, not a one-element list, and take their single-level routes
+        head_out = fused if len(fused) > 1 else fused[0]
         with torch.no_grad():
             self.box_selector_train.train()
-            detached = [f.detach() for f in fused]
-            if PROPOSALS_SIDE_STREAM and fused[0].is_cuda:
+            detached = [f.detach() for f in fused] if len(fused) > 1 else fused[0].detach()
+            if PROPOSALS_SIDE_STREAM and fused[0].is_cuda:   # selection runs next to the loss kernels below
                 pending = self.box_selector_train.launch_on_side_stream(anchors, detached, A)
             else:
                 pending = self.box_selector_train.launch(anchors, detached, A)
-        loss_objectness, loss_rpn_box_reg = self.loss_evaluator(anchors, None, None, targets, rpn_output_source, fused=fused)
+        loss_objectness, loss_rpn_box_reg = self.loss_evaluator(anchors, None, None, targets, rpn_output_source, fused=head_out)
         return dict(pending=pending, targets=targets, anchors=anchors, rpn_output=rpn_output,
                     losses={"loss_objectness": loss_objectness, "loss_rpn_box_reg": loss_rpn_box_reg})
 

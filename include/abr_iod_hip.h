@@ -634,7 +634,8 @@ int abr_rpn_pyramid_max_k(void);
  * ascending index -- bit for bit what abr_topk_sigmoid returns for that level alone; entries k_l .. k_max-1 are 0. */
 int abr_rpn_pyramid_topk(const float* const* y_host, const int* nloc_host, const int* A_host, const int* ld_host, int L, int N, int pre_nms_top_n,
                          int k_max, float* scores, int64_t* idx, void* stream);
-/* BoxCoder.decode + clip_to_image of the ranked anchors with abr_rpn_decode_clip's arithmetic (ld[l] >= 5 A[l]; anchors_host[l] = device [nloc*A,4]),
+/* BoxCoder.decode + clip_to_image of the ranked anchors (ld[l] >= 5 A[l]; anchors_host[l] = device [nloc*A,4]) through the one decode and clip
+ * that abr_rpn_decode_clip and abr_det_softmax_decode call too (csrc/box_math.h), so the three agree bit for bit on the same inputs,
  * then remove_small_boxes (boxlist_ops.py:34-48: keep iff x2-x1+1 >= min_size and y2-y1+1 >= min_size; min_size <= 0 keeps every row) and a stable
  * compaction: props [S,k_max,4] / scores_out [S,k_max] hold each segment's survivors in rank order without holes (rows past the count: 0),
  * counts [S] int32 (device; may be 0).  img_hw [N,2] int32 (h, w). */

@@ -101,6 +101,9 @@ _SIGS = {
     "abr_fpn_levels": (_i, [_vp, _i, _f, _f, _f, _f, _f, _vp, _vp]),
     "abr_roi_align_pyramid_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
     "abr_roi_align_pyramid_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _vp, _vp]),
+    "abr_roi_align_pyramid_rows_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "abr_roi_align_pyramid_rows_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _vp,
+                                                 _vp]),
     "abr_fpn_topdown_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "abr_fpn_topdown_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "abr_fpn_subsample2_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

@@ -817,6 +817,13 @@ __global__ __launch_bounds__(256) void fpn_levels_kernel(const float* __restrict
     if (n < K) levels[n] = fpn_level(rois + 5 * (size_t)n, rule);
 }
 
+// this workgroup's bins of output row n, all zero
+__device__ __forceinline__ void zero_bins(float* __restrict__ out, int n, int bin0, int bpb, int nbins, int C) {
+    const int cnt = min(bpb, nbins - bin0) * C;
+    float* o = out + ((size_t)n * nbins + bin0) * C;
+    for (int i = threadIdx.x; i < cnt; i += 256) o[i] = 0.f;
+}
+
 #pragma clang fp contract(off)
 template <int VEC>
 __global__ __launch_bounds__(256) void roi_align_pyramid_fwd(Pyramid<float> py, const float* __restrict__ rois, int C, int PH, int PW, int sr, int bpb,
@@ -831,10 +838,7 @@ __global__ __launch_bounds__(256) void roi_align_pyramid_fwd(Pyramid<float> py, 
     const int lv = __builtin_amdgcn_readfirstlane(fpn_level(roi, py.rule));
     if (levels_out && bin0 == 0 && threadIdx.x == 0) levels_out[n] = lv;
     if (lv < 0) {   // no level: the row is zero (poolers.py:99)
-        const int nbins = PH * PW;
-        const int cnt = min(bpb, nbins - bin0) * C;
-        float* o = out + ((size_t)n * nbins + bin0) * C;
-        for (int i = threadIdx.x; i < cnt; i += 256) o[i] = 0.f;
+        zero_bins(out, n, bin0, bpb, PH * PW, C);
         return;
     }
     fwd_nhwc_tile<VEC>(py.feat[lv], roi, n, bin0, 0, C, py.H[lv], py.W[lv], py.scale[lv], PH, PW, sr, 1, PH, PW, bpb, tx, 1, out, s_idx, s_w);
@@ -867,6 +871,72 @@ __global__ __launch_bounds__(256) void roi_align_pyramid_bwd_sep(Pyramid<double>
     const int lv = __builtin_amdgcn_readfirstlane(fpn_level(roi, py.rule));
     if (lv < 0) return;
     bwd_nhwc_sep_tile<VEC, double>(grad, roi, n, chunk, C, py.H[lv], py.W[lv], py.scale[lv], PH, PW, sr, 1, PH, PW, tx, py.feat[lv], sm);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The indexed forms: workgroup p pools row rows[p] of the table into out[p] (backward: scatters grad[p]).  The FPN mask head pools the
+// positives of the box head's sampled set, a -1-padded row list on the device (ops.mask_compact_pos): no gathered copy of the table.
+// The row index is a per-workgroup scalar like the level; a padding entry (negative, or >= K) never reaches the table or the tile code:
+// its output is zero and its level -1 (forward), it adds nothing and its grad row is not read (backward).
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int table_row(const int64_t* __restrict__ rows, int p, int K) {
+    const int64_t r = rows[p];
+    return __builtin_amdgcn_readfirstlane((r >= 0 && r < (int64_t)K) ? (int)r : -1);
+}
+
+#pragma clang fp contract(off)
+template <int VEC>
+__global__ __launch_bounds__(256) void roi_align_pyramid_rows_fwd(Pyramid<float> py, const float* __restrict__ rois, const int64_t* __restrict__ rows,
+                                                                   int K, int C, int PH, int PW, int sr, int bpb, int tx, int blocks_per_roi,
+                                                                   float* __restrict__ out, int32_t* __restrict__ levels_out) {
+    __shared__ int4 s_idx[256];
+    __shared__ float4 s_w[256];
+    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const int p = bid / blocks_per_roi;
+    const int bin0 = (bid % blocks_per_roi) * bpb;
+    const int row = table_row(rows, p, K);
+    const float* roi = rois + 5 * (size_t)max(row, 0);
+    const int lv = row < 0 ? -1 : __builtin_amdgcn_readfirstlane(fpn_level(roi, py.rule));
+    if (levels_out && bin0 == 0 && threadIdx.x == 0) levels_out[p] = lv;
+    if (lv < 0) {   // padding, or a row without a level
+        zero_bins(out, p, bin0, bpb, PH * PW, C);
+        return;
+    }
+    fwd_nhwc_tile<VEC>(py.feat[lv], roi, p, bin0, 0, C, py.H[lv], py.W[lv], py.scale[lv], PH, PW, sr, 1, PH, PW, bpb, tx, 1, out, s_idx, s_w);
+}
+
+#pragma clang fp contract(off)
+template <int VEC>
+__global__ __launch_bounds__(256) void roi_align_pyramid_rows_bwd(Pyramid<double> py, const float* __restrict__ grad, const float* __restrict__ rois,
+                                                                   const int64_t* __restrict__ rows, int K, int C, int PH, int PW, int sr, int bpb,
+                                                                   int tx, int blocks_per_roi) {
+    __shared__ int4 s_idx[256];
+    __shared__ float4 s_w[256];
+    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const int p = bid / blocks_per_roi;
+    const int bin0 = (bid % blocks_per_roi) * bpb;
+    const int row = table_row(rows, p, K);
+    if (row < 0) return;
+    const float* roi = rois + 5 * (size_t)row;
+    const int lv = __builtin_amdgcn_readfirstlane(fpn_level(roi, py.rule));
+    if (lv < 0) return;
+    bwd_nhwc_tile<VEC, double>(grad, roi, p, bin0, C, py.H[lv], py.W[lv], py.scale[lv], PH, PW, sr, 1, PH, PW, bpb, tx, py.feat[lv], s_idx, s_w);
+}
+
+#pragma clang fp contract(off)
+template <int VEC>
+__global__ __launch_bounds__(256) void roi_align_pyramid_rows_bwd_sep(Pyramid<double> py, const float* __restrict__ grad,
+                                                                       const float* __restrict__ rois, const int64_t* __restrict__ rows, int K, int C,
+                                                                       int PH, int PW, int sr, int tx, int cchunks) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const unsigned bid = abr::xcd_remap(blockIdx.x, gridDim.x);
+    const int p = bid / cchunks, chunk = bid % cchunks;
+    const int row = table_row(rows, p, K);
+    if (row < 0) return;
+    const float* roi = rois + 5 * (size_t)row;
+    const int lv = __builtin_amdgcn_readfirstlane(fpn_level(roi, py.rule));
+    if (lv < 0) return;
+    bwd_nhwc_sep_tile<VEC, double>(grad, roi, p, chunk, C, py.H[lv], py.W[lv], py.scale[lv], PH, PW, sr, 1, PH, PW, tx, py.feat[lv], sm);
 }
 
 // The backward's last step: every element of every level's gradient = (accumulate ? what is there : 0) + the float64 sum, rounded ONCE.
@@ -913,6 +983,127 @@ int make_pyramid(const char* name, const void* feats, const int* H, const int* W
     return ABR_OK;
 }
 
+// Both forward entry points.  rows == nullptr: N = K, workgroup n pools row n.  Otherwise N = P entries of `rows` into a table of K rows.
+int pyramid_forward(const char* name, const float* const* feats, const int* H, const int* W, const float* scales, int L, const float* rois,
+                    const int64_t* rows, int N, int K, int B, int C, int PH, int PW, int sr, float k_min, float k_max, float s0, float lvl0, float eps,
+                    float* out, int32_t* levels_out, void* stream) {
+    Pyramid<float> py;
+    const int rc = make_pyramid(name, feats, H, W, scales, L, N, B, C, PH, PW, k_min, k_max, s0, lvl0, eps, &py);
+    if (rc != ABR_OK) return rc;
+    ABR_REQUIRE(K >= 0, "%s: bad shape", name);
+    if (N == 0) return ABR_OK;
+    ABR_REQUIRE((rois || (rows && K == 0)) && out, "%s: null pointer", name);
+    for (int l = 0; l < L; l++) {
+        ABR_REQUIRE(feats[l], "%s: null map at level %d", name, l);
+        py.feat[l] = const_cast<float*>(feats[l]);
+    }
+    hipStream_t st = abr::as_stream(stream);
+    const int nbins = PH * PW;
+    const int vec = (C % 4 == 0) ? 4 : 1;
+    int tx, bpb;
+    pick_shape(C / vec, nbins, &tx, &bpb);
+    const int bpr = (nbins + bpb - 1) / bpb;
+    const unsigned grid = (unsigned)(N * bpr);
+    if (rows) {
+        if (vec == 4)
+            roi_align_pyramid_rows_fwd<4><<<grid, 256, 0, st>>>(py, rois, rows, K, C, PH, PW, sr, bpb, tx, bpr, out, levels_out);
+        else
+            roi_align_pyramid_rows_fwd<1><<<grid, 256, 0, st>>>(py, rois, rows, K, C, PH, PW, sr, bpb, tx, bpr, out, levels_out);
+    } else {
+        if (vec == 4)
+            roi_align_pyramid_fwd<4><<<grid, 256, 0, st>>>(py, rois, C, PH, PW, sr, bpb, tx, bpr, out, levels_out);
+        else
+            roi_align_pyramid_fwd<1><<<grid, 256, 0, st>>>(py, rois, C, PH, PW, sr, bpb, tx, bpr, out, levels_out);
+    }
+    ABR_CHECK_LAUNCH(name);
+    return ABR_OK;
+}
+
+// Both backward entry points; rows, N and K as for pyramid_forward.
+int pyramid_backward(const char* name, const float* grad, const float* rois, const int64_t* rows, int N, int K, int B, int C, const int* H,
+                     const int* W, const float* scales, int L, int PH, int PW, int sr, float k_min, float k_max, float s0, float lvl0, float eps,
+                     int accumulate, float* const* grad_feats, void* stream) {
+    Pyramid<double> py;
+    const int rc = make_pyramid(name, grad_feats, H, W, scales, L, N, B, C, PH, PW, k_min, k_max, s0, lvl0, eps, &py);
+    if (rc != ABR_OK) return rc;
+    ABR_REQUIRE(K >= 0, "%s: bad shape", name);
+    for (int l = 0; l < L; l++) ABR_REQUIRE(grad_feats[l], "%s: null output at level %d", name, l);
+    hipStream_t st = abr::as_stream(stream);
+    if (N == 0) {   // nothing to add: every level, reached or not, is zero unless accumulating
+        for (int l = 0; l < L && !accumulate; l++) {
+            if (hipMemsetAsync(grad_feats[l], 0, sizeof(float) * (size_t)B * C * H[l] * W[l], st) != hipSuccess) {
+                abr::set_error("%s: memset failed", name);
+                return ABR_E_LAUNCH;
+            }
+        }
+        return ABR_OK;
+    }
+    ABR_REQUIRE(grad && (rois || (rows && K == 0)), "%s: null pointer", name);
+    // The atomics add into zeroed float64 scratch, one buffer per level back to back, and roi_align_pyramid_round rounds each sum to the
+    // gradient once.  With float32 atomics an element that hundreds of RoIs reach is a float32 sum in arrival order: every add rounds at the
+    // ulp of the running sum, and 300 small terms behind three large ones measured 1.1e-6 of the sum of |addends| (MEASUREMENTS.md).
+    PyramidOut po;
+    int64_t total = 0;
+    for (int l = 0; l < ABR_MAX_PYRAMID_LEVELS; l++) {
+        if (l < L) total += (int64_t)B * H[l] * W[l] * C;
+        po.dst[l] = l < L ? grad_feats[l] : nullptr;
+        po.end[l] = total;
+    }
+    double* acc = static_cast<double*>(abr::scratch(abr::SCRATCH_ROI_PYRAMID, st, sizeof(double) * (size_t)total));
+    if (!acc) {
+        abr::set_error("%s: no memory for %lld bytes of accumulation scratch", name, (long long)(sizeof(double) * total));
+        return ABR_E_WORKSPACE;
+    }
+    if (hipMemsetAsync(acc, 0, sizeof(double) * (size_t)total, st) != hipSuccess) {
+        abr::set_error("%s: memset failed", name);
+        return ABR_E_LAUNCH;
+    }
+    for (int l = 0; l < L; l++) py.feat[l] = acc + (l ? po.end[l - 1] : 0);
+    const int vec = (C % 4 == 0) ? 4 : 1;
+    const int cvecs = C / vec;
+    size_t sep_lds = 0;
+    for (int l = 0; l < L; l++) sep_lds = std::max(sep_lds, sizeof(float) * ((size_t)PH * H[l] + (size_t)PW * W[l]) + 16);
+    if (PH <= kMaxPo && PW <= kMaxPo && sep_lds <= 60 * 1024) {
+        int t = 1;
+        while (t < cvecs && t < 256) t <<= 1;
+        if (t < 16) t = 16;
+        const int cchunks = (cvecs + t - 1) / t;
+        const unsigned grid = (unsigned)(N * cchunks);
+        if (rows) {
+            if (vec == 4)
+                roi_align_pyramid_rows_bwd_sep<4><<<grid, 256, sep_lds, st>>>(py, grad, rois, rows, K, C, PH, PW, sr, t, cchunks);
+            else
+                roi_align_pyramid_rows_bwd_sep<1><<<grid, 256, sep_lds, st>>>(py, grad, rois, rows, K, C, PH, PW, sr, t, cchunks);
+        } else {
+            if (vec == 4)
+                roi_align_pyramid_bwd_sep<4><<<grid, 256, sep_lds, st>>>(py, grad, rois, C, PH, PW, sr, t, cchunks);
+            else
+                roi_align_pyramid_bwd_sep<1><<<grid, 256, sep_lds, st>>>(py, grad, rois, C, PH, PW, sr, t, cchunks);
+        }
+    } else {
+        const int nbins = PH * PW;
+        int tx, bpb;
+        pick_shape(cvecs, nbins, &tx, &bpb);
+        const int bpr = (nbins + bpb - 1) / bpb;
+        const unsigned grid = (unsigned)(N * bpr);
+        if (rows) {
+            if (vec == 4)
+                roi_align_pyramid_rows_bwd<4><<<grid, 256, 0, st>>>(py, grad, rois, rows, K, C, PH, PW, sr, bpb, tx, bpr);
+            else
+                roi_align_pyramid_rows_bwd<1><<<grid, 256, 0, st>>>(py, grad, rois, rows, K, C, PH, PW, sr, bpb, tx, bpr);
+        } else {
+            if (vec == 4)
+                roi_align_pyramid_bwd<4><<<grid, 256, 0, st>>>(py, grad, rois, C, PH, PW, sr, bpb, tx, bpr);
+            else
+                roi_align_pyramid_bwd<1><<<grid, 256, 0, st>>>(py, grad, rois, C, PH, PW, sr, bpb, tx, bpr);
+        }
+    }
+    ABR_CHECK_LAUNCH(name);
+    roi_align_pyramid_round<<<(unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32), 256, 0, st>>>(acc, po, L, accumulate);
+    ABR_CHECK_LAUNCH(name);
+    return ABR_OK;
+}
+
 }  // namespace
 
 extern "C" int abr_fpn_levels(const float* rois, int K, float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
@@ -930,98 +1121,33 @@ extern "C" int abr_fpn_levels(const float* rois, int K, float k_min, float k_max
 extern "C" int abr_roi_align_pyramid_forward(const float* const* feats, const int* H, const int* W, const float* scales, int L, const float* rois, int K,
                                              int B, int C, int PH, int PW, int sr, float k_min, float k_max, float canonical_scale,
                                              float canonical_level, float eps, float* out, int32_t* levels_out, void* stream) {
-    Pyramid<float> py;
-    const int rc = make_pyramid("roi_align_pyramid_forward", feats, H, W, scales, L, K, B, C, PH, PW, k_min, k_max, canonical_scale, canonical_level,
-                                eps, &py);
-    if (rc != ABR_OK) return rc;
-    if (K == 0) return ABR_OK;
-    ABR_REQUIRE(rois && out, "roi_align_pyramid_forward: null pointer");
-    for (int l = 0; l < L; l++) {
-        ABR_REQUIRE(feats[l], "roi_align_pyramid_forward: null map at level %d", l);
-        py.feat[l] = const_cast<float*>(feats[l]);
-    }
-    hipStream_t st = abr::as_stream(stream);
-    const int nbins = PH * PW;
-    int tx, bpb;
-    if (C % 4 == 0) {
-        pick_shape(C / 4, nbins, &tx, &bpb);
-        const int bpr = (nbins + bpb - 1) / bpb;
-        roi_align_pyramid_fwd<4><<<(unsigned)(K * bpr), 256, 0, st>>>(py, rois, C, PH, PW, sr, bpb, tx, bpr, out, levels_out);
-    } else {
-        pick_shape(C, nbins, &tx, &bpb);
-        const int bpr = (nbins + bpb - 1) / bpb;
-        roi_align_pyramid_fwd<1><<<(unsigned)(K * bpr), 256, 0, st>>>(py, rois, C, PH, PW, sr, bpb, tx, bpr, out, levels_out);
-    }
-    ABR_CHECK_LAUNCH("roi_align_pyramid_forward");
-    return ABR_OK;
+    return pyramid_forward("roi_align_pyramid_forward", feats, H, W, scales, L, rois, nullptr, K, K, B, C, PH, PW, sr, k_min, k_max, canonical_scale,
+                           canonical_level, eps, out, levels_out, stream);
+}
+
+extern "C" int abr_roi_align_pyramid_rows_forward(const float* const* feats, const int* H, const int* W, const float* scales, int L, const float* rois,
+                                                  int K, const int64_t* rows, int P, int B, int C, int PH, int PW, int sr, float k_min, float k_max,
+                                                  float canonical_scale, float canonical_level, float eps, float* out, int32_t* levels_out,
+                                                  void* stream) {
+    ABR_REQUIRE(P >= 0 && (rows || P == 0), "roi_align_pyramid_rows_forward: P = %d rows, list %s", P, rows ? "given" : "null");
+    return pyramid_forward("roi_align_pyramid_rows_forward", feats, H, W, scales, L, rois, rows, P, K, B, C, PH, PW, sr, k_min, k_max,
+                           canonical_scale, canonical_level, eps, out, levels_out, stream);
 }
 
 extern "C" int abr_roi_align_pyramid_backward(const float* grad, const float* rois, int K, int B, int C, const int* H, const int* W, const float* scales,
                                               int L, int PH, int PW, int sr, float k_min, float k_max, float canonical_scale, float canonical_level,
                                               float eps, int accumulate, float* const* grad_feats, void* stream) {
-    Pyramid<double> py;
-    const int rc = make_pyramid("roi_align_pyramid_backward", grad_feats, H, W, scales, L, K, B, C, PH, PW, k_min, k_max, canonical_scale,
-                                canonical_level, eps, &py);
-    if (rc != ABR_OK) return rc;
-    for (int l = 0; l < L; l++) ABR_REQUIRE(grad_feats[l], "roi_align_pyramid_backward: null output at level %d", l);
-    hipStream_t st = abr::as_stream(stream);
-    if (K == 0) {   // nothing to add: every level, reached or not, is zero unless accumulating
-        for (int l = 0; l < L && !accumulate; l++) {
-            if (hipMemsetAsync(grad_feats[l], 0, sizeof(float) * (size_t)B * C * H[l] * W[l], st) != hipSuccess) {
-                abr::set_error("roi_align_pyramid_backward: memset failed");
-                return ABR_E_LAUNCH;
-            }
-        }
-        return ABR_OK;
-    }
-    ABR_REQUIRE(grad && rois, "roi_align_pyramid_backward: null pointer");
-    // The atomics add into zeroed float64 scratch, one buffer per level back to back, and roi_align_pyramid_round rounds each sum to the
-    // gradient once.  With float32 atomics an element that hundreds of RoIs reach is a float32 sum in arrival order: every add rounds at the
-    // ulp of the running sum, and 300 small terms behind three large ones measured 1.1e-6 of the sum of |addends| (MEASUREMENTS.md).
-    PyramidOut po;
-    int64_t total = 0;
-    for (int l = 0; l < ABR_MAX_PYRAMID_LEVELS; l++) {
-        if (l < L) total += (int64_t)B * H[l] * W[l] * C;
-        po.dst[l] = l < L ? grad_feats[l] : nullptr;
-        po.end[l] = total;
-    }
-    double* acc = static_cast<double*>(abr::scratch(abr::SCRATCH_ROI_PYRAMID, st, sizeof(double) * (size_t)total));
-    if (!acc) {
-        abr::set_error("roi_align_pyramid_backward: no memory for %lld bytes of accumulation scratch", (long long)(sizeof(double) * total));
-        return ABR_E_WORKSPACE;
-    }
-    if (hipMemsetAsync(acc, 0, sizeof(double) * (size_t)total, st) != hipSuccess) {
-        abr::set_error("roi_align_pyramid_backward: memset failed");
-        return ABR_E_LAUNCH;
-    }
-    for (int l = 0; l < L; l++) py.feat[l] = acc + (l ? po.end[l - 1] : 0);
-    const int vec = (C % 4 == 0) ? 4 : 1;
-    const int cvecs = C / vec;
-    size_t sep_lds = 0;
-    for (int l = 0; l < L; l++) sep_lds = std::max(sep_lds, sizeof(float) * ((size_t)PH * H[l] + (size_t)PW * W[l]) + 16);
-    if (PH <= kMaxPo && PW <= kMaxPo && sep_lds <= 60 * 1024) {
-        int t = 1;
-        while (t < cvecs && t < 256) t <<= 1;
-        if (t < 16) t = 16;
-        const int cchunks = (cvecs + t - 1) / t;
-        if (vec == 4)
-            roi_align_pyramid_bwd_sep<4><<<(unsigned)(K * cchunks), 256, sep_lds, st>>>(py, grad, rois, C, PH, PW, sr, t, cchunks);
-        else
-            roi_align_pyramid_bwd_sep<1><<<(unsigned)(K * cchunks), 256, sep_lds, st>>>(py, grad, rois, C, PH, PW, sr, t, cchunks);
-    } else {
-        const int nbins = PH * PW;
-        int tx, bpb;
-        pick_shape(cvecs, nbins, &tx, &bpb);
-        const int bpr = (nbins + bpb - 1) / bpb;
-        if (vec == 4)
-            roi_align_pyramid_bwd<4><<<(unsigned)(K * bpr), 256, 0, st>>>(py, grad, rois, C, PH, PW, sr, bpb, tx, bpr);
-        else
-            roi_align_pyramid_bwd<1><<<(unsigned)(K * bpr), 256, 0, st>>>(py, grad, rois, C, PH, PW, sr, bpb, tx, bpr);
-    }
-    ABR_CHECK_LAUNCH("roi_align_pyramid_backward");
-    roi_align_pyramid_round<<<(unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32), 256, 0, st>>>(acc, po, L, accumulate);
-    ABR_CHECK_LAUNCH("roi_align_pyramid_backward");
-    return ABR_OK;
+    return pyramid_backward("roi_align_pyramid_backward", grad, rois, nullptr, K, K, B, C, H, W, scales, L, PH, PW, sr, k_min, k_max, canonical_scale,
+                            canonical_level, eps, accumulate, grad_feats, stream);
+}
+
+extern "C" int abr_roi_align_pyramid_rows_backward(const float* grad, const float* rois, const int64_t* rows, int P, int K, int B, int C, const int* H,
+                                                   const int* W, const float* scales, int L, int PH, int PW, int sr, float k_min, float k_max,
+                                                   float canonical_scale, float canonical_level, float eps, int accumulate, float* const* grad_feats,
+                                                   void* stream) {
+    ABR_REQUIRE(P >= 0 && (rows || P == 0), "roi_align_pyramid_rows_backward: P = %d rows, list %s", P, rows ? "given" : "null");
+    return pyramid_backward("roi_align_pyramid_rows_backward", grad, rois, rows, P, K, B, C, H, W, scales, L, PH, PW, sr, k_min, k_max,
+                            canonical_scale, canonical_level, eps, accumulate, grad_feats, stream);
 }
 
 extern "C" int abr_roi_align_forward(const float* feat, const float* rois, int K, int B, int C, int H, int W,

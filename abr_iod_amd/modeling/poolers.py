@@ -40,26 +40,28 @@ class LevelMapper(object):
 
 
 class _PyramidROIAlign(Function):
-    """(rois, geometry, level rule, *maps logical [B,C,H_l,W_l]) -> logical [K,C,ph,pw]; a gradient for every level's map"""
+    """(rois, rows, geometry, level rule, *maps logical [B,C,H_l,W_l]) -> logical [K,C,ph,pw]; a gradient for every level's map.
+    rows: None, or an int64 [P] device list of table rows (entries < 0 are padding) -> logical [P,C,ph,pw], zero at the padding"""
 
     @staticmethod
-    def forward(ctx, rois, output_size, scales, sampling_ratio, rule, *feats):
+    def forward(ctx, rois, rows, output_size, scales, sampling_ratio, rule, *feats):
         xs = [as_nhwc(f) for f in feats]
-        out = ops.roi_align_pyramid_forward(xs, rois, scales, output_size[0], output_size[1], sampling_ratio, *rule)
+        out = ops.roi_align_pyramid_forward(xs, rois, scales, output_size[0], output_size[1], sampling_ratio, *rule, rows=rows)
         # a pooled value is an average of bilinear samples of ONE level's map (or 0): the largest of the levels' amax words bounds the result
         # (f16x3 scales; ops.amax_carry_bound for L maps).  A level without a tag leaves the result untagged: its consumer reduces it.
+        # A subset of the table's rows and zeros for padding keep that bound.
         ops.amax_bound_levels(out, xs)
-        ctx.save_for_backward(rois)
+        ctx.save_for_backward(rois, *(() if rows is None else (rows,)))
         ctx.geom = (tuple(output_size), tuple(scales), sampling_ratio, rule, [tuple(x.shape) for x in xs])
         return from_nhwc(out)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        (rois,) = ctx.saved_tensors
+        rois, *rows = ctx.saved_tensors
         (ph, pw), scales, sr, rule, shapes = ctx.geom
-        gs = ops.roi_align_pyramid_backward(as_nhwc(grad_output), rois, scales, ph, pw, sr, shapes, *rule)
-        return (None, None, None, None, None) + tuple(from_nhwc(g) for g in gs)
+        gs = ops.roi_align_pyramid_backward(as_nhwc(grad_output), rois, scales, ph, pw, sr, shapes, *rule, rows=rows[0] if rows else None)
+        return (None, None, None, None, None, None) + tuple(from_nhwc(g) for g in gs)
 
 
 class Pooler(nn.Module):
@@ -77,17 +79,24 @@ class Pooler(nn.Module):
     def convert_to_roi_format(self, boxes):
         return _roi_table(boxes)
 
-    def forward(self, x, boxes):
-        """boxes: list of BoxLists (poolers.py:80-105) or an [K,5] RoI table (batch index, x1, y1, x2, y2) already on the device"""
+    def forward(self, x, boxes, rows=None):
+        """boxes: list of BoxLists (poolers.py:80-105) or an [K,5] RoI table (batch index, x1, y1, x2, y2) already on the device.
+        rows: an int64 [P] device list of rows of that table -> [P,C,ph,pw]: only those rows are pooled, in one launch and without a gathered
+        copy; an entry < 0 (the padding of ops.mask_compact_pos) gives a zero row and takes no gradient."""
         rois = boxes if torch.is_tensor(boxes) else self.convert_to_roi_format(boxes)
-        if len(self.poolers) == 1:
+        if len(self.poolers) == 1 and rows is None:
             return self.poolers[0](x[0], rois)
         if len(x) != len(self.poolers):
             raise RuntimeError(f"Pooler: {len(x)} feature maps for {len(self.poolers)} scales")
+        return _PyramidROIAlign.apply(rois, rows, *self.geometry(), *x)
+
+    def geometry(self):
+        """(output size, scales, sampling ratio, level rule): what the ops.roi_align_pyramid_* calls take -- for a head that folds the pooler
+        into its own autograd node (roi_heads/mask_head/fpn_mask_head.py)"""
         m = self.map_levels
         output_size = self.output_size if isinstance(self.output_size, (tuple, list)) else (self.output_size, self.output_size)
-        return _PyramidROIAlign.apply(rois, tuple(output_size), tuple(p.spatial_scale for p in self.poolers), self.poolers[0].sampling_ratio,
-                                      (m.k_min, m.k_max, m.s0, m.lvl0, m.eps), *x)
+        return (tuple(output_size), tuple(p.spatial_scale for p in self.poolers), self.poolers[0].sampling_ratio,
+                (m.k_min, m.k_max, m.s0, m.lvl0, m.eps))
 
 
 def make_pooler(cfg, head_name):

@@ -27,6 +27,7 @@ from ....structures.bounding_box import BoxList
 from ....structures.keypoint import PersonKeypoints
 from ...backbone.resnet import Conv2d, _grad_buf
 from ..box_head.box_head import convert_to_roi_format
+from ..conv_stack import conv_stack_backward, conv_stack_forward
 
 
 def check_keypoint_head_cfg(cfg, body_scale=None):
@@ -77,27 +78,17 @@ class _ExtractorFn(Function):
 
     @staticmethod
     def backward(ctx, g):
-        ext, math = ctx.ext, ctx.ext.math
+        ext = ctx.ext
         acts, vs = ctx.saved
-        convs = ext.convs()
-        gz = as_nhwc(g)
-        gz = ops.relu_backward(gz if gz.is_contiguous() else gz.contiguous(), acts[-1])
+        gp = conv_stack_backward(ext.convs(), acts, vs, as_nhwc(g), ext.math, ctx.need_dx)
         gx = None
-        for i in range(len(convs) - 1, -1, -1):
-            c = convs[i]
-            if c.weight.requires_grad:
-                ops.conv_wgrad_async(acts[i], gz, _grad_buf(c.weight), 1, 1, math=math, wino_v=vs[i])
-                ops.bias_grad(gz, _grad_buf(c.bias))
-            if i > 0:
-                gz = ops.conv_forward(gz, c.dgrad_weight(), 1, 1, mask=acts[i], math=math, w_version=c.version())
-            elif ctx.need_dx:
-                gp = ops.conv_forward(gz, c.dgrad_weight(), 1, 1, math=math, w_version=c.version())
-                if ctx.rois is None:
-                    gx = from_nhwc(gp)
-                else:
-                    B, H, W, C_ = ctx.feat_shape
-                    r = ext.resolution
-                    gx = from_nhwc(ops.roi_align_backward(gp, ctx.rois, ext.spatial_scale, r, r, ext.sampling_ratio, B, H, W, C_))
+        if gp is not None:
+            if ctx.rois is None:
+                gx = from_nhwc(gp)
+            else:
+                B, H, W, C_ = ctx.feat_shape
+                r = ext.resolution
+                gx = from_nhwc(ops.roi_align_backward(gp, ctx.rois, ext.spatial_scale, r, r, ext.sampling_ratio, B, H, W, C_))
         ctx.saved = None
         return (gx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
@@ -135,14 +126,7 @@ class KeypointRCNNFeatureExtractor(nn.Module):
         if rois is not None:
             x = ops.roi_align_forward(fh, rois, self.spatial_scale, r, r, self.sampling_ratio)
             ops.amax_carry_bound(x, fh)      # pooled values are averages of bilinear samples: bounded by the feature map's amax (f16x3 scales)
-        acts, vs = [x], []
-        for c in self.convs():
-            v = ops.wino_v_alloc(x, c.weight, 1, 1, self.math) if keep and c.weight.requires_grad else None
-            x = ops.conv_forward(x, c.weight, 1, 1, bias=c.bias, relu=True, math=self.math, wino_v=v, w_version=c.version())
-            if keep:
-                acts.append(x)
-                vs.append(v)
-        return (acts, vs) if keep else x
+        return conv_stack_forward(self.convs(), x, self.math, keep)
 
     def forward(self, features, rois):
         """features: the backbone's list (one level); rois [P,5] (image index, xyxy) -> logical [P,C,r,r].  rois None: features[0] is the

@@ -24,15 +24,48 @@ from ....structures.polygon import PolygonList
 from ...backbone.resnet import Conv2d, _grad_buf
 
 
+FPN_LEVEL_SCALES = (0.25, 0.125, 0.0625, 0.03125)      # P2..P5: the maps a RoI pooler may read (P6 is the RPN's alone)
+
+
 def check_mask_head_cfg(cfg):
-    """NotImplementedError naming the key for everything but the shared C4 head; ValueError when RESOLUTION does not fit the box head's pooler"""
+    """C4 body: NotImplementedError naming the key for everything but the shared C4 head; ValueError when RESOLUTION does not fit the box head's
+    pooler.  FPN body: the unshared MaskRCNNFPNFeatureExtractor + MaskRCNNC4Predictor; every refusal names its key and value."""
+    from ...backbone.resnet import FPN_BODIES
     m, b = cfg.MODEL.ROI_MASK_HEAD, cfg.MODEL.ROI_BOX_HEAD
+    body = cfg.MODEL.BACKBONE.CONV_BODY
 
     def unsupported(key, value, why):
         raise NotImplementedError("MODEL.ROI_MASK_HEAD.{} = {!r}: {}".format(key, value, why))
 
+    if body in FPN_BODIES:
+        if m.FEATURE_EXTRACTOR != "MaskRCNNFPNFeatureExtractor":
+            raise NotImplementedError("MODEL.MASK_ON True on MODEL.BACKBONE.CONV_BODY {!r} with MODEL.ROI_MASK_HEAD.FEATURE_EXTRACTOR = {!r}: an FPN "
+                                      "body runs the mask head on its own pyramid pooler; set MODEL.ROI_MASK_HEAD.FEATURE_EXTRACTOR to "
+                                      "'MaskRCNNFPNFeatureExtractor' (and SHARE_BOX_FEATURE_EXTRACTOR to False)".format(body, m.FEATURE_EXTRACTOR))
+        if m.PREDICTOR != "MaskRCNNC4Predictor":
+            unsupported("PREDICTOR", m.PREDICTOR, "this build runs MaskRCNNC4Predictor only (upstream's FPN configurations name it too)")
+        if m.SHARE_BOX_FEATURE_EXTRACTOR:
+            unsupported("SHARE_BOX_FEATURE_EXTRACTOR", m.SHARE_BOX_FEATURE_EXTRACTOR,
+                        "the FPN box extractor ends in the MLP head's [N, MLP_HEAD_DIM] rows, which no mask predictor can read; set it to False")
+        if m.USE_GN:
+            unsupported("USE_GN", m.USE_GN, "the GroupNorm mask convs are not built")
+        if m.DILATION != 1:
+            unsupported("DILATION", m.DILATION, "dilated mask convs are not built")
+        layers = tuple(m.CONV_LAYERS)
+        if not layers or any(c <= 0 or c % 4 for c in layers):
+            unsupported("CONV_LAYERS", layers, "channel counts must be positive multiples of 4")
+        scales = tuple(m.POOLER_SCALES)
+        if not scales or scales != FPN_LEVEL_SCALES[:len(scales)]:
+            unsupported("POOLER_SCALES", scales, "the mask pooler reads the leading maps of the pyramid, at most the four of P2..P5: a prefix of {!r}"
+                        .format(FPN_LEVEL_SCALES))
+        if m.RESOLUTION != 2 * m.POOLER_RESOLUTION:
+            raise ValueError("MODEL.ROI_MASK_HEAD.RESOLUTION = {} but the predictor's output is {} x {} for MODEL.ROI_MASK_HEAD.POOLER_RESOLUTION = {} "
+                             "(the conv stack keeps the pooled size, the deconvolution doubles it): set RESOLUTION to {}".format(
+                                 m.RESOLUTION, 2 * m.POOLER_RESOLUTION, 2 * m.POOLER_RESOLUTION, m.POOLER_RESOLUTION, 2 * m.POOLER_RESOLUTION))
+        return
     if m.FEATURE_EXTRACTOR != "ResNet50Conv5ROIFeatureExtractor":
-        unsupported("FEATURE_EXTRACTOR", m.FEATURE_EXTRACTOR, "this build runs the C4 mask head (ResNet50Conv5ROIFeatureExtractor) only, no FPN extractor")
+        unsupported("FEATURE_EXTRACTOR", m.FEATURE_EXTRACTOR, "a C4 body runs the C4 mask head (ResNet50Conv5ROIFeatureExtractor) only, no FPN extractor "
+                    "(MaskRCNNFPNFeatureExtractor pools a pyramid: MODEL.BACKBONE.CONV_BODY {!r} has none)".format(body))
     if m.PREDICTOR != "MaskRCNNC4Predictor":
         unsupported("PREDICTOR", m.PREDICTOR, "this build runs MaskRCNNC4Predictor only")
     if m.USE_GN:
@@ -186,7 +219,7 @@ class MaskRCNNLossComputation(object):
 
     def select(self, proposals, targets, fused=None):
         """the positives of the box head's sampled proposals (labels > 0, loss.py:86 / mask_head.py:27-33) and their targets, on the device:
-        -> dict(pos_rows, pos_labels, inv, n_pos, mask_targets [P_max,M,M])"""
+        -> dict(pos_rows, pos_labels, inv, n_pos, mask_targets [P_max,M,M], rois: the sampled set's [R,5] table pos_rows indexes)"""
         if fused is not None:      # ops.roi_head_targets' output: the batch's RoI table and labels are single tensors already
             labels, rois = fused["labels"], fused["rois"]
         else:
@@ -210,7 +243,7 @@ class MaskRCNNLossComputation(object):
             mt = ops.poly_mask_targets(segs, gt_boxes, rois, pos_rows, self.discretization_size)
         else:
             mt = ops.mask_targets([seg.masks for seg in segs], gt_boxes, rois, pos_rows, self.discretization_size)
-        return dict(pos_rows=pos_rows, pos_labels=pos_labels, inv=inv, n_pos=n_pos, mask_targets=mt)
+        return dict(pos_rows=pos_rows, pos_labels=pos_labels, inv=inv, n_pos=n_pos, mask_targets=mt, rois=rois)
 
     def __call__(self, sel, padded_logits, num_classes):
         """padded_logits: MaskRCNNC4Predictor.forward_padded's"""
@@ -246,29 +279,42 @@ class MaskPostProcessor(nn.Module):
 
 
 class ROIMaskHead(nn.Module):
+    """Two modes.  SHARED (the C4 bodies): the extractor is the box head's, training reads the box head's layer4 rows.  UNSHARED (the FPN bodies,
+    SHARE_BOX_FEATURE_EXTRACTOR False): its own MaskRCNNFPNFeatureExtractor (fpn_mask_head.py) on the pyramid, registered here."""
+
     def __init__(self, cfg, in_channels, box_feature_extractor):
         super().__init__()
         check_mask_head_cfg(cfg)
-        # the SHARED extractor is the box head's module; it is not registered a second time (one set of parameters in the flat buffers);
-        # reference_state_dict emits the reference's duplicate roi_heads.mask.feature_extractor.* keys
-        self.__dict__["_feature_extractor"] = box_feature_extractor
-        self.predictor = MaskRCNNC4Predictor(cfg, box_feature_extractor.out_channels)
+        self.unshared = not cfg.MODEL.ROI_MASK_HEAD.SHARE_BOX_FEATURE_EXTRACTOR
+        if self.unshared:
+            from .fpn_mask_head import MaskRCNNFPNFeatureExtractor
+            self.add_module("feature_extractor", MaskRCNNFPNFeatureExtractor(cfg, in_channels))
+        else:
+            # the SHARED extractor is the box head's module; it is not registered a second time (one set of parameters in the flat buffers);
+            # reference_state_dict emits the reference's duplicate roi_heads.mask.feature_extractor.* keys
+            self.__dict__["_feature_extractor"] = box_feature_extractor
+        self.predictor = MaskRCNNC4Predictor(cfg, self.feature_extractor.out_channels)
         self.post_processor = MaskPostProcessor(cfg.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS, cfg.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS_THRESHOLD)
         rh = cfg.MODEL.ROI_HEADS
         self.loss_evaluator = MaskRCNNLossComputation(cfg.MODEL.ROI_MASK_HEAD.RESOLUTION, int(rh.BATCH_SIZE_PER_IMAGE * rh.POSITIVE_FRACTION))
 
     @property
     def feature_extractor(self):
-        return self._feature_extractor
+        own = self._modules.get("feature_extractor")
+        return own if own is not None else self._feature_extractor
 
     def forward(self, features, proposals, targets=None, fused=None):
-        """training: `features` = the box head's layer4 output for `proposals` (its sampled set, with "labels") -> (x, proposals, {loss_mask});
+        """training: `features` = the box head's layer4 output for `proposals` (its sampled set, with "labels") -- unshared: the backbone's
+        maps -> (x, proposals, {loss_mask});
         eval: `features` = the backbone's, `proposals` = the detections -> (x, detections with "mask", {})  (mask_head.py:46-79)"""
         K = self.predictor.num_classes
         if self.training:
             with torch.no_grad():
                 sel = self.loss_evaluator.select(proposals, targets, fused=fused)
-            x = _GatherRowsFn.apply(features, sel["pos_rows"], sel["inv"])
+            if self.unshared:     # the positives are pooled as rows of the sampled set's table: nothing is gathered, nothing read back
+                x = self.feature_extractor(features, sel["rois"], rows=sel["pos_rows"])
+            else:
+                x = _GatherRowsFn.apply(features, sel["pos_rows"], sel["inv"])
             padded = self.predictor.forward_padded(x)
             self.last_selection, self.last_mask_logits = sel, padded[:, :K]       # (introspection for parity tests)
             return x, proposals, dict(loss_mask=self.loss_evaluator(sel, padded, K))
@@ -276,11 +322,18 @@ class ROIMaskHead(nn.Module):
             side = self.loss_evaluator.discretization_size
             empty = features[0].new_zeros((0, side, side, 4)).permute(0, 3, 1, 2)
             return None, self.post_processor(empty, proposals, K), {}
-        x, _ = self.feature_extractor(features, proposals, need_roi_features=False)
+        if self.unshared:
+            x = self.feature_extractor(features, proposals)
+        else:
+            x, _ = self.feature_extractor(features, proposals, need_roi_features=False)
         return x, self.post_processor(self.predictor.forward_padded(x), proposals, K), {}
 
-    def calculate_soften_label(self, features):
-        """mask_head.py:81-86: the predictor on the given head features"""
+    def calculate_soften_label(self, features, proposals=None):
+        """mask_head.py:81-86: the predictor on the given head features.  Unshared: `features` = the backbone's maps and the logits are
+        predictor(extractor(features, proposals)) on the proposals the box soften labels use -- this project's definition (the reference
+        feeds the MLP head's [N,1024] output to the deconvolution and fails there); an empty set gives an empty tensor."""
+        if self.unshared:
+            return self.predictor(self.feature_extractor(features, proposals))
         return self.predictor(features)
 
 

@@ -1,7 +1,15 @@
-"""CombinedROIHeads (mirror of maskrcnn_benchmark/modeling/roi_heads/roi_heads.py:9-77): the box head and, behind it, the C4 mask head under
+"""CombinedROIHeads (mirror of maskrcnn_benchmark/modeling/roi_heads/roi_heads.py:9-77): the box head and, behind it, the mask head under
 MODEL.MASK_ON (mask_head/mask_head.py) and the keypoint head under MODEL.KEYPOINT_ON (keypoint_head/keypoint_head.py; its own extractor on
-the backbone features, SHARE_BOX_FEATURE_EXTRACTOR False).  The keypoint head adds loss_kp in training and a "keypoints" field to the
-detections in eval; it has no distillation term (the reference has none): calculate_soften_label does not see it."""
+the backbone features, SHARE_BOX_FEATURE_EXTRACTOR False).
+
+The mask head has two forms.  On a C4 body it shares the box head's extractor and reads the box head's layer4 rows in training.  On an FPN
+body it is unshared: MaskRCNNFPNFeatureExtractor (mask_head/fpn_mask_head.py) pools the positives of the box head's sampled set on its own
+14 x 14 pooler over P2..P5, as rows of the sampled set's device table, and MaskRCNNC4Predictor follows.  With the unshared head the mask
+logits of calculate_soften_label / forward_joint are predictor(extractor(features, proposals)) on the proposals the box soften labels use
+(this project's definition: the reference hands the MLP head's [N,1024] rows to the deconvolution and fails).
+
+The keypoint head (C4 bodies only) adds loss_kp in training and a "keypoints" field to the detections in eval; it has no distillation term
+(the reference has none): calculate_soften_label does not see it."""
 import torch
 
 from .box_head.box_head import build_roi_box_head
@@ -13,7 +21,7 @@ class CombinedROIHeads(torch.nn.ModuleDict):
     def __init__(self, cfg, heads):
         super().__init__(heads)
         self.cfg = cfg.clone()
-        if "mask" in self:
+        if "mask" in self and not self.mask.unshared:
             self.box.keep_joint_head_features = True
 
     @property
@@ -21,9 +29,10 @@ class CombinedROIHeads(torch.nn.ModuleDict):
         """whether forward_joint can run (an even pooler, e.g. the Mask R-CNN C4 setting 14 -> 7x7, takes the two passes: engine/trainer.py)"""
         return self.box.feature_extractor.joint_supported
 
-    def _mask_train(self, x, detections, targets):
+    def _mask_train(self, features, x, detections, targets):
+        """the shared head reads the box head's output rows `x`, the unshared one pools the backbone's `features` itself"""
         t = getattr(self.box.loss_evaluator, "_fused_targets", None)     # the fused sampler's RoI table and labels, already single device tensors
-        return self.mask(x, detections, targets, fused=t)
+        return self.mask(features if self.mask.unshared else x, detections, targets, fused=t)
 
     def _keypoint_train(self, features, detections, targets):
         t = getattr(self.box.loss_evaluator, "_fused_targets", None)
@@ -43,8 +52,8 @@ class CombinedROIHeads(torch.nn.ModuleDict):
             return x, detections, results_background, []
         x, detections, soft_res, loss_box, roi_align_features = self.box(features, proposals, targets)
         losses.update(loss_box)
-        if mask_on:         # training: the box head's layer4 rows of the positives, no second ROIAlign / layer4 pass
-            _, detections, loss_mask = self._mask_train(x, detections, targets)
+        if mask_on:         # training, shared head: the box head's layer4 rows of the positives, no second ROIAlign / layer4 pass
+            _, detections, loss_mask = self._mask_train(features, x, detections, targets)
             losses.update(loss_mask)
         if "keypoint" in self:     # its own ROIAlign + conv stack on the backbone features, for the sampled positives
             _, detections, loss_kp = self._keypoint_train(features, detections, targets)
@@ -56,10 +65,13 @@ class CombinedROIHeads(torch.nn.ModuleDict):
         (x, detections, soft_res, loss_box, raf), (s_score, s_bbox, s_raf) = self.box.forward_joint(features, proposals, targets, soften_proposals)
         losses, mask_logits = dict(loss_box), None
         if "mask" in self:
-            _, detections, loss_mask = self._mask_train(x, detections, targets)       # x: the detection rows of the joint head pass
+            _, detections, loss_mask = self._mask_train(features, x, detections, targets)       # x: the detection rows of the joint head pass
             losses.update(loss_mask)
-            mask_logits = self.mask.calculate_soften_label(self.box.last_joint_soft_x)
-            self.box.last_joint_soft_x = None
+            if self.mask.unshared:
+                mask_logits = self.mask.calculate_soften_label(features, soften_proposals)
+            else:
+                mask_logits = self.mask.calculate_soften_label(self.box.last_joint_soft_x)
+                self.box.last_joint_soft_x = None
         if "keypoint" in self:
             _, detections, loss_kp = self._keypoint_train(features, detections, targets)
             losses.update(loss_kp)
@@ -68,7 +80,9 @@ class CombinedROIHeads(torch.nn.ModuleDict):
     def calculate_soften_label(self, features, proposals, targets=None):
         """-> (soften_score, soften_bbox, mask_logits (None without a mask head), roi_align_features)  (roi_heads.py:65-72)"""
         soften_score, soften_bbox, x, roi_align_features = self.box.calculate_soften_label(features, proposals, targets)
-        mask_logits = self.mask.calculate_soften_label(x) if "mask" in self else None
+        mask_logits = None
+        if "mask" in self:
+            mask_logits = self.mask.calculate_soften_label(features, proposals) if self.mask.unshared else self.mask.calculate_soften_label(x)
         return soften_score, soften_bbox, mask_logits, roi_align_features
 
 
@@ -76,12 +90,10 @@ def build_roi_heads(cfg, in_channels):
     if cfg.MODEL.RETINANET_ON:
         raise NotImplementedError("only the box, mask and keypoint heads are on the hot path (SURVEY.md §2 row 6b)")
     from ..backbone.resnet import FPN_BODIES
-    if cfg.MODEL.BACKBONE.CONV_BODY in FPN_BODIES:
-        for key in ("MASK_ON", "KEYPOINT_ON"):      # the FPN mask and keypoint heads (their own poolers and conv stacks) are not built
-            if cfg.MODEL[key]:
-                raise NotImplementedError("MODEL.{} True on MODEL.BACKBONE.CONV_BODY {!r}: only the box head (FPN2MLPFeatureExtractor + "
-                                          "FPNPredictor) runs on an FPN body; the mask and keypoint heads are the C4 ones"
-                                          .format(key, cfg.MODEL.BACKBONE.CONV_BODY))
+    if cfg.MODEL.BACKBONE.CONV_BODY in FPN_BODIES and cfg.MODEL.KEYPOINT_ON:      # the FPN keypoint head (its own pooler) is not built
+        raise NotImplementedError("MODEL.KEYPOINT_ON True on MODEL.BACKBONE.CONV_BODY {!r}: only the box head (FPN2MLPFeatureExtractor + "
+                                  "FPNPredictor) and the mask head (MaskRCNNFPNFeatureExtractor) run on an FPN body; the keypoint head is the "
+                                  "C4 one".format(cfg.MODEL.BACKBONE.CONV_BODY))
     if cfg.MODEL.MASK_ON:
         check_mask_head_cfg(cfg)
     if cfg.MODEL.KEYPOINT_ON:

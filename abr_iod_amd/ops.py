@@ -130,37 +130,63 @@ def _pyramid_check(what, feats, name="feats"):
     return f0.shape[0], f0.shape[3]
 
 
+def _pyramid_rows(what, rows, rois):
+    """the device row list of the indexed pyramid calls: int64 [P], contiguous, on the table's device"""
+    if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.dim() != 1:
+        raise RuntimeError(f"{what}: rows must be a one-dimensional int64 tensor")
+    if rows.device != rois.device:
+        raise RuntimeError(f"{what}: rows is on {rows.device}, rois on {rois.device}")
+    return rows.contiguous()
+
+
 def roi_align_pyramid_forward(feats, rois, scales, ph, pw, sampling_ratio, k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6,
-                              out=None, want_levels=False):
+                              out=None, want_levels=False, rows=None):
     """feats: list of contiguous [B,H_l,W_l,C], rois [K,5] -> [K,ph,pw,C] in ONE launch (written into `out` when given): every row pooled on
     the level fpn_levels gives it, all zero for a row without one.  want_levels: -> (out, int32 [K] levels).  The result carries no amax
-    tag: its rows come from maps with different amax words (modeling.poolers.Pooler tags it with their maximum: amax_bound_levels)."""
+    tag: its rows come from maps with different amax words (modeling.poolers.Pooler tags it with their maximum: amax_bound_levels).
+    rows: int64 [P] on the device -> [P,ph,pw,C] (and [P] levels), out[p] = the bits row rows[p] of the table gets without `rows`; an entry
+    < 0 or >= K is padding: all zero, level -1, its table row never read."""
+    what = "roi_align_pyramid_forward"
     feats = list(feats)
-    B, Ch = _pyramid_check("roi_align_pyramid_forward", feats)
+    B, Ch = _pyramid_check(what, feats)
     L.require_cuda(rois)
     rois = L.f32c(rois)
     K = rois.shape[0]
+    if rows is not None:
+        rows = _pyramid_rows(what, rows, rois)
+    N = K if rows is None else rows.shape[0]
     if out is None:
-        out = _empty((K, ph, pw, Ch), rois)
+        out = _empty((N, ph, pw, Ch), rois)
     else:
-        assert tuple(out.shape) == (K, ph, pw, Ch) and out.is_contiguous() and out.dtype == _f32
-    levels = torch.empty((K,), dtype=torch.int32, device=rois.device) if want_levels else None
-    fp, Hs, Ws, sc = _pyramid_tables("roi_align_pyramid_forward", feats, [f.shape for f in feats], scales)
-    L.check(L.lib().abr_roi_align_pyramid_forward(fp, Hs, Ws, sc, len(feats), L.ptr(rois), K, B, Ch, ph, pw, sampling_ratio, float(k_min), float(k_max),
-                                                  float(canonical_scale), float(canonical_level), float(eps), L.ptr(out), L.ptr(levels), L.stream()),
-            "roi_align_pyramid_forward")
+        assert tuple(out.shape) == (N, ph, pw, Ch) and out.is_contiguous() and out.dtype == _f32
+    levels = torch.empty((N,), dtype=torch.int32, device=rois.device) if want_levels else None
+    fp, Hs, Ws, sc = _pyramid_tables(what, feats, [f.shape for f in feats], scales)
+    rule = (float(k_min), float(k_max), float(canonical_scale), float(canonical_level), float(eps))
+    if rows is None:
+        rc = L.lib().abr_roi_align_pyramid_forward(fp, Hs, Ws, sc, len(feats), L.ptr(rois), K, B, Ch, ph, pw, sampling_ratio, *rule, L.ptr(out),
+                                                   L.ptr(levels), L.stream())
+    else:
+        rc = L.lib().abr_roi_align_pyramid_rows_forward(fp, Hs, Ws, sc, len(feats), L.ptr(rois), K, L.ptr(rows), N, B, Ch, ph, pw, sampling_ratio,
+                                                        *rule, L.ptr(out), L.ptr(levels), L.stream())
+    L.check(rc, what)
     amax_drop(out)
     return (out, levels) if want_levels else out
 
 
 def roi_align_pyramid_backward(grad, rois, scales, ph, pw, sampling_ratio, shapes, k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6,
-                               out=None):
+                               out=None, rows=None):
     """grad [K,ph,pw,C], shapes: the [B,H_l,W_l,C] of every level -> list of grad_feat [B,H_l,W_l,C]: one launch over the RoIs adds into
     float64 scratch with hardware atomics (their order varies from run to run), a second rounds every level's sums to fp32 once; every level is
-    written whole, reached or not, unless the list `out` is given: then it accumulates"""
+    written whole, reached or not, unless the list `out` is given: then it accumulates.
+    rows: int64 [P] on the device, grad [P,ph,pw,C]: grad[p] belongs to row rows[p] of the table; a padding entry (< 0 or >= K) adds nothing
+    and its grad row is not read."""
+    what = "roi_align_pyramid_backward"
     L.require_cuda(grad, rois)
     grad, rois = L.f32c(grad), L.f32c(rois)
     K = rois.shape[0]
+    if rows is not None:
+        rows = _pyramid_rows(what, rows, rois)
+    N = K if rows is None else rows.shape[0]
     shapes = [tuple(int(v) for v in s) for s in shapes]
     acc = out is not None
     if out is None:
@@ -168,14 +194,19 @@ def roi_align_pyramid_backward(grad, rois, scales, ph, pw, sampling_ratio, shape
     else:
         out = list(out)
         if [tuple(o.shape) for o in out] != shapes:
-            raise RuntimeError(f"roi_align_pyramid_backward: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
-    B, Ch = _pyramid_check("roi_align_pyramid_backward", out, "out")
-    if tuple(grad.shape) != (K, ph, pw, Ch):
-        raise RuntimeError(f"roi_align_pyramid_backward: grad {tuple(grad.shape)} is not [{K}, {ph}, {pw}, {Ch}]")
-    gp, Hs, Ws, sc = _pyramid_tables("roi_align_pyramid_backward", out, shapes, scales)
-    L.check(L.lib().abr_roi_align_pyramid_backward(L.ptr(grad), L.ptr(rois), K, B, Ch, Hs, Ws, sc, len(out), ph, pw, sampling_ratio, float(k_min),
-                                                   float(k_max), float(canonical_scale), float(canonical_level), float(eps), int(acc), gp, L.stream()),
-            "roi_align_pyramid_backward")
+            raise RuntimeError(f"{what}: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
+    B, Ch = _pyramid_check(what, out, "out")
+    if tuple(grad.shape) != (N, ph, pw, Ch):
+        raise RuntimeError(f"{what}: grad {tuple(grad.shape)} is not [{N}, {ph}, {pw}, {Ch}]")
+    gp, Hs, Ws, sc = _pyramid_tables(what, out, shapes, scales)
+    rule = (float(k_min), float(k_max), float(canonical_scale), float(canonical_level), float(eps))
+    if rows is None:
+        rc = L.lib().abr_roi_align_pyramid_backward(L.ptr(grad), L.ptr(rois), K, B, Ch, Hs, Ws, sc, len(out), ph, pw, sampling_ratio, *rule, int(acc),
+                                                    gp, L.stream())
+    else:
+        rc = L.lib().abr_roi_align_pyramid_rows_backward(L.ptr(grad), L.ptr(rois), L.ptr(rows), N, K, B, Ch, Hs, Ws, sc, len(out), ph, pw,
+                                                         sampling_ratio, *rule, int(acc), gp, L.stream())
+    L.check(rc, what)
     for o in out:
         amax_drop(o)
     return out

@@ -30,8 +30,9 @@ def reference_state_dict(model):
             out[head + "cell_anchors." + level] = b.detach().clone()
             continue
         out[name] = b.detach().clone()
-    if "mask" in getattr(model, "roi_heads", {}):
-        # the reference registers the SHARED feature extractor under the mask head too (roi_heads.py:18-21): its state_dict repeats every key
+    if "mask" in getattr(model, "roi_heads", {}) and not model.roi_heads.mask.unshared:
+        # the reference registers the SHARED feature extractor under the mask head too (roi_heads.py:18-21): its state_dict repeats every key.
+        # The unshared head (MaskRCNNFPNFeatureExtractor) has its own roi_heads.mask.feature_extractor.mask_fcn* parameters, emitted above.
         box, mask = "roi_heads.box.feature_extractor.", "roi_heads.mask.feature_extractor."
         for k in [k for k in out if k.startswith(box)]:
             out[mask + k[len(box):]] = out[k]

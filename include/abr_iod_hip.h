@@ -171,6 +171,20 @@ int abr_roi_align_pyramid_backward(const float* grad, const float* rois, int K, 
                                    float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
                                    int accumulate, float* const* grad_feats_host, void* stream);
 
+/* The indexed forms: pool (scatter) only the rows of the table that a device list names, one launch each way, no gathered copy of the table.
+ * rois [K,5]; rows [P] int64 on the device; out / grad [P,PH,PW,C]; levels_out [P] int32 or NULL.  out[p] has exactly the bits
+ * abr_roi_align_pyramid_forward gives row rows[p]; an entry < 0 or >= K is padding: its table row is never read, out[p] is all zero and its
+ * level -1; the backward adds nothing for it and does not read grad[p] (which may hold NaN).  The grid is over P; P * PH * PW * C must fit
+ * int32.  Scratch, rounding and `accumulate` as in abr_roi_align_pyramid_backward; P == 0 behaves as K == 0 does there (rows may be NULL). */
+int abr_roi_align_pyramid_rows_forward(const float* const* feats_host, const int* H_host, const int* W_host, const float* scales_host, int L,
+                                       const float* rois, int K, const int64_t* rows, int P, int B, int C, int PH, int PW, int sampling_ratio,
+                                       float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
+                                       float* out, int32_t* levels_out, void* stream);
+int abr_roi_align_pyramid_rows_backward(const float* grad, const float* rois, const int64_t* rows, int P, int K, int B, int C, const int* H_host,
+                                        const int* W_host, const float* scales_host, int L, int PH, int PW, int sampling_ratio,
+                                        float k_min, float k_max, float canonical_scale, float canonical_level, float eps,
+                                        int accumulate, float* const* grad_feats_host, void* stream);
+
 /* The top-down pathway of a feature pyramid network (modeling/backbone/fpn.py:47-70) and LastLevelMaxPool (:90-92), csrc/fpn.hip.
  * All maps are NHWC fp32, contiguous, 16-byte aligned, C % 4 == 0; level 0 is the finest, H[l] == 2 H[l+1] and W[l] == 2 W[l+1];
  * 1 <= L <= ABR_MAX_PYRAMID_LEVELS; B * H[0] * W[0] * C / 4 must fit int32.  The *_host arguments are HOST arrays of L entries copied into the

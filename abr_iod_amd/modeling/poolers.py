@@ -92,7 +92,7 @@ class Pooler(nn.Module):
 
     def geometry(self):
         """(output size, scales, sampling ratio, level rule): what the ops.roi_align_pyramid_* calls take -- for a head that folds the pooler
-        into its own autograd node (roi_heads/mask_head/fpn_mask_head.py)"""
+        into its own autograd node (roi_heads/pyramid_extractor.py)"""
         m = self.map_levels
         output_size = self.output_size if isinstance(self.output_size, (tuple, list)) else (self.output_size, self.output_size)
         return (tuple(output_size), tuple(p.spatial_scale for p in self.poolers), self.poolers[0].sampling_ratio,

@@ -1,4 +1,4 @@
-"""RoI keypoint head on the HIP library (MODEL.KEYPOINT_ON on the C4 bodies, SHARE_BOX_FEATURE_EXTRACTOR False).
+"""RoI keypoint head on the HIP library (MODEL.KEYPOINT_ON on the C4 and the FPN bodies, SHARE_BOX_FEATURE_EXTRACTOR False).
 
 Mirrors:
     ROIKeypointHead                  maskrcnn_benchmark/modeling/roi_heads/keypoint_head/keypoint_head.py
@@ -16,6 +16,13 @@ MI355X-first differences:
   * ConvTranspose2d(C, K, 4, 2, 1) is a GEMM with 16 * Kp output columns on the conv planner plus a fold pass into PLANAR maps [P,Kp,2h,2w].
   * training never materialises the upsampled logits: ops.kp_loss upsamples on the fly and returns the gradient of the low-resolution maps.
   * heatmaps_to_keypoints runs on the device (ops.kp_decode), for any number of images (the reference asserts one).
+
+On an FPN body (upstream's only published keypoint setting: four POOLER_SCALES, pooler 14, sampling ratio 2, RESOLUTION 56) the extractor is
+its pyramid form, roi_heads/pyramid_extractor.py's pooler + conv stack node, the one the FPN mask head runs.  Training pools
+rows = pos_rows of the table the sampled set already is on the device (the fused sampler's, or the concatenated BoxLists'): no gathered RoI
+table is built.  A padding row is ZERO features in and relu(bias) features out (the C4 form pools a degenerate RoI instead); it never reads
+the table, has valid = 0, and so adds no loss and exactly zero gradient to weights, biases and maps.  Eval pools the detections of all
+images through the same extractor, without rows.
 """
 import torch
 from torch import nn
@@ -28,12 +35,20 @@ from ....structures.keypoint import PersonKeypoints
 from ...backbone.resnet import Conv2d, _grad_buf
 from ..box_head.box_head import convert_to_roi_format
 from ..conv_stack import conv_stack_backward, conv_stack_forward
+from ..pyramid_extractor import PyramidConvExtractor, make_conv3x3_stack
+
+
+def _on_pyramid(cfg):
+    from ...backbone.resnet import FPN_BODIES
+    return cfg.MODEL.BACKBONE.CONV_BODY in FPN_BODIES
 
 
 def check_keypoint_head_cfg(cfg, body_scale=None):
-    """NotImplementedError naming the key for everything but the C4 keypoint head with its own extractor; ValueError when RESOLUTION is not
-    four times the pooler's"""
+    """C4 body: NotImplementedError naming the key for everything but the keypoint head with its own extractor on the body's one scale.
+    FPN body: the same extractor and predictor on its own pyramid pooler, POOLER_SCALES a leading run of P2..P5's; every refusal names its key
+    and value.  Both: ValueError when RESOLUTION is not four times the pooler's"""
     k = cfg.MODEL.ROI_KEYPOINT_HEAD
+    body, pyramid = cfg.MODEL.BACKBONE.CONV_BODY, _on_pyramid(cfg)
 
     def unsupported(key, value, why):
         raise NotImplementedError("MODEL.ROI_KEYPOINT_HEAD.{} = {!r}: {}".format(key, value, why))
@@ -42,13 +57,26 @@ def check_keypoint_head_cfg(cfg, body_scale=None):
         unsupported("FEATURE_EXTRACTOR", k.FEATURE_EXTRACTOR, "this build runs KeypointRCNNFeatureExtractor only")
     if k.PREDICTOR != "KeypointRCNNPredictor":
         unsupported("PREDICTOR", k.PREDICTOR, "this build runs KeypointRCNNPredictor only")
-    if k.SHARE_BOX_FEATURE_EXTRACTOR:
+    if pyramid:
+        from ..mask_head.mask_head import FPN_LEVEL_SCALES
+        scales = tuple(k.POOLER_SCALES)
+        if k.SHARE_BOX_FEATURE_EXTRACTOR:
+            raise NotImplementedError("MODEL.KEYPOINT_ON True on MODEL.BACKBONE.CONV_BODY {!r} with MODEL.ROI_KEYPOINT_HEAD.SHARE_BOX_FEATURE_EXTRACTOR = "
+                                      "{!r}: the FPN box extractor ends in the MLP head's [N, MLP_HEAD_DIM] rows, which no keypoint predictor can read; "
+                                      "an FPN body runs the keypoint head on its own pyramid pooler: set SHARE_BOX_FEATURE_EXTRACTOR to False and "
+                                      "MODEL.ROI_KEYPOINT_HEAD.POOLER_SCALES to the body's {!r} (upstream's keypoint configs do)".format(
+                                          body, k.SHARE_BOX_FEATURE_EXTRACTOR, FPN_LEVEL_SCALES))
+        if not scales or scales != FPN_LEVEL_SCALES[:len(scales)]:
+            raise NotImplementedError("MODEL.KEYPOINT_ON True on MODEL.BACKBONE.CONV_BODY {!r} with MODEL.ROI_KEYPOINT_HEAD.POOLER_SCALES = {!r}: the "
+                                      "keypoint pooler reads the leading maps of the pyramid, at most the four of P2..P5: set POOLER_SCALES to a "
+                                      "prefix of {!r}".format(body, scales, FPN_LEVEL_SCALES))
+    elif k.SHARE_BOX_FEATURE_EXTRACTOR:
         unsupported("SHARE_BOX_FEATURE_EXTRACTOR", k.SHARE_BOX_FEATURE_EXTRACTOR,
                     "on a C4 body the box extractor's output is layer4's [N,2048,7,7], which the reference then pools as if it were a feature-map "
                     "list, for a predictor built for CONV_LAYERS[-1] channels: it cannot run; set it to False (upstream's keypoint configs do)")
     scales = tuple(k.POOLER_SCALES)
     want = tuple(cfg.MODEL.ROI_BOX_HEAD.POOLER_SCALES) if body_scale is None else (body_scale,)
-    if len(scales) != 1 or scales != want:
+    if not pyramid and (len(scales) != 1 or scales != want):
         unsupported("POOLER_SCALES", scales, "one pooler scale, the C4 body's {!r}, is run (no FPN level mapping)".format(want))
     layers = tuple(k.CONV_LAYERS)
     if not layers or any(c <= 0 or c % 4 for c in layers):
@@ -93,31 +121,25 @@ class _ExtractorFn(Function):
         return (gx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
-class KeypointRCNNFeatureExtractor(nn.Module):
+class KeypointRCNNFeatureExtractor(PyramidConvExtractor):
+    """roi_keypoint_feature_extractors.py:11-43: one class, one set of names (conv_fcn1..n) on both kinds of body, as upstream, so a reference
+    checkpoint loads key for key.  On an FPN body (`pyramid`) it IS roi_heads/pyramid_extractor.py's node over its own multi-scale pooler:
+    forward(maps, proposals or a [K,5] table, rows=None).  On a C4 body it is the single-scale form below: forward([feature map], rois)."""
+
     def __init__(self, cfg, in_channels):
-        super().__init__()
         k = cfg.MODEL.ROI_KEYPOINT_HEAD
         if in_channels % 4:
             raise NotImplementedError("the keypoint head's input has {} channels: channel counts must be multiples of 4".format(in_channels))
+        if _on_pyramid(cfg):
+            super().__init__(cfg, in_channels, "ROI_KEYPOINT_HEAD", "conv_fcn")
+            self.pyramid = True
+            return
+        nn.Module.__init__(self)
+        self.pyramid = False
         self.resolution, self.spatial_scale, self.sampling_ratio = k.POOLER_RESOLUTION, tuple(k.POOLER_SCALES)[0], k.POOLER_SAMPLING_RATIO
         self.math = ops.MATH_F32     # see backbone.resnet.set_conv_math
-        self.blocks, c = [], in_channels
-        for i, width in enumerate(k.CONV_LAYERS, 1):
-            name = "conv_fcn{}".format(i)
-            conv = Conv2d(c, width, 3, stride=1, padding=1)
-            with torch.no_grad():     # kaiming_normal_(mode="fan_out", nonlinearity="relu"), bias 0 (roi_keypoint_feature_extractors.py:31-32)
-                conv.weight.normal_(0.0, (2.0 / (9 * width)) ** 0.5)
-            self.add_module(name, conv)
-            self.blocks.append(name)
-            c = width
-        self.out_channels = c
-
-    def convs(self):
-        return [getattr(self, n) for n in self.blocks]
-
-    def prep_entries(self):
-        """FusedSGD's batched weight preparation (see Bottleneck.prep_entries)"""
-        return [(c, None, 1, 1, self.math) for c in self.convs() if c.weight.requires_grad and c.weight.is_cuda]
+        # kaiming_normal_(mode="fan_out", nonlinearity="relu"), bias 0 (roi_keypoint_feature_extractors.py:31-32)
+        self.blocks, self.out_channels = make_conv3x3_stack(self, in_channels, k.CONV_LAYERS, "conv_fcn")
 
     def _run(self, fh, rois, keep=False):
         """fh NHWC features, rois [P,5] (None: fh is the pooled tensor already) -> the activations [pooled, conv_fcn1's, ...] (keep) or just
@@ -128,9 +150,14 @@ class KeypointRCNNFeatureExtractor(nn.Module):
             ops.amax_carry_bound(x, fh)      # pooled values are averages of bilinear samples: bounded by the feature map's amax (f16x3 scales)
         return conv_stack_forward(self.convs(), x, self.math, keep)
 
-    def forward(self, features, rois):
-        """features: the backbone's list (one level); rois [P,5] (image index, xyxy) -> logical [P,C,r,r].  rois None: features[0] is the
-        pooled tensor [P,C,r,r] itself (the conv stack alone, for parity tests)"""
+    def forward(self, features, rois, rows=None):
+        """C4 form -- features: the backbone's list (one level); rois [P,5] (image index, xyxy) -> logical [P,C,r,r].  rois None: features[0]
+        is the pooled tensor [P,C,r,r] itself (the conv stack alone, for parity tests).
+        Pyramid form -- PyramidConvExtractor.forward(maps, proposals or a [K,5] table, rows)"""
+        if self.pyramid:
+            return super().forward(features, rois, rows)
+        if rows is not None:
+            raise RuntimeError("KeypointRCNNFeatureExtractor: rows index a RoI table for the pyramid pooler; the single-scale form takes the RoIs themselves")
         feat = features[0]
         if rois is not None and rois.shape[0] == 0:
             return feat.new_zeros((0, self.resolution, self.resolution, self.out_channels)).permute(0, 3, 1, 2)
@@ -232,9 +259,10 @@ class KeypointRCNNLossComputation(object):
     def __init__(self, discretization_size, max_pos_per_image):
         self.discretization_size, self.max_pos_per_image = discretization_size, max_pos_per_image
 
-    def select(self, proposals, targets, fused=None):
+    def select(self, proposals, targets, fused=None, gather=True):
         """the box head's sampled positives whose matched instance has a visible keypoint inside its box (loss.py:79-143) and their heat-map
-        targets (loss.py:145-157), on the device: ops.kp_select_targets' dict + rois [P_max,5], the kept rows' RoIs"""
+        targets (loss.py:145-157), on the device: ops.kp_select_targets' dict + table [R,5], the sampled set's RoI table pos_rows indexes, and,
+        with `gather` (the single-scale pooler), rois [P_max,5], the kept rows' RoIs"""
         if fused is not None:      # ops.roi_head_targets' output: the batch's RoI table and labels are single tensors already
             labels, rois = fused["labels"], fused["rois"]
         else:
@@ -249,9 +277,11 @@ class KeypointRCNNLossComputation(object):
             kps.append(kp.keypoints)
         p_max = max(1, min(labels.numel(), self.max_pos_per_image * len(proposals)))
         sel = ops.kp_select_targets(rois, labels, [t.convert("xyxy").bbox for t in targets], kps, self.discretization_size, p_max)
-        wide = torch.zeros((rois.shape[0], 8), dtype=rois.dtype, device=rois.device)      # (row gather moves 16-byte pieces)
-        wide[:, :5] = rois
-        sel["rois"] = ops.mask_gather_rows(wide, sel["pos_rows"])[:, :5].contiguous()
+        sel["table"] = rois
+        if gather:
+            wide = torch.zeros((rois.shape[0], 8), dtype=rois.dtype, device=rois.device)      # (row gather moves 16-byte pieces)
+            wide[:, :5] = rois
+            sel["rois"] = ops.mask_gather_rows(wide, sel["pos_rows"])[:, :5].contiguous()
         return sel
 
 
@@ -301,15 +331,22 @@ class ROIKeypointHead(nn.Module):
     def forward(self, features, proposals, targets=None, fused=None):
         """training: `features` = the backbone's, `proposals` = the box head's sampled set (with "labels") -> (x, proposals, {loss_kp});
         eval: `proposals` = the detections -> (x, detections with "keypoints", {})  (keypoint_head.py:20-49)"""
+        pyramid = self.feature_extractor.pyramid
         if self.training:
             with torch.no_grad():
-                sel = self.loss_evaluator.select(proposals, targets, fused=fused)
-            x = self.feature_extractor(features, sel["rois"])
+                sel = self.loss_evaluator.select(proposals, targets, fused=fused, gather=not pyramid)
+            if pyramid:      # the kept positives are pooled as rows of the sampled set's table: nothing is gathered, nothing read back
+                x = self.feature_extractor(features, sel["table"], rows=sel["pos_rows"])
+            else:
+                x = self.feature_extractor(features, sel["rois"])
             self.last_selection = sel
             return x, proposals, dict(loss_kp=self.predictor.loss(x, sel))
         K, side = self.predictor.num_keypoints, self.loss_evaluator.discretization_size
         if sum(len(p) for p in proposals) == 0:
             return None, self.post_processor(features[0].new_zeros((0, K, side, side)), proposals), {}
+        if pyramid:
+            x = self.feature_extractor(features, proposals)
+            return x, self.post_processor(self.predictor(x), proposals), {}
         x = self.feature_extractor(features, convert_to_roi_format([p.convert("xyxy") for p in proposals]))
         return x, self.post_processor(self.predictor(x), proposals), {}
 

@@ -11,101 +11,18 @@ MI355X-first differences (results identical):
   * training pools only the positives of the box head's sampled set, and it pools them as ROWS of the table that set already is on the device
     (ops.roi_align_pyramid_forward(rows=): the -1-padded list of ops.mask_compact_pos indexes the fused sampler's RoI table): no gathered
     copy of the table, no degenerate box for the padding -- a padding row is zero, never reads the table and takes no gradient.
-  * pooler and conv stack are ONE autograd node; the stack is the loop the keypoint head runs (roi_heads/conv_stack.py); its backward ends in
-    the indexed pyramid backward, which hands every level's map its gradient.
+  * pooler and conv stack are ONE autograd node, the one the FPN keypoint head runs too (roi_heads/pyramid_extractor.py); its backward ends
+    in the indexed pyramid backward, which hands every level's map its gradient.
 """
-import torch
-from torch import nn
-from torch.autograd import Function
-from torch.autograd.function import once_differentiable
-
-from .... import ops
-from ....layers._layout import as_nhwc, from_nhwc
-from ...backbone.resnet import Conv2d
-from ...poolers import make_pooler
-from ..conv_stack import conv_stack_backward, conv_stack_forward
+from ..pyramid_extractor import PyramidConvExtractor
 
 
-class _FPNExtractorFn(Function):
-    """(extractor, rois [K,5], rows int64 [P] or None, n_maps, *maps logical [B,C,H_l,W_l], *parameters) -> logical [P or K, width, r, r]"""
-
-    @staticmethod
-    def forward(ctx, ext, rois, rows, n_maps, *args):
-        xs = [as_nhwc(f) for f in args[:n_maps]]
-        acts, vs = conv_stack_forward(ext.convs(), ext._pool(xs, rois, rows), ext.math, keep=True)
-        ctx.ext, ctx.saved, ctx.table, ctx.n_maps = ext, (acts, vs), (rois, rows), n_maps
-        ctx.shapes = [tuple(x.shape) for x in xs]
-        return from_nhwc(acts[-1])
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        ext = ctx.ext
-        acts, vs = ctx.saved
-        ctx.saved = None
-        need_dx = any(ctx.needs_input_grad[4:4 + ctx.n_maps])
-        gp = conv_stack_backward(ext.convs(), acts, vs, as_nhwc(g), ext.math, need_dx)
-        gmaps = (None,) * ctx.n_maps
-        if gp is not None:
-            rois, rows = ctx.table
-            (ph, pw), scales, sr, rule = ext.pooler.geometry()
-            gmaps = tuple(from_nhwc(t) for t in ops.roi_align_pyramid_backward(gp, rois, scales, ph, pw, sr, ctx.shapes, *rule, rows=rows))
-        return (None, None, None, None) + gmaps + (None,) * (len(ctx.needs_input_grad) - 4 - ctx.n_maps)
-
-
-class MaskRCNNFPNFeatureExtractor(nn.Module):
+class MaskRCNNFPNFeatureExtractor(PyramidConvExtractor):
     """roi_mask_feature_extractors.py:16-65.  forward -> logical [P,CONV_LAYERS[-1],r,r]"""
 
     def __init__(self, cfg, in_channels):
-        super().__init__()
         m = cfg.MODEL.ROI_MASK_HEAD
         if m.USE_GN or m.DILATION != 1:
             raise NotImplementedError("MODEL.ROI_MASK_HEAD.USE_GN {!r} / DILATION {!r}: the GroupNorm and dilated mask convs are not built".format(
                 m.USE_GN, m.DILATION))
-        if in_channels % 4:
-            raise NotImplementedError("MaskRCNNFPNFeatureExtractor: {} input channels, need a multiple of 4".format(in_channels))
-        self.pooler = make_pooler(cfg, "ROI_MASK_HEAD")
-        self.n_levels = len(m.POOLER_SCALES)
-        self.resolution, self.in_channels = m.POOLER_RESOLUTION, in_channels
-        self.math = ops.MATH_F32     # see backbone.resnet.set_conv_math
-        self.blocks, c = [], in_channels
-        for i, width in enumerate(m.CONV_LAYERS, 1):
-            name = "mask_fcn{}".format(i)
-            conv = Conv2d(c, width, 3, stride=1, padding=1)
-            with torch.no_grad():     # make_conv3x3: kaiming_normal_(mode="fan_out", nonlinearity="relu"), bias 0
-                conv.weight.normal_(0.0, (2.0 / (9 * width)) ** 0.5)
-            self.add_module(name, conv)
-            self.blocks.append(name)
-            c = width
-        self.out_channels = c
-
-    def convs(self):
-        return [getattr(self, n) for n in self.blocks]
-
-    def prep_entries(self):
-        """FusedSGD's batched weight preparation (see Bottleneck.prep_entries)"""
-        return [(c, None, 1, 1, self.math) for c in self.convs() if c.weight.requires_grad and c.weight.is_cuda]
-
-    def _pool(self, xs, rois, rows):
-        """NHWC maps -> NHWC [P or K, r, r, C], tagged with the levels' amax bound (a subset of the table's rows and zeros keep it)"""
-        (ph, pw), scales, sr, rule = self.pooler.geometry()
-        out = ops.roi_align_pyramid_forward(xs, rois, scales, ph, pw, sr, *rule, rows=rows)
-        return ops.amax_bound_levels(out, xs)
-
-    def forward(self, x, proposals, rows=None):
-        """x: the pyramid's maps, logical [B,C,H_l,W_l] -- the first len(POOLER_SCALES) are pooled (P6 is the RPN's alone: the reference's
-        zip drops it); proposals: list of BoxLists or a ready [K,5] RoI table; rows: int64 [P] device list of rows of that table (entries < 0
-        are padding: zero features in, relu(bias) features out, no gradient to the maps)"""
-        x = list(x)
-        if len(x) < self.n_levels:
-            raise RuntimeError("MaskRCNNFPNFeatureExtractor: {} feature maps for {} MODEL.ROI_MASK_HEAD.POOLER_SCALES".format(len(x), self.n_levels))
-        x = x[: self.n_levels]
-        rois = proposals if torch.is_tensor(proposals) else self.pooler.convert_to_roi_format(proposals)
-        n = rois.shape[0] if rows is None else rows.shape[0]
-        r = self.resolution
-        if n == 0:
-            return rois.new_zeros((0, r, r, self.out_channels)).permute(0, 3, 1, 2)
-        params = list(self.parameters())
-        if torch.is_grad_enabled() and (any(f.requires_grad for f in x) or any(p.requires_grad for p in params)):
-            return _FPNExtractorFn.apply(self, rois, rows, len(x), *x, *params)
-        return from_nhwc(conv_stack_forward(self.convs(), self._pool([as_nhwc(f) for f in x], rois, rows), self.math))
+        super().__init__(cfg, in_channels, "ROI_MASK_HEAD", "mask_fcn")

@@ -8,8 +8,11 @@ body it is unshared: MaskRCNNFPNFeatureExtractor (mask_head/fpn_mask_head.py) po
 logits of calculate_soften_label / forward_joint are predictor(extractor(features, proposals)) on the proposals the box soften labels use
 (this project's definition: the reference hands the MLP head's [N,1024] rows to the deconvolution and fails).
 
-The keypoint head (C4 bodies only) adds loss_kp in training and a "keypoints" field to the detections in eval; it has no distillation term
-(the reference has none): calculate_soften_label does not see it."""
+The keypoint head runs on both kinds of body, always unshared: on a C4 body KeypointRCNNFeatureExtractor pools the body's one map, on an FPN
+body it pools P2..P5 on its own pooler (roi_heads/pyramid_extractor.py, the node the FPN mask head runs), again as rows of the sampled set's
+device table.  Mask and keypoint heads may run together; the mask head goes first (roi_heads.py:33-62).  The keypoint head adds loss_kp in
+training and a "keypoints" field to the detections in eval; it has no distillation term (the reference has none): calculate_soften_label
+does not see it."""
 import torch
 
 from .box_head.box_head import build_roi_box_head
@@ -89,11 +92,6 @@ class CombinedROIHeads(torch.nn.ModuleDict):
 def build_roi_heads(cfg, in_channels):
     if cfg.MODEL.RETINANET_ON:
         raise NotImplementedError("only the box, mask and keypoint heads are on the hot path (SURVEY.md §2 row 6b)")
-    from ..backbone.resnet import FPN_BODIES
-    if cfg.MODEL.BACKBONE.CONV_BODY in FPN_BODIES and cfg.MODEL.KEYPOINT_ON:      # the FPN keypoint head (its own pooler) is not built
-        raise NotImplementedError("MODEL.KEYPOINT_ON True on MODEL.BACKBONE.CONV_BODY {!r}: only the box head (FPN2MLPFeatureExtractor + "
-                                  "FPNPredictor) and the mask head (MaskRCNNFPNFeatureExtractor) run on an FPN body; the keypoint head is the "
-                                  "C4 one".format(cfg.MODEL.BACKBONE.CONV_BODY))
     if cfg.MODEL.MASK_ON:
         check_mask_head_cfg(cfg)
     if cfg.MODEL.KEYPOINT_ON:

@@ -208,6 +208,33 @@ _C.MODEL.ROI_KEYPOINT_HEAD.RESOLUTION = 14
 _C.MODEL.ROI_KEYPOINT_HEAD.NUM_CLASSES = 17
 _C.MODEL.ROI_KEYPOINT_HEAD.SHARE_BOX_FEATURE_EXTRACTOR = True
 
+# RetinaNet (defaults.py:325-380).  Honoured in eval: the anchors, USE_C5, NUM_CONVS, PRIOR_PROB, PRE_NMS_TOP_N, INFERENCE_TH, NMS_TH; the loss keys
+# (BBOX_REG_*, FG / BG_IOU_THRESHOLD, LOSS_*) wait for the RetinaNet loss: a RetinaNet model in training mode raises
+_C.MODEL.RETINANET = CN()
+_C.MODEL.RETINANET.NUM_CLASSES = 81            # foreground classes and background
+_C.MODEL.RETINANET.ANCHOR_SIZES = (32, 64, 128, 256, 512)
+_C.MODEL.RETINANET.ASPECT_RATIOS = (0.5, 1.0, 2.0)
+_C.MODEL.RETINANET.ANCHOR_STRIDES = (8, 16, 32, 64, 128)
+_C.MODEL.RETINANET.STRADDLE_THRESH = 0
+_C.MODEL.RETINANET.OCTAVE = 2.0
+_C.MODEL.RETINANET.SCALES_PER_OCTAVE = 3
+_C.MODEL.RETINANET.USE_C5 = True               # P6 from C5 (else from P5)
+_C.MODEL.RETINANET.NUM_CONVS = 4               # convs of the cls and bbox towers, the output convs not counted
+_C.MODEL.RETINANET.BBOX_REG_WEIGHT = 4.0
+_C.MODEL.RETINANET.BBOX_REG_BETA = 0.11
+_C.MODEL.RETINANET.PRE_NMS_TOP_N = 1000        # per level, at most ops.rpn_pyramid_max_k() and ops.retina_max_candidates() / levels
+_C.MODEL.RETINANET.FG_IOU_THRESHOLD = 0.5
+_C.MODEL.RETINANET.BG_IOU_THRESHOLD = 0.4
+_C.MODEL.RETINANET.LOSS_ALPHA = 0.25
+_C.MODEL.RETINANET.LOSS_GAMMA = 2.0
+_C.MODEL.RETINANET.PRIOR_PROB = 0.01
+_C.MODEL.RETINANET.INFERENCE_TH = 0.05
+_C.MODEL.RETINANET.NMS_TH = 0.4
+
+# detections kept per image by RetinaNet's post-processor (defaults.py:459; the RoI heads read MODEL.ROI_HEADS.DETECTIONS_PER_IMG)
+_C.TEST = CN()
+_C.TEST.DETECTIONS_PER_IMG = 100
+
 _C.SOLVER = CN()
 _C.SOLVER.MAX_ITER = 40000
 _C.SOLVER.BASE_LR = 0.001

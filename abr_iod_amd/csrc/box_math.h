@@ -1,5 +1,5 @@
 // Box coder, matcher and label arithmetic: the one definition behind every kernel that encodes, decodes, clips, matches or labels boxes
-// (rpn.hip, roi_targets.h, rpn_pyramid.hip, detect.hip), beside abr::box_iou (common.h).  Those kernels' results must agree with the reference's
+// (rpn.hip, roi_targets.h, rpn_pyramid.hip, detect.hip, nms.hip, retinanet.hip), beside abr::box_iou (common.h).  Those kernels' results must agree with the reference's
 // and with each other bit for bit, so each function here rounds once per operation: the library is built with the compiler's default
 // contraction, and every body switches it off for itself (a fused dx * w + cx would change results).  Operation order is the reference's,
 // divisions included.
@@ -36,6 +36,20 @@ __device__ __forceinline__ float4 box_decode(const float4 b, const float* d, flo
 __device__ __forceinline__ float4 box_clip(const float4 o, float W1, float H1) {
 #pragma clang fp contract(off)
     return make_float4(fminf(fmaxf(o.x, 0.f), W1), fminf(fmaxf(o.y, 0.f), H1), fminf(fmaxf(o.z, 0.f), W1), fminf(fmaxf(o.w, 0.f), H1));
+}
+
+// Greedy NMS's test of a kept box a (area_a = (a.z - a.x + 1) * (a.w - a.y + 1)) against a later box b (nms_cpu.cpp:5-75): IoU in the reference's
+// form inter / (a + b - inter); `ovr >= thr` suppresses (strict_gt = 0, the CPU rule, canonical here) or `ovr > thr` (nms.cu).  Shared by nms.hip
+// and retinanet.hip, so their keep lists agree pair for pair.
+__device__ __forceinline__ bool nms_suppresses(const float4 a, float area_a, const float4 b, float thr, int strict_gt) {
+#pragma clang fp contract(off)
+    const float xx1 = fmaxf(a.x, b.x), yy1 = fmaxf(a.y, b.y);
+    const float xx2 = fminf(a.z, b.z), yy2 = fminf(a.w, b.w);
+    const float w = fmaxf(0.f, xx2 - xx1 + 1), h = fmaxf(0.f, yy2 - yy1 + 1);
+    const float inter = w * h;
+    const float area_b = (b.z - b.x + 1) * (b.w - b.y + 1);
+    const float ovr = inter / (area_a + area_b - inter);
+    return strict_gt ? (ovr > thr) : (ovr >= thr);
 }
 
 // Matcher's scan of one box against G ground truths (matcher.py:64-66 max over dim 0: the FIRST maximum wins, as torch.max does).  `rowmax`

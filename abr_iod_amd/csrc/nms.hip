@@ -19,20 +19,12 @@
 //           that is all pass 1 computes -- (kept so far + 2048) x 2048 pairs instead of the whole upper triangle -- and every
 //           launch after the sweep has its max_keep boxes returns at once.  2000 of 12000 proposals kept by box ~5500: 11 M pairs
 //           per image instead of 72 M.
-#include "common.h"
+#include "box_math.h"
 
 namespace {
 
 #pragma clang fp contract(off)
-__device__ __forceinline__ bool suppresses(const float4 a, float area_a, const float4 b, float thr, int strict_gt) {
-    const float xx1 = fmaxf(a.x, b.x), yy1 = fmaxf(a.y, b.y);
-    const float xx2 = fminf(a.z, b.z), yy2 = fminf(a.w, b.w);
-    const float w = fmaxf(0.f, xx2 - xx1 + 1), h = fmaxf(0.f, yy2 - yy1 + 1);
-    const float inter = w * h;
-    const float area_b = (b.z - b.x + 1) * (b.w - b.y + 1);
-    const float ovr = inter / (area_a + area_b - inter);
-    return strict_gt ? (ovr > thr) : (ovr >= thr);
-}
+using abr::nms_suppresses;
 
 constexpr int kChunk = 2048;   // boxes per chunk (a multiple of the sweep's 256-box blocks)
 
@@ -74,7 +66,7 @@ __global__ __launch_bounds__(64) void nms_mask_chunk_kernel(const float* __restr
     uint64_t bits = 0;
     const int jend = min(64, n - ct * 64);
     for (int j = jstart; j < jend; j++)
-        if (suppresses(a, area_a, cb[j], thr, strict_gt)) bits |= 1ull << j;
+        if (nms_suppresses(a, area_a, cb[j], thr, strict_gt)) bits |= 1ull << j;
     mask[((size_t)img * n_max + ri) * words + ct] = bits;
 }
 

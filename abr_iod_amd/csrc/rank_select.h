@@ -1,5 +1,5 @@
-// Ranking device code shared by topk.hip, rpn_pyramid.hip and detect.hip: score keys, 64-bit rank words, the radix-select step and the in-LDS
-// bitonic sort.  Every ranking here orders by descending score and breaks ties by ascending index; the entry points agree on that, and on
+// Ranking device code shared by topk.hip, rpn_pyramid.hip, detect.hip and retinanet.hip: score keys, 64-bit rank words, the radix-select step,
+// the exact k-th word, the in-LDS bitonic sort and the stable in-order compaction.  Every ranking here orders by descending score and breaks ties by ascending index; the entry points agree on that, and on
 // which elements tie, only while they share these definitions.
 #pragma once
 #include "common.h"
@@ -63,6 +63,50 @@ __device__ __forceinline__ void bitonic_desc(unsigned long long* buf, int p2) {
             __syncthreads();
         }
     }
+}
+
+// the want-th largest of the nonzero words a[0 .. m): six radix levels over all 64 bits (12, 12, 8 | 12, 12, 8); with first_level = 1 the top
+// 12 bits are known to be `pre` already.  All threads call; h: 4096 ints of LDS.  Returns the word (valid when 1 <= want <= #nonzero words).
+__device__ __forceinline__ unsigned long long kth_word(const unsigned long long* __restrict__ a, long long m, int want, int first_level,
+                                                       unsigned long long pre, int* h, int* s_bin, int* s_krem) {
+    if (threadIdx.x == 0) { *s_krem = want; *s_bin = 0; }
+    __syncthreads();
+    for (int lv = first_level; lv < 6; lv++) {
+        const int sh = lv == 0 ? 52 : lv == 1 ? 40 : lv == 2 ? 32 : lv == 3 ? 20 : lv == 4 ? 8 : 0;
+        const int bits = (lv == 2 || lv == 5) ? 8 : 12, nb = 1 << bits;
+        for (int i = threadIdx.x; i < nb; i += blockDim.x) h[i] = 0;
+        __syncthreads();
+        for (long long j = threadIdx.x; j < m; j += blockDim.x) {
+            const unsigned long long w = a[j];
+            if (w != 0ull && (lv == 0 || (w >> (sh + bits)) == pre)) atomicAdd(&h[(unsigned)(w >> sh) & (nb - 1)], 1);
+        }
+        __syncthreads();
+        find_bin_from_top(h, nb, s_bin, s_krem);
+        __syncthreads();
+        pre = (pre << bits) | (unsigned)*s_bin;
+        __syncthreads();
+    }
+    return pre;
+}
+
+// keep flag -> position among the workgroup's kept elements (rank order), running base in *s_base; all NT threads call; s_wave: NT / 64 ints of LDS
+template <int NT>
+__device__ __forceinline__ int compact_pos(bool keep, int* s_wave, int* s_base) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(keep);
+    const int before = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) s_wave[wave] = __popcll(b);
+    __syncthreads();
+    int off = *s_base;
+    for (int w = 0; w < wave; w++) off += s_wave[w];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < NT / 64; w++) t += s_wave[w];
+        *s_base += t;
+    }
+    __syncthreads();
+    return off + before;
 }
 
 }  // namespace abr

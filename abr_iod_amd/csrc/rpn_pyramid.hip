@@ -34,6 +34,7 @@
 namespace {
 
 using abr::find_bin_from_top;
+using abr::kth_word;
 
 constexpr int MAXL = ABR_MAX_PYRAMID_LEVELS;
 constexpr int KT = 256;       // threads of the chip-wide kernels
@@ -51,30 +52,6 @@ struct PyrLevels {            // by value in the kernel arguments: no device-sid
 };
 struct PyrCnt { int surv, cand; };
 struct SelThr { unsigned long long word; int want, total; };
-
-// the want-th largest of the nonzero words a[0 .. m): six radix levels over all 64 bits (12, 12, 8 | 12, 12, 8); with first_level = 1 the top
-// 12 bits are known to be `pre` already.  All threads call; h: HB ints of LDS.  Returns the word (valid when 1 <= want <= #nonzero words).
-__device__ __forceinline__ unsigned long long kth_word(const unsigned long long* __restrict__ a, long long m, int want, int first_level,
-                                                       unsigned long long pre, int* h, int* s_bin, int* s_krem) {
-    if (threadIdx.x == 0) { *s_krem = want; *s_bin = 0; }
-    __syncthreads();
-    for (int lv = first_level; lv < 6; lv++) {
-        const int sh = lv == 0 ? 52 : lv == 1 ? 40 : lv == 2 ? 32 : lv == 3 ? 20 : lv == 4 ? 8 : 0;
-        const int bits = (lv == 2 || lv == 5) ? 8 : 12, nb = 1 << bits;
-        for (int i = threadIdx.x; i < nb; i += blockDim.x) h[i] = 0;
-        __syncthreads();
-        for (long long j = threadIdx.x; j < m; j += blockDim.x) {
-            const unsigned long long w = a[j];
-            if (w != 0ull && (lv == 0 || (w >> (sh + bits)) == pre)) atomicAdd(&h[(unsigned)(w >> sh) & (nb - 1)], 1);
-        }
-        __syncthreads();
-        find_bin_from_top(h, nb, s_bin, s_krem);
-        __syncthreads();
-        pre = (pre << bits) | (unsigned)*s_bin;
-        __syncthreads();
-    }
-    return pre;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------- ranking
 __global__ __launch_bounds__(KT) void pyr_keys_kernel(PyrLevels lv, int L, unsigned* __restrict__ keys, int* __restrict__ hist) {
@@ -189,25 +166,6 @@ __global__ __launch_bounds__(TT) void pyr_select_sort_kernel(PyrLevels lv, int L
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------- decode
-// keep flag -> position among the workgroup's kept elements (rank order), running base in *s_base; all TT threads call
-__device__ __forceinline__ int compact_pos(bool keep, int* s_wave, int* s_base) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(keep);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = __popcll(b);
-    __syncthreads();
-    int off = *s_base;
-    for (int w = 0; w < wave; w++) off += s_wave[w];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < TT / 64; w++) t += s_wave[w];
-        *s_base += t;
-    }
-    __syncthreads();
-    return off + before;
-}
-
 #pragma clang fp contract(off)
 __global__ __launch_bounds__(TT) void pyr_decode_kernel(PyrLevels lv, int L, int k_max, const int64_t* __restrict__ idx, const float* __restrict__ scores_in,
                                                         const int32_t* __restrict__ img_hw, float wx, float wy, float ww, float wh, float min_size,
@@ -236,7 +194,7 @@ __global__ __launch_bounds__(TT) void pyr_decode_kernel(PyrLevels lv, int L, int
             // boxlist_ops.py:34-48 remove_small_boxes; min_size <= 0 keeps every row, as the single-level path does
             keep = min_size <= 0.f || ((o.z - o.x + 1 >= min_size) && (o.w - o.y + 1 >= min_size));
         }
-        const int pos = compact_pos(keep, s_wave, &s_base);
+        const int pos = abr::compact_pos<TT>(keep, s_wave, &s_base);
         if (keep) {
             po[pos] = o;
             so[pos] = sc;
@@ -335,7 +293,7 @@ __global__ __launch_bounds__(TT) void sel_emit_kernel(const unsigned long long* 
             const int p = c0 + threadIdx.x;
             const unsigned long long w = p < per_img ? a[p] : 0ull;
             const bool take = t.want > 0 && w != 0ull && w >= t.word;
-            const int pos = compact_pos(take, s_wave, &s_base);
+            const int pos = abr::compact_pos<TT>(take, s_wave, &s_base);
             if (take && pos < cap) {
                 const int seg = i * L + p / post;
                 const int row = keep[(size_t)seg * post + p % post];

@@ -41,14 +41,26 @@ ResNet152FPNStagesTo5 = tuple(StageSpec(index=i, block_count=c, return_features=
 STAGE_SPECS = {"R-50-C4": ResNet50StagesTo4, "R-101-C4": ResNet101StagesTo4,
                "R-50-FPN": ResNet50FPNStagesTo5, "R-101-FPN": ResNet101FPNStagesTo5, "R-152-FPN": ResNet152FPNStagesTo5}
 FPN_BODIES = ("R-50-FPN", "R-101-FPN", "R-152-FPN")
+# the single-stage detector's bodies (resnet.py:447-448, backbone.py:74-97): C3..C5 under an FPN with LastLevelP6P7, built only with MODEL.RETINANET_ON
+RETINANET_STAGE_SPECS = {"R-50-FPN-RETINANET": ResNet50FPNStagesTo5, "R-101-FPN-RETINANET": ResNet101FPNStagesTo5}
+RETINANET_BODIES = tuple(RETINANET_STAGE_SPECS)
 
 
-def stage_specs(conv_body):
-    """the StageSpecs of MODEL.BACKBONE.CONV_BODY; NotImplementedError for every body this build does not run"""
+def stage_specs(conv_body, retinanet_on=False):
+    """the StageSpecs of MODEL.BACKBONE.CONV_BODY; NotImplementedError for every body this build does not run.  retinanet_on =
+    MODEL.RETINANET_ON: the RetinaNet bodies are built with it and only with it, and it builds on no other body (the reference's RetinaNet
+    is "only FPN" too)."""
+    if retinanet_on:
+        if conv_body not in RETINANET_BODIES:
+            raise NotImplementedError("MODEL.RETINANET_ON True with MODEL.BACKBONE.CONV_BODY {!r}: RetinaNet runs on its own bodies {} only"
+                                      .format(conv_body, ", ".join(sorted(RETINANET_BODIES))))
+        return RETINANET_STAGE_SPECS[conv_body]
     specs = STAGE_SPECS.get(conv_body)
     if specs is None:
-        raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r}: this build runs the C4 bodies {} and the FPN bodies {} only (no C5, RetinaNet or "
-                                  "FBNet body)".format(conv_body, ", ".join(sorted(set(STAGE_SPECS) - set(FPN_BODIES))), ", ".join(sorted(FPN_BODIES))))
+        raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r}: this build runs the C4 bodies {} and the FPN bodies {} only (no C5 or FBNet body; "
+                                  "the RetinaNet bodies {} need MODEL.RETINANET_ON True)"
+                                  .format(conv_body, ", ".join(sorted(set(STAGE_SPECS) - set(FPN_BODIES))), ", ".join(sorted(FPN_BODIES)),
+                                          ", ".join(sorted(RETINANET_BODIES))))
     return specs
 
 def check_fpn_config(cfg):
@@ -676,7 +688,7 @@ class _StemFn(Function):
 class ResNet(nn.Module):
     def __init__(self, cfg):
         super().__init__()
-        specs = stage_specs(cfg.MODEL.BACKBONE.CONV_BODY)
+        specs = stage_specs(cfg.MODEL.BACKBONE.CONV_BODY, cfg.MODEL.RETINANET_ON)
         check_fpn_config(cfg)
         assert cfg.MODEL.RESNETS.STRIDE_IN_1X1 and cfg.MODEL.RESNETS.NUM_GROUPS == 1
         self.stem = StemWithFixedBatchNorm(cfg)

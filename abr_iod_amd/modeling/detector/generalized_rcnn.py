@@ -11,6 +11,11 @@ backbone -> rpn -> roi_heads orchestration with the reference's three entry poin
     generate_feature_logits_by_targets(images, targets=None)
                              -> ((target_scores, target_bboxes), mask_logits, features, backbone_features,
                                  roi_align_features)                                                            (:169-175)
+
+MODEL.RETINANET_ON (a deliberate departure): the reference's detector cannot call its own RetinaNetModule -- generalized_rcnn.py:74-93 hands it
+four arguments where it takes three and goes on to names that a model without RoI heads never defines.  Here the RetinaNet module stands where the
+RPN does, eval forward(images) returns (detections, features, None) -- there are no RoI heads and no background results -- and everything that
+needs RoI heads or the RetinaNet loss (training, the soften / distillation entry points, the features + proposals call) raises NotImplementedError.
 """
 import os
 import random
@@ -49,7 +54,8 @@ class GeneralizedRCNN(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         self.backbone = build_backbone(cfg)
-        if not cfg.MODEL.RPN_ONLY:
+        self.retinanet = bool(cfg.MODEL.RETINANET_ON)
+        if not cfg.MODEL.RPN_ONLY and not self.retinanet:
             # body and box head must match (C4 body + C5 head, FPN body + MLP head): said here, before the RPN is built around the body's maps
             from ..roi_heads.box_head.box_head import check_box_head_cfg
             check_box_head_cfg(cfg)
@@ -63,8 +69,8 @@ class GeneralizedRCNN(nn.Module):
         # bf16 contractions to the RPN head and layer4 as well (the predictor FCs and every loss stay fp32).
         if cfg.DTYPE == "bfloat16" and os.environ.get("ABR_BF16_SCOPE", "backbone") == "all":
             from ..backbone.resnet import set_conv_math
-            set_conv_math(self.rpn, ops.MATH_BF16)
-            set_conv_math(self.roi_heads, ops.MATH_BF16)
+            for m in self._head_modules():
+                set_conv_math(m, ops.MATH_BF16)
         # Contraction arithmetic of every bottleneck / RPN conv (cfg.DTYPE float32): "bf16x6" = fp32-ACCURATE contractions on the bf16
         # matrix cores -- each operand split exactly into three bf16 terms, six cross products, fp32 accumulate (csrc/conv_igemm.hip),
         # guarded by a hardware range check (ops.x6_range_flags; engine/trainer.py falls back to "f32" when it trips) -- or "f32" =
@@ -82,8 +88,8 @@ class GeneralizedRCNN(nn.Module):
             # "bf16 MFMA backbone" (configs[4]): layer1-3 contract in bf16, EVERYTHING ELSE in the default arithmetic -- until round 4 the RPN head and
             # layer4 of this mode were left on the fp32 MFMA kernels (round 1's default), which is what made the mode 20 % slower than bf16x6
             from ..backbone.resnet import set_conv_math
-            set_conv_math(self.rpn, ops.MATH_F16X3 if env_math == "f16x3" else ops.MATH_BF16X6)
-            set_conv_math(self.roi_heads, ops.MATH_F16X3 if env_math == "f16x3" else ops.MATH_BF16X6)
+            for m in self._head_modules():
+                set_conv_math(m, ops.MATH_F16X3 if env_math == "f16x3" else ops.MATH_BF16X6)
             self.conv_math = env_math      # (the range guard of engine/trainer.py watches the fp32-accurate part)
             self.bf16_backbone = True
         elif cfg.DTYPE == "float16":
@@ -92,13 +98,26 @@ class GeneralizedRCNN(nn.Module):
             self.set_conv_math("f16")
         self.flat = None
 
+    def _head_modules(self):
+        """what follows the backbone: the RPN (or RetinaNet) module and the RoI heads (RetinaNet has none: build_roi_heads gives [])"""
+        return (self.rpn,) if self.retinanet else (self.rpn, self.roi_heads)
+
+    def _no_retinanet(self, what):
+        if self.retinanet:
+            raise NotImplementedError("{} on a RetinaNet model (MODEL.RETINANET_ON): there are no RoI heads, and the RetinaNet loss is not built; "
+                                      "eval forward(images) detects".format(what))
+
+    def _retinanet_training(self):
+        raise NotImplementedError("training a RetinaNet model (MODEL.RETINANET_ON): the RetinaNet loss is not built (rpn/retinanet/loss.py) and "
+                                  "neither is the head's backward; eval() detects")
+
     def set_conv_math(self, name):
         """'f32', 'bf16x6', 'f16x3' or 'f16' for every conv of the backbone, RPN head and layer4 head (takes effect at the next call)"""
         from ..backbone.resnet import set_conv_math
         math = {"f32": ops.MATH_F32, "bf16x6": ops.MATH_BF16X6, "f16x3": ops.MATH_F16X3, "f16": ops.MATH_F16}[name]
         # (a "bf16 MFMA backbone" -- configs[4] -- keeps its own arithmetic when the guard moves the rest: rounding to bf16 is defined for every
         #  finite value, and the mode would otherwise silently stop being what its name says)
-        for m in ((self.rpn, self.roi_heads) if self.bf16_backbone else (self.backbone, self.rpn, self.roi_heads)):
+        for m in (() if self.bf16_backbone else (self.backbone,)) + self._head_modules():
             set_conv_math(m, math)
         self.conv_math = name
 
@@ -131,9 +150,12 @@ class GeneralizedRCNN(nn.Module):
         return out
 
     def forward(self, images, targets=None, rpn_output_source=None, features=None, proposals=None):
+        if self.retinanet and self.training:
+            self._retinanet_training()
         if self.training and targets is None:
             raise ValueError("In training mode, targets should be passed")
         if features is not None and proposals is not None:
+            self._no_retinanet("forward(features=, proposals=)")
             target_scores, target_bboxes, mask_logits, roi_align_features = self.roi_heads.calculate_soften_label(features, proposals)
             return (target_scores, target_bboxes), mask_logits, roi_align_features
         if self.training:
@@ -141,6 +163,8 @@ class GeneralizedRCNN(nn.Module):
         images = to_image_list(images)
         features, backbone_features = self.backbone(images.tensors)
         (proposals, proposal_losses), anchors, rpn_output = self.rpn(images, features, targets, rpn_output_source)
+        if self.retinanet:    # the module's boxes ARE the detections
+            return proposals, features, None
         # generalized_rcnn.py:76-78 -> (detections, features, background detections)
         x, result, results_background, _ = self.roi_heads(features, proposals, targets)
         return result, features, results_background
@@ -155,6 +179,8 @@ class GeneralizedRCNN(nn.Module):
         """Training forward up to the point where the host needs the proposal counts: backbone, RPN head, RPN loss, and the
         proposal selection in flight on its side stream.  The trainer slots the source model's head pass between `forward_begin`
         and `forward_finish`, so the selection (and the host's read-back of its counts) hides behind real work."""
+        if self.retinanet:
+            self._retinanet_training()
         images = to_image_list(images)
         features, backbone_features = self.backbone(images.tensors, prefix)
         return dict(features=features, backbone_features=backbone_features, targets=targets,
@@ -184,6 +210,7 @@ class GeneralizedRCNN(nn.Module):
         """`forward(images, targets)` followed by `forward(images, targets, features=..., proposals=soften_proposals)`
         (train_incremental.py:89-95) as ONE pass: the 64 distillation RoIs per image ride along with the 512 detection RoIs through
         layer4 and the predictor.  Returns (the training 8-tuple, the second call's 3-tuple); same values as the two calls."""
+        self._no_retinanet("forward_joint")
         if targets is None:
             raise ValueError("In training mode, targets should be passed")
         images = to_image_list(images)
@@ -200,6 +227,7 @@ class GeneralizedRCNN(nn.Module):
     def generate_soften_proposal(self, images, targets=None, selected_indices=None):
         """Source-model pass (model.eval(), under no_grad in the trainer): top-128 by objectness, python `random.sample`
         picks 64 (:140-149).  `selected_indices` (list of index lists) injects that choice for parity tests."""
+        self._no_retinanet("generate_soften_proposal")
         if not self.training and targets is None:
             return self.soften_finish(self.soften_begin(images, defer=False), selected_indices)
         images = to_image_list(images)
@@ -304,6 +332,7 @@ class GeneralizedRCNN(nn.Module):
         return (soften_scores, soften_bboxes), mask_logits, all_selected, features, backbone_features, anchors, rpn_output, roi_align_features
 
     def generate_feature_logits_by_targets(self, images, targets=None):
+        self._no_retinanet("generate_feature_logits_by_targets")
         images = to_image_list(images)
         features, backbone_features = self.backbone(images.tensors)
         target_scores, target_bboxes, mask_logits, roi_align_features = self.roi_heads.calculate_soften_label(features, targets)

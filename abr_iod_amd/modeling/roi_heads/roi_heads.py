@@ -90,8 +90,12 @@ class CombinedROIHeads(torch.nn.ModuleDict):
 
 
 def build_roi_heads(cfg, in_channels):
-    if cfg.MODEL.RETINANET_ON:
-        raise NotImplementedError("only the box, mask and keypoint heads are on the hot path (SURVEY.md §2 row 6b)")
+    if cfg.MODEL.RETINANET_ON:   # roi_heads.py:75-79: RetinaNet has no RoI heads
+        from ..backbone.resnet import RETINANET_BODIES
+        if cfg.MODEL.BACKBONE.CONV_BODY not in RETINANET_BODIES:
+            raise NotImplementedError("MODEL.RETINANET_ON True with MODEL.BACKBONE.CONV_BODY {!r}: RetinaNet runs on its own bodies {} only"
+                                      .format(cfg.MODEL.BACKBONE.CONV_BODY, ", ".join(sorted(RETINANET_BODIES))))
+        return []
     if cfg.MODEL.MASK_ON:
         check_mask_head_cfg(cfg)
     if cfg.MODEL.KEYPOINT_ON:

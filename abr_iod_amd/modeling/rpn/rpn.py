@@ -768,4 +768,8 @@ class RPNModule(nn.Module):
 
 
 def build_rpn(cfg, in_channels):
+    """rpn.py:224-230: RetinaNet takes the RPN's place in the detector"""
+    if cfg.MODEL.RETINANET_ON:
+        from .retinanet import build_retinanet
+        return build_retinanet(cfg, in_channels)
     return RPNModule(cfg, in_channels)

@@ -1687,6 +1687,54 @@ def rpn_pyramid_select(props, scores, keep, n_keep, N, fpn_post_n, per_batch):
     return rois, out_scores, src, n_out
 
 
+def retina_max_candidates():
+    """most candidates abr_retina_detect ranks per image, levels * pre_nms_top_n: its in-LDS sort (8192)"""
+    return L.lib().abr_retina_max_candidates()
+
+
+def retina_detect(cls, reg, anchors, A, num_classes, img_hw, score_thresh, pre_nms_top_n, nms_thresh, detections_per_img,
+                  weights=(10.0, 10.0, 5.0, 5.0), min_size=0):
+    """RetinaNet's post-processor for the whole batch (abr_retina_detect: 1 memset + 4 launches, nothing read back).  cls: list of L head outputs
+    [N, nloc_l, ldc_l] (column a * C + c: anchor a, class c + 1; columns >= A * C are padding), reg: list of L [N, nloc_l, ldr_l] (columns 4a .. 4a+3),
+    anchors: list of L [nloc_l * A, 4], C = num_classes foreground classes, img_hw [N,2] int32 -> (boxes [N,cap,4], scores [N,cap], labels [N,cap]
+    int64, n_out [N] int32), cap = L * pre_nms_top_n: per image the classes' NMS survivors class by class, each class by descending score, cut at
+    the detections_per_img-th largest score (ties kept)."""
+    cls, reg, anchors = list(cls), list(reg), list(anchors)
+    n, A, Cn, pre = len(cls), int(A), int(num_classes), int(pre_nms_top_n)
+    if not 1 <= n <= MAX_PYRAMID_LEVELS:
+        raise RuntimeError(f"retina_detect: {n} levels, need 1 .. {MAX_PYRAMID_LEVELS}")
+    if len(reg) != n or len(anchors) != n:
+        raise RuntimeError("retina_detect: the level lists differ in length")
+    if pre > rpn_pyramid_max_k():
+        raise RuntimeError(f"retina_detect: MODEL.RETINANET.PRE_NMS_TOP_N = {pre} exceeds the {rpn_pyramid_max_k()} candidates ranked per (image, level)")
+    if n * pre > retina_max_candidates():
+        raise RuntimeError(f"retina_detect: {n} levels x MODEL.RETINANET.PRE_NMS_TOP_N = {pre} exceeds the {retina_max_candidates()} candidates ranked per image")
+    N = cls[0].shape[0]
+    for l in range(n):
+        L.require_cuda(cls[l], reg[l], anchors[l])
+        for what, t, need in (("cls", cls[l], A * Cn), ("reg", reg[l], 4 * A)):
+            if t.dtype != _f32 or t.dim() != 3 or not t.is_contiguous() or t.shape[0] != N or t.shape[1] != cls[l].shape[1] or t.shape[2] < need:
+                raise RuntimeError(f"retina_detect: {what} of level {l} must be a contiguous float32 [{N},nloc,>={need}] tensor, got {tuple(t.shape)} {t.dtype}")
+        a = anchors[l]
+        if a.dtype != _f32 or not a.is_contiguous() or tuple(a.shape) != (cls[l].shape[1] * A, 4):
+            raise RuntimeError(f"retina_detect: anchors of level {l} must be a contiguous float32 [{cls[l].shape[1] * A},4] tensor, got {tuple(a.shape)}")
+    L.require_cuda(img_hw)
+    if img_hw.dtype != torch.int32 or tuple(img_hw.shape) != (N, 2) or not img_hw.is_contiguous():
+        raise RuntimeError(f"retina_detect: img_hw must be a contiguous int32 [{N},2] tensor")
+    dev, cap = cls[0].device, n * pre
+    boxes = torch.empty((N, cap, 4), dtype=_f32, device=dev)
+    scores = torch.empty((N, cap), dtype=_f32, device=dev)
+    labels = torch.empty((N, cap), dtype=torch.int64, device=dev)
+    n_out = torch.empty((N,), dtype=torch.int32, device=dev)
+    vp, ci = C.c_void_p * n, C.c_int * n
+    L.check(L.lib().abr_retina_detect(vp(*[t.data_ptr() for t in cls]), ci(*[t.shape[2] for t in cls]), vp(*[t.data_ptr() for t in reg]),
+                                      ci(*[t.shape[2] for t in reg]), vp(*[t.data_ptr() for t in anchors]), ci(*[t.shape[1] for t in cls]), n, N, A, Cn,
+                                      L.ptr(img_hw), float(score_thresh), pre, float(nms_thresh), int(detections_per_img),
+                                      *[float(v) for v in weights], float(min_size), cap, L.ptr(boxes), L.ptr(scores), L.ptr(labels), L.ptr(n_out),
+                                      L.stream()), "retina_detect")
+    return boxes, scores, labels, n_out
+
+
 def match_encode(boxes, gt, gt_labels, vis, hi, lo, allow_low_quality, weights, rpn_labels):
     """-> matched int64 [n], labels (fp32 RPN / int64 head) [n], reg_targets [n,4]"""
     boxes, gt = L.f32c(boxes), L.f32c(gt)

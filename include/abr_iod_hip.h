@@ -667,6 +667,31 @@ int abr_rpn_pyramid_decode(const float* const* y_host, const int* nloc_host, con
  * count), n_out [N] int32.  Scores may be any non-NaN fp32. */
 int abr_rpn_pyramid_select(const float* props, const float* scores, const int32_t* keep, const int32_t* n_keep, int N, int L, int k_max, int post,
                            int fpn_post_n, int mode, float* rois, float* out_scores, int32_t* src, int32_t* n_out, void* stream);
+/* RetinaNet's test-time post-processor over a feature pyramid (rpn/retinanet/inference.py:73-123 per level, :131-174 across the levels), S = N * L
+ * (image, level) segments, through every stage together and nothing read back (csrc/retinanet.hip): 1 memset + 4 launches whatever N, L and C are.
+ * cls_host[l] = device pointer of level l's class logits [N, nloc[l], ldc[l]] (row = location; column a * C + c the logit of anchor loc * A + a and
+ * class c + 1, columns >= A * C never read), reg_host[l] = its deltas [N, nloc[l], ldr[l]] (columns 4a .. 4a+3 anchor a's, further columns never
+ * read), anchors_host[l] = device [nloc[l] * A, 4]; the six tables are HOST arrays of L entries copied into the kernels' arguments.  A anchors per
+ * location and C = NUM_CLASSES - 1 foreground classes are shared by the levels: there is one head.  img_hw [N,2] int32 (h, w).
+ *   a. per segment: score = sigmoid(x) in fp32 by abr_topk_sigmoid's formula; a logit is a candidate iff score > score_thresh; the
+ *      min(#candidates, pre_nms_top_n) highest are kept by descending score.  torch.topk(sorted=False) leaves ties undefined: here equal scores go
+ *      by ascending flat index loc * A * C + a * C + c.
+ *   b. anchor = flat / C, label = flat % C + 1; BoxCoder(wx, wy, ww, wh).decode and clip_to_image through the one decode and clip of csrc/box_math.h
+ *      (bit for bit abr_rpn_pyramid_decode's), remove_small_boxes(min_size) (min_size <= 0 keeps every row), stable compaction in rank order.
+ *   c. per image: for each class 1 .. C in turn its candidates of all levels by descending score -- equal scores by ascending candidate position
+ *      level * pre_nms_top_n + rank -- through greedy NMS at nms_thresh with abr_nms_sorted_batched's `>=` rule (strict_gt = 0); the survivors
+ *      concatenated class by class; when more than detections_per_img (> 0; <= 0: no limit) remain only those with score >= the
+ *      detections_per_img-th largest (ties at the cut all kept, order unchanged).
+ * Every cut is an exact radix selection on unique words, every list is compacted in order: no result depends on which workgroup won an atomic.
+ * out_boxes [N,cap,4], out_scores [N,cap], out_labels [N,cap] int64, n_out [N] int32 (device), rows past the count 0; cap = L * pre_nms_top_n holds
+ * every case, ties included.  Limits, checked before any launch (else ABR_E_INVALID): 1 <= L <= ABR_MAX_PYRAMID_LEVELS, pre_nms_top_n <=
+ * abr_rpn_pyramid_max_k() (2048), L * pre_nms_top_n <= abr_retina_max_candidates() (8192: the per-image sort in LDS; the defaults need 5 x 1000),
+ * C <= 524286, every level's nloc * A * C and N * nloc * ld in int32, N * L <= 65535.  N == 0 launches nothing. */
+int abr_retina_max_candidates(void);
+int abr_retina_detect(const float* const* cls_host, const int* ldc_host, const float* const* reg_host, const int* ldr_host,
+                      const float* const* anchors_host, const int* nloc_host, int L, int N, int A, int C, const int32_t* img_hw, float score_thresh,
+                      int pre_nms_top_n, float nms_thresh, int detections_per_img, float wx, float wy, float ww, float wh, float min_size, int cap,
+                      float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* n_out, void* stream);
 /* The RPN loss over a feature pyramid (rpn/loss.py:104-148 with rpn/utils.py:10-45; csrc/rpn_pyramid_loss.hip).  y_host[l] = device pointer of
  * level l's fused head output [N, nloc[l], Cf] (columns 0 .. A-1 the logits of anchors loc * A + a, A + 4a .. +3 their deltas; A, Cf and N are
  * shared by the levels: there is one head); y_host / nloc_host are HOST arrays of L entries copied into the kernel's arguments.  An image's anchors

@@ -123,7 +123,7 @@ def to_tensor_normalize(img, mean, std, to_bgr255=True, flip=False):
     -> float32 [3,H,W]."""
     import torch
     if flip:
-        img = img[:, ::-1]
+        img = img[:, ::-1].copy()   # (a copy: the view of a 1-pixel-wide image counts as contiguous and keeps its negative stride)
     t = torch.from_numpy(np.ascontiguousarray(img)).permute(2, 0, 1).contiguous().to(torch.float32).div(255)
     if to_bgr255:
         t = t[[2, 1, 0]] * 255

@@ -179,6 +179,9 @@ _SIGS = {
     "abr_rpn_pyramid_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "abr_retina_max_candidates": (_i, []),
     "abr_retina_detect": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _f, _i, _f, _i, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "abr_retina_targets": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "abr_retina_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp]),
+    "abr_retina_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "abr_rpn_pyramid_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "abr_rpn_pyramid_loss_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "abr_box_encode": (_i, [_vp, _vp, _i, _f, _f, _f, _f, _vp, _vp]),

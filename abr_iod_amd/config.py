@@ -208,8 +208,8 @@ _C.MODEL.ROI_KEYPOINT_HEAD.RESOLUTION = 14
 _C.MODEL.ROI_KEYPOINT_HEAD.NUM_CLASSES = 17
 _C.MODEL.ROI_KEYPOINT_HEAD.SHARE_BOX_FEATURE_EXTRACTOR = True
 
-# RetinaNet (defaults.py:325-380).  Honoured in eval: the anchors, USE_C5, NUM_CONVS, PRIOR_PROB, PRE_NMS_TOP_N, INFERENCE_TH, NMS_TH; the loss keys
-# (BBOX_REG_*, FG / BG_IOU_THRESHOLD, LOSS_*) wait for the RetinaNet loss: a RetinaNet model in training mode raises
+# RetinaNet (defaults.py:325-380).  Honoured in eval: the anchors, USE_C5, NUM_CONVS, PRIOR_PROB, PRE_NMS_TOP_N, INFERENCE_TH, NMS_TH; in training the
+# loss keys too (BBOX_REG_BETA / BBOX_REG_WEIGHT, FG / BG_IOU_THRESHOLD, LOSS_GAMMA / LOSS_ALPHA: rpn/retinanet.py make_retinanet_loss_evaluator)
 _C.MODEL.RETINANET = CN()
 _C.MODEL.RETINANET.NUM_CLASSES = 81            # foreground classes and background
 _C.MODEL.RETINANET.ANCHOR_SIZES = (32, 64, 128, 256, 512)

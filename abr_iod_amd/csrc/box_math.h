@@ -72,6 +72,32 @@ __device__ __forceinline__ MatchScan match_scan(const float* gt, int G, const fl
     return rowmax ? match_scan_lq<true>(gt, G, b, rowmax) : match_scan_lq<false>(gt, G, b, nullptr);
 }
 
+// Matcher.set_low_quality_matches_'s first pass (matcher.py:83-112): per ground truth its maximum IoU over all boxes, as the bit pattern
+// match_scan_lq compares against.  The maximum over a 256-thread workgroup (all threads call; s_m: 4 floats): ONE atomic per workgroup and
+// ground-truth box then goes to the shared word: with one per WAVE, the ~560 waves of the RPN call queued on a handful of addresses (80 us
+// for 35 910 anchors x 5 boxes)
+__device__ __forceinline__ float block_max_256(float m, float* s_m) {
+    m = wave_max(m);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+    __syncthreads();
+    return fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+}
+// the pass itself, for one image's G ground truths (G == 0: nothing is read): all 256 threads of every workgroup along x call, each with its
+// first box j0 and the grid's stride along x (read off blockDim in the kernel, where the compiler knows the launch is uniform); rowmax zeroed
+// by the caller.  Shared by the RPN's targets (rpn.hip) and RetinaNet's (retinanet_loss.hip).
+__device__ __forceinline__ void gt_row_max(const float* boxes, int n, unsigned j0, unsigned stride, const float* gt, int G, unsigned* rowmax) {
+    __shared__ float s_m[4];
+    for (int g = 0; g < G; g++) {
+        const float4 gb = reinterpret_cast<const float4*>(gt)[g];
+        float m = 0.f;
+        for (int j = j0; j < n; j += stride)
+            m = fmaxf(m, box_iou(gb, reinterpret_cast<const float4*>(boxes)[j]));
+        m = block_max_256(m, s_m);
+        if (threadIdx.x == 0) atomicMax(rowmax + g, __float_as_uint(m));  // IoU >= 0: bit pattern is monotone
+    }
+}
+
 // Matcher's result for a scanned box (matcher.py:68-75, low-quality matches restored :108-112): the ground truth's index, -1 BELOW_LOW_THRESHOLD,
 // -2 BETWEEN_THRESHOLDS.  The ground truth a caller then reads is row max(m, 0) (clamp(min=0) of rpn/loss.py:59, box_head/loss.py:52).
 __device__ __forceinline__ int match_index(float best, int bi, bool lq, float hi, float lo) {

@@ -4,28 +4,20 @@
 #include <float.h>
 
 #include "common.h"
+#include "focal.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
 // Sigmoid focal loss -- csrc/cuda/SigmoidFocalLoss_cuda.cu:20-101, for T = float and T = double (AT_DISPATCH_FLOATING_TYPES, :128,172).
-// The reference's template keeps its expf / powf / logf calls and its `1.` literals with every T: float transcendentals inside double
-// sub-expressions (kept so, it is elementwise and fp64 is cheap on CDNA4); gamma / alpha are `const float` there too.
+// The element (value and derivative) is abr::focal_value / abr::focal_deriv (focal.h), shared with the RetinaNet loss.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void focal_fwd(const T* __restrict__ logits, const int32_t* __restrict__ targets, int64_t total, int C, float gamma,
                                                   float alpha, T* __restrict__ losses) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int n = i / C, d = i % C, t = targets[n];
-        const T c1 = (t == d + 1), c2 = (t >= 0) & (t != d + 1);
-        const T zn = (1.0 - alpha), zp = alpha, x = logits[i];
-        const T p = 1. / (1. + expf((float)-x));
-        const T term1 = powf((float)(1. - p), gamma) * logf((float)fmax(p, (T)FLT_MIN));
-        const T term2 = powf((float)p, gamma) * (-1. * x * (x >= 0) - logf((float)(1. + expf((float)(x - 2. * x * (x >= 0))))));
-        T l = 0;
-        l += -c1 * term1 * zp;
-        l += -c2 * term2 * zn;
-        losses[i] = l;
+        losses[i] = abr::focal_value<T>(logits[i], t, d, gamma, alpha);
     }
 }
 
@@ -34,16 +26,7 @@ __global__ __launch_bounds__(256) void focal_bwd(const T* __restrict__ logits, c
                                                   int64_t total, int C, float gamma, float alpha, T* __restrict__ d_logits) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int n = i / C, d = i % C, t = targets[n];
-        const T c1 = (t == d + 1), c2 = (t >= 0) & (t != d + 1);
-        const T zn = (1.0 - alpha), zp = alpha, x = logits[i];
-        const T p = 1. / (1. + expf((float)-x));
-        const T term1 = powf((float)(1. - p), gamma) * (1. - p - (p * gamma * logf((float)fmax(p, (T)FLT_MIN))));
-        const T term2 = powf((float)p, gamma) *
-                        ((-1. * x * (x >= 0) - logf((float)(1. + expf((float)(x - 2. * x * (x >= 0)))))) * (1. - p) * gamma - p);
-        T g = 0;
-        g += -c1 * term1 * zp;
-        g += -c2 * term2 * zn;
-        d_logits[i] = g * d_losses[i];
+        d_logits[i] = abr::focal_deriv<T>(logits[i], t, d, gamma, alpha) * d_losses[i];
     }
 }
 

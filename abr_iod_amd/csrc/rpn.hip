@@ -38,29 +38,8 @@ __global__ void decode_clip_kernel(const float* __restrict__ reg, int reg_stride
 }
 
 // pass 1: per-gt maximum IoU over all boxes (needed only for Matcher.set_low_quality_matches_, matcher.py:83-112)
-// maximum over a 256-thread workgroup (all threads call; s_m: 4 floats).  ONE atomic per workgroup and ground-truth box then goes to the
-// shared word: with one per WAVE, the ~560 waves of the RPN call queued on a handful of addresses (80 us for 35 910 anchors x 5 boxes)
-__device__ __forceinline__ float block_max_256(float m, float* s_m) {
-    m = abr::wave_max(m);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-    __syncthreads();
-    return fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-}
-
-// the pass itself, for one image's G ground truths: all 256 threads of every workgroup along x call, each with its first box j0 and the
-// grid's stride along x (read off blockDim in the kernel, where the compiler knows the launch is uniform)
-__device__ __forceinline__ void gt_row_max(const float* boxes, int n, unsigned j0, unsigned stride, const float* gt, int G, unsigned* rowmax) {
-    __shared__ float s_m[4];
-    for (int g = 0; g < G; g++) {
-        const float4 gb = reinterpret_cast<const float4*>(gt)[g];
-        float m = 0.f;
-        for (int j = j0; j < n; j += stride)
-            m = fmaxf(m, abr::box_iou(gb, reinterpret_cast<const float4*>(boxes)[j]));
-        m = block_max_256(m, s_m);
-        if (threadIdx.x == 0) atomicMax(rowmax + g, __float_as_uint(m));  // IoU >= 0: bit pattern is monotone
-    }
-}
+// (the pass itself is abr::gt_row_max, box_math.h)
+using abr::gt_row_max;
 
 __global__ __launch_bounds__(256) void gt_max_iou_kernel(const float* __restrict__ boxes, int n, const float* __restrict__ gt, int G,
                                   unsigned* __restrict__ rowmax) {

@@ -28,6 +28,7 @@ enum ScratchSlot {
     SCRATCH_RPN_PYRAMID,    // rpn_pyramid.hip: the pyramid ranking's histograms, counters, survivors, candidates and keys
     SCRATCH_RPN_SELECT,     // rpn_pyramid.hip: the cross-level selection's candidate words and thresholds
     SCRATCH_RETINA,         // retinanet.hip: histograms, counters, survivors, the segments' decoded rows and the bin lists
+    SCRATCH_RETINA_TARGETS, // retinanet_loss.hip: the per-ground-truth maximum IoUs of abr_retina_targets
 };
 // process-wide zero-initialised words
 enum WordSlot { WORDS_X6_FLAGS, WORDS_H3_STATS, WORDS_AMAX_RING, WORDS_SLOTS };

@@ -243,7 +243,11 @@ def _join_source_stream(deferred):
 
 def train_step(model_source, model_target, images, targets, optimizer, scheduler, cfg, faithful_rng=False, log=None, next_images=None):
     """One iteration of tools/train_incremental.py:77-147.  Returns (loss_dict_target incl. 'distillation_loss', total loss)."""
-    from ..modeling.backbone.resnet import FPN_BODIES
+    from ..modeling.backbone.resnet import FPN_BODIES, RETINANET_BODIES
+    if cfg.MODEL.BACKBONE.CONV_BODY in RETINANET_BODIES:
+        # a single-stage detector has no RoI heads to distil: it trains through model(images, targets) and an optimiser step
+        raise NotImplementedError("MODEL.BACKBONE.CONV_BODY {!r}: the incremental train_step runs the C4 bodies only; drive a RetinaNet model "
+                                  "through GeneralizedRCNN.forward(images, targets) and FusedSGD.step".format(cfg.MODEL.BACKBONE.CONV_BODY))
     if cfg.MODEL.BACKBONE.CONV_BODY in FPN_BODIES:
         # the step's stream choreography (source prefetch, joint head pass, gradient-exchange hooks on layer4's backward) is written around the
         # C4 head; an FPN detector trains through model(images, targets) / forward_joint and an optimiser step

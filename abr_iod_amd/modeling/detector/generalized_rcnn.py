@@ -14,8 +14,11 @@ backbone -> rpn -> roi_heads orchestration with the reference's three entry poin
 
 MODEL.RETINANET_ON (a deliberate departure): the reference's detector cannot call its own RetinaNetModule -- generalized_rcnn.py:74-93 hands it
 four arguments where it takes three and goes on to names that a model without RoI heads never defines.  Here the RetinaNet module stands where the
-RPN does, eval forward(images) returns (detections, features, None) -- there are no RoI heads and no background results -- and everything that
-needs RoI heads or the RetinaNet loss (training, the soften / distillation entry points, the features + proposals call) raises NotImplementedError.
+RPN does, eval forward(images) returns (detections, features, None) -- there are no RoI heads and no background results -- and training
+forward(images, targets) returns the training 8-tuple (losses, features, backbone_features, anchors, rpn_output, None, None, None) with
+losses = {"loss_retina_cls", "loss_retina_reg"}: loss.backward() and FusedSGD.step() train it as they train the FPN detectors.  Targets are one
+BoxList with `labels` per image; a call without them raises rpn.MissingTargets.  Everything that needs RoI heads or a proposal selection to
+overlap (forward_begin / forward_finish, the soften / distillation entry points, the features + proposals call) raises NotImplementedError.
 """
 import os
 import random
@@ -104,12 +107,14 @@ class GeneralizedRCNN(nn.Module):
 
     def _no_retinanet(self, what):
         if self.retinanet:
-            raise NotImplementedError("{} on a RetinaNet model (MODEL.RETINANET_ON): there are no RoI heads, and the RetinaNet loss is not built; "
+            raise NotImplementedError("{} on a RetinaNet model (MODEL.RETINANET_ON): there are no RoI heads; forward(images, targets) trains, "
                                       "eval forward(images) detects".format(what))
 
-    def _retinanet_training(self):
-        raise NotImplementedError("training a RetinaNet model (MODEL.RETINANET_ON): the RetinaNet loss is not built (rpn/retinanet/loss.py) and "
-                                  "neither is the head's backward; eval() detects")
+    def _retinanet_targets(self, what, images, targets):
+        """a training call on a RetinaNet model: its targets are checked before the backbone runs (rpn.MissingTargets)"""
+        from ..rpn.retinanet import require_targets
+        n = len(images) if isinstance(images, (list, tuple)) else (len(images.image_sizes) if hasattr(images, "image_sizes") else None)
+        require_targets(what, targets, n)
 
     def set_conv_math(self, name):
         """'f32', 'bf16x6', 'f16x3' or 'f16' for every conv of the backbone, RPN head and layer4 head (takes effect at the next call)"""
@@ -150,19 +155,23 @@ class GeneralizedRCNN(nn.Module):
         return out
 
     def forward(self, images, targets=None, rpn_output_source=None, features=None, proposals=None):
+        if self.retinanet and features is not None and proposals is not None:
+            self._no_retinanet("forward(features=, proposals=)")
         if self.retinanet and self.training:
-            self._retinanet_training()
+            self._retinanet_targets("GeneralizedRCNN.forward on a RetinaNet model", images, targets)
         if self.training and targets is None:
             raise ValueError("In training mode, targets should be passed")
         if features is not None and proposals is not None:
             self._no_retinanet("forward(features=, proposals=)")
             target_scores, target_bboxes, mask_logits, roi_align_features = self.roi_heads.calculate_soften_label(features, proposals)
             return (target_scores, target_bboxes), mask_logits, roi_align_features
-        if self.training:
+        if self.training and not self.retinanet:
             return self.forward_finish(self.forward_begin(images, targets, rpn_output_source))
         images = to_image_list(images)
         features, backbone_features = self.backbone(images.tensors)
         (proposals, proposal_losses), anchors, rpn_output = self.rpn(images, features, targets, rpn_output_source)
+        if self.retinanet and self.training:    # no RoI heads: the module's two losses are the detector's
+            return dict(proposal_losses), features, backbone_features, anchors, rpn_output, None, None, None
         if self.retinanet:    # the module's boxes ARE the detections
             return proposals, features, None
         # generalized_rcnn.py:76-78 -> (detections, features, background detections)
@@ -180,7 +189,9 @@ class GeneralizedRCNN(nn.Module):
         proposal selection in flight on its side stream.  The trainer slots the source model's head pass between `forward_begin`
         and `forward_finish`, so the selection (and the host's read-back of its counts) hides behind real work."""
         if self.retinanet:
-            self._retinanet_training()
+            self._retinanet_targets("GeneralizedRCNN.forward_begin on a RetinaNet model", images, targets)
+            raise NotImplementedError("forward_begin / forward_finish on a RetinaNet model (MODEL.RETINANET_ON): there is no proposal selection "
+                                      "to overlap with a source model's pass; forward(images, targets) trains")
         images = to_image_list(images)
         features, backbone_features = self.backbone(images.tensors, prefix)
         return dict(features=features, backbone_features=backbone_features, targets=targets,

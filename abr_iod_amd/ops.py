@@ -1970,6 +1970,107 @@ def rpn_pyramid_loss_backward(shapes, A, rec, max_pos, batch, g_obj, g_box, devi
     return out
 
 
+def retina_targets(anchors, gt_boxes, gt_labels, hi, lo, weights=(10.0, 10.0, 5.0, 5.0)):
+    """RetinaNet's labelled anchor targets for the whole batch (abr_retina_targets: two launches, nothing read back).  anchors [n,4]: the levels'
+    anchors concatenated, shared by the images; gt_boxes / gt_labels: per image [G_i,4] fp32 and [G_i] integer classes (G_i may be 0: every
+    anchor of that image is background) -> (labels [N,n] int32: class / 0 background / -1 ignored, reg_targets [N,n,4], n_pos [1] int32)"""
+    gt_boxes, gt_labels = list(gt_boxes), list(gt_labels)
+    N, dev = len(gt_boxes), anchors.device
+    if len(gt_labels) != N:
+        raise RuntimeError(f"retina_targets: {N} box tables and {len(gt_labels)} label tables")
+    L.require_cuda(anchors, *gt_boxes, *gt_labels)
+    anchors = L.f32c(anchors)
+    if anchors.dim() != 2 or anchors.shape[1] != 4:
+        raise RuntimeError(f"retina_targets: anchors must be [n,4], got {tuple(anchors.shape)}")
+    n = anchors.shape[0]
+    gtb = [L.f32c(b).reshape(-1, 4) for b in gt_boxes]
+    gtl = [l.to(torch.int64).contiguous() for l in gt_labels]
+    n_gt = [int(b.shape[0]) for b in gtb]
+    if any(l.numel() != g for l, g in zip(gtl, n_gt)):
+        raise RuntimeError("retina_targets: every image needs one label per ground-truth box")
+    labels = torch.empty((N, n), dtype=torch.int32, device=dev)
+    tgt = torch.empty((N, n, 4), dtype=_f32, device=dev)
+    n_pos = torch.zeros((1,), dtype=torch.int32, device=dev)
+    if N == 0:
+        return labels, tgt, n_pos
+    gtb_tab, gtl_tab, ngt_tab = _pointer_table(gtb, dev), _pointer_table(gtl, dev), _small_table(n_gt, torch.int32, dev)
+    L.check(L.lib().abr_retina_targets(L.ptr(anchors), n, N, L.ptr(gtb_tab), L.ptr(gtl_tab), L.ptr(ngt_tab), max(n_gt), float(hi), float(lo),
+                                       *[float(v) for v in weights], L.ptr(labels), L.ptr(tgt), L.ptr(n_pos), L.stream()), "retina_targets")
+    del gtb, gtl    # (kept alive until the launch is enqueued: a free is then ordered behind the kernels on this stream)
+    return labels, tgt, n_pos
+
+
+def _retina_loss_tables(what, cls, reg, A, num_classes, labels, reg_targets, n_pos):
+    """checks and host tables shared by retina_loss and retina_loss_backward; cls / reg: the levels' contiguous fp32 NHWC head outputs
+    [N,H_l,W_l,ld] (or [N,nloc_l,ld])"""
+    cls, reg = list(cls), list(reg)
+    nL = len(cls)
+    if not 1 <= nL <= MAX_PYRAMID_LEVELS:
+        raise RuntimeError(f"{what}: {nL} levels, need 1 .. {MAX_PYRAMID_LEVELS}")
+    if len(reg) != nL:
+        raise RuntimeError(f"{what}: the level lists differ in length")
+    N = cls[0].shape[0]
+    nloc = []
+    for l in range(nL):
+        L.require_cuda(cls[l], reg[l])
+        for name, t in (("cls", cls[l]), ("reg", reg[l])):
+            if t.dtype != _f32 or t.dim() not in (3, 4) or not t.is_contiguous() or t.shape[0] != N:
+                raise RuntimeError(f"{what}: {name} of level {l} must be a contiguous float32 [{N},H,W,ld] tensor, got {tuple(t.shape)} {t.dtype}")
+        nloc.append(cls[l][0, ..., 0].numel() if N and cls[l].shape[-1] else 1)
+        if N and reg[l].shape[-1] and reg[l][0, ..., 0].numel() != nloc[l]:
+            raise RuntimeError(f"{what}: cls and reg of level {l} differ in their locations: {tuple(cls[l].shape)} and {tuple(reg[l].shape)}")
+    n = int(A) * sum(nloc)
+    L.require_cuda(labels, reg_targets, n_pos)
+    if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (N, n):
+        raise RuntimeError(f"{what}: labels must be contiguous int32 [{N},{n}], got {tuple(labels.shape)} {labels.dtype}")
+    if reg_targets.dtype != _f32 or not reg_targets.is_contiguous() or tuple(reg_targets.shape) != (N, n, 4):
+        raise RuntimeError(f"{what}: reg_targets must be contiguous float32 [{N},{n},4], got {tuple(reg_targets.shape)} {reg_targets.dtype}")
+    if n_pos.dtype != torch.int32 or n_pos.numel() != 1:
+        raise RuntimeError(f"{what}: n_pos must be one int32, got {tuple(n_pos.shape)} {n_pos.dtype}")
+    vp, ci = C.c_void_p * nL, C.c_int * nL
+    tabs = (vp(*[t.data_ptr() for t in cls]), ci(*[t.shape[-1] for t in cls]), vp(*[t.data_ptr() for t in reg]), ci(*[t.shape[-1] for t in reg]),
+            ci(*nloc), nL, N, int(A), int(num_classes))
+    return cls, reg, nloc, N, tabs
+
+
+def retina_loss(cls, reg, A, num_classes, labels, reg_targets, n_pos, gamma, alpha, beta, regress_norm):
+    """RetinaNet's two losses over L levels in one launch (abr_retina_loss).  cls / reg: lists of L NHWC head outputs [N,H_l,W_l,ldc] (column
+    a * C + c; columns >= A * C never read) / [N,H_l,W_l,ldr] (columns 4a .. 4a+3); labels [N,n] int32, reg_targets [N,n,4], n_pos [1] int32 as
+    retina_targets returns them -> losses [2] = (focal sum / (n_pos + N), smooth-L1 sum over the positives / max(1, n_pos * regress_norm))"""
+    cls, reg, nloc, N, tabs = _retina_loss_tables("retina_loss", cls, reg, A, num_classes, labels, reg_targets, n_pos)
+    losses = torch.zeros((2,), dtype=_f32, device=cls[0].device)
+    L.check(L.lib().abr_retina_loss(*tabs, L.ptr(labels), L.ptr(reg_targets), L.ptr(n_pos), float(gamma), float(alpha), float(beta),
+                                    float(regress_norm), L.ptr(losses), L.stream()), "retina_loss")
+    return losses
+
+
+def retina_loss_backward(cls, reg, A, num_classes, labels, reg_targets, n_pos, gamma, alpha, beta, regress_norm, g_cls, g_reg, out=None):
+    """The gradient of retina_loss's two losses times their upstream gradients g_cls / g_reg (device scalars), recomputed from the logits
+    (abr_retina_loss_backward: one launch that writes every element) -> (list of L views shaped like cls, list of L views shaped like reg) of
+    ONE allocation each, the levels back to back.  out = (d_cls, d_reg): flat fp32 buffers to write into (tests: sentinels)."""
+    cls, reg, nloc, N, tabs = _retina_loss_tables("retina_loss_backward", cls, reg, A, num_classes, labels, reg_targets, n_pos)
+    dev = cls[0].device
+    g_cls, g_reg = L.f32c(g_cls), L.f32c(g_reg)
+    L.require_cuda(g_cls, g_reg)
+    nc, nr = sum(t.numel() for t in cls), sum(t.numel() for t in reg)
+    if out is None:
+        out = (torch.empty((nc,), dtype=_f32, device=dev), torch.empty((nr,), dtype=_f32, device=dev))
+    d_cls, d_reg = out
+    if d_cls.numel() != nc or d_reg.numel() != nr or d_cls.dtype != _f32 or d_reg.dtype != _f32 or not (d_cls.is_contiguous() and d_reg.is_contiguous()):
+        raise RuntimeError(f"retina_loss_backward: out must be contiguous float32 buffers of {nc} and {nr} elements")
+    L.check(L.lib().abr_retina_loss_backward(*tabs, L.ptr(labels), L.ptr(reg_targets), L.ptr(n_pos), float(gamma), float(alpha), float(beta),
+                                             float(regress_norm), L.ptr(g_cls), L.ptr(g_reg), L.ptr(d_cls), L.ptr(d_reg), L.stream()),
+            "retina_loss_backward")
+    views = []
+    for buf, ts in ((d_cls, cls), (d_reg, reg)):
+        o, vs = 0, []
+        for t in ts:
+            vs.append(buf[o: o + t.numel()].view(t.shape))
+            o += t.numel()
+        views.append(vs)
+    return views[0], views[1]
+
+
 def gather_proposals(props, scores, keep, picks, P):
     """rois [N*P,5] = (i, props[i, keep[i, picks[i*P+j]]]), obj [N*P]: P picked rows per image of the post-NMS lists"""
     N, k_pre, _ = props.shape

@@ -692,6 +692,43 @@ int abr_retina_detect(const float* const* cls_host, const int* ldc_host, const f
                       const float* const* anchors_host, const int* nloc_host, int L, int N, int A, int C, const int32_t* img_hw, float score_thresh,
                       int pre_nms_top_n, float nms_thresh, int detections_per_img, float wx, float wy, float ww, float wh, float min_size, int cap,
                       float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* n_out, void* stream);
+/* RetinaNet's training targets for the whole batch (rpn/retinanet/loss.py with rpn/loss.py:66-102; csrc/retinanet_loss.hip): Matcher(hi, lo,
+ * allow_low_quality_matches = True), copied_fields = ['labels'], discard_cases = ['between_thresholds'] only -- there is NO visibility discard.
+ * anchors [n,4]: the levels' anchors concatenated, shared by the images (n = A * sum nloc[l]); gt_ptrs / gt_label_ptrs: device arrays of N device
+ * pointers ([G_i,4] fp32, [G_i] int64); n_gt [N] int32 (device), g_max >= max G_i.
+ *   labels [N,n] int32: the class of the matched ground truth (first maximum wins), 0 background (best IoU < lo), -1 ignored (lo <= best < hi and
+ *     no low-quality match);  reg_targets [N,n,4] = BoxCoder(wx, wy, ww, wh).encode(gt[max(m, 0)], anchor);  n_pos [1] int32 = the number of
+ *     labels > 0 over the batch (integer counting: deterministic).
+ * Through the one matcher, label rule and box coder of csrc/box_math.h.  An image with G_i == 0 (the reference crashes there): every anchor gets
+ * label 0 and zero targets, and neither of its ground-truth tables is read.  2 memsets + 2 launches, no host synchronisation; N == 0 launches
+ * nothing.  N * n in int32, N <= 65535, anchors and reg_targets 16-byte aligned, else ABR_E_INVALID before any launch. */
+int abr_retina_targets(const float* anchors, int n, int N, const float* const* gt_ptrs, const int64_t* const* gt_label_ptrs, const int32_t* n_gt,
+                       int g_max, float hi, float lo, float wx, float wy, float ww, float wh, int32_t* labels, float* reg_targets, int32_t* n_pos,
+                       void* stream);
+/* RetinaNet's loss over a feature pyramid (rpn/retinanet/loss.py:44-84; csrc/retinanet_loss.hip), read where the head left its outputs.  The level
+ * tables are abr_retina_detect's: cls_host[l] = [N, nloc[l], ldc[l]] (column a * C + c the logit of anchor loc * A + a and class c + 1, columns
+ * >= A * C never read), reg_host[l] = [N, nloc[l], ldr[l]] (columns 4a .. 4a+3); HOST arrays of L entries copied into the kernel's arguments.
+ * labels / reg_targets / n_pos as abr_retina_targets leaves them, anchor (l, loc, a) of image i at i * n + A * sum_{m<l} nloc[m] + loc * A + a.
+ *   losses[0] = sum of focal(x, label; gamma, alpha) over every anchor with label >= 0 and every class / float(n_pos + N)
+ *   losses[1] = sum of smooth_l1(beta) over the four deltas of the anchors with label > 0 / max(1, n_pos * regress_norm)
+ * both divided on the device.  The focal element is abr_sigmoid_focal_forward's (csrc/focal.h).  One launch; the sums go through per-workgroup
+ * partials added in a fixed order (no float atomics): the same inputs give the same bits, whatever else runs.
+ * Limits, checked before any launch (else ABR_E_INVALID): 1 <= L <= ABR_MAX_PYRAMID_LEVELS, C >= 1, 1 <= A <= 4096, ldc >= A * C, ldr >= 4A, both
+ * % 4 == 0, every N * nloc * ld and N * n in int32, beta > 0, non-null tables, 16-byte aligned outputs of the head.  N == 0 launches nothing. */
+int abr_retina_loss(const float* const* cls_host, const int* ldc_host, const float* const* reg_host, const int* ldr_host, const int* nloc_host,
+                    int L, int N, int A, int C, const int32_t* labels, const float* reg_targets, const int32_t* n_pos, float gamma, float alpha,
+                    float beta, float regress_norm, float* losses, void* stream);
+/* Its gradient, recomputed from the logits (the forward parks nothing).  g_cls / g_reg: the upstream gradients of the two losses (device scalars,
+ * no sync).  d_cls / d_reg: ONE allocation each, level l the [N, nloc[l], ld[l]] block at float offset N * sum_{m<l} nloc[m] * ld[m] (16-byte
+ * aligned as ld % 4 == 0).  One launch of plain 16-byte stores that writes EVERY element: no memset, no scatter, no atomics.
+ *   d_cls = focal'(x) * s, s = g_cls / float(n_pos + N) formed once in fp32 (the element of abr_sigmoid_focal_backward with d_losses = s: the
+ *     same bits); exactly 0 for ignored anchors and in the pad columns.
+ *   d_reg = smooth_l1'(beta) * (g_reg / max(1, n_pos * regress_norm)) at the deltas of the anchors with label > 0, exactly 0 elsewhere.
+ * Same argument checks. */
+int abr_retina_loss_backward(const float* const* cls_host, const int* ldc_host, const float* const* reg_host, const int* ldr_host,
+                             const int* nloc_host, int L, int N, int A, int C, const int32_t* labels, const float* reg_targets,
+                             const int32_t* n_pos, float gamma, float alpha, float beta, float regress_norm, const float* g_cls,
+                             const float* g_reg, float* d_cls, float* d_reg, void* stream);
 /* The RPN loss over a feature pyramid (rpn/loss.py:104-148 with rpn/utils.py:10-45; csrc/rpn_pyramid_loss.hip).  y_host[l] = device pointer of
  * level l's fused head output [N, nloc[l], Cf] (columns 0 .. A-1 the logits of anchors loc * A + a, A + 4a .. +3 their deltas; A, Cf and N are
  * shared by the levels: there is one head); y_host / nloc_host are HOST arrays of L entries copied into the kernel's arguments.  An image's anchors

@@ -66,11 +66,13 @@ def pool(maps, rois, res=RES, sr=SAMPLING):
     return _Pool.apply(rois, lv, res, sr, *maps), lv
 
 
-def neck(cs, params, mutate=None):
-    """cs: C2..C5; params {"fpn_inner1": (w, b), ..} -> [P2..P6] (fpn.py:51-79; the maps are each exactly twice the next, as tests/fpn_ref.py::up2)"""
+def neck(cs, params, mutate=None, first=1, top=True):
+    """cs: C2..C5; params {"fpn_inner1": (w, b), ..} -> [P2..P6] (fpn.py:51-79; the maps are each exactly twice the next, as tests/fpn_ref.py::up2).
+    first: the block number of cs[0] (RetinaNet's pyramid starts at C3: 2); top=False leaves LastLevelMaxPool's P6 out (tests/detector_retinanet_ref.py
+    appends LastLevelP6P7's maps itself)"""
     n = len(cs)
-    inner = lambda i, t: F.conv2d(t, *params["fpn_inner%d" % (i + 1)])                # noqa: E731
-    layer = lambda i, t: F.conv2d(t, *params["fpn_layer%d" % (i + 1)], padding=1)     # noqa: E731
+    inner = lambda i, t: F.conv2d(t, *params["fpn_inner%d" % (i + first)])                # noqa: E731
+    layer = lambda i, t: F.conv2d(t, *params["fpn_layer%d" % (i + first)], padding=1)     # noqa: E731
     last = inner(n - 1, cs[-1])
     ps = [layer(n - 1, last)]
     for i in range(n - 2, -1, -1):
@@ -78,6 +80,8 @@ def neck(cs, params, mutate=None):
         up = F.interpolate(last.detach() if mutate == "detach_topdown" else last, scale_factor=2, mode="nearest")
         last = inner(i, cs[i]) + up
         ps.insert(0, layer(i, last))
+    if not top:
+        return ps
     top = ps[-1].detach() if mutate == "drop_p6_grad" else ps[-1]
     ps.append(top[:, :, ::2, ::2])      # F.max_pool2d(x, 1, 2, 0)
     return ps
